@@ -2,7 +2,13 @@
 """Headline benchmark: training iterations / second (forward + backward + Adam + MSE) of 2D Gaussian
 splatting on a 4096x4096 synthetic image with 1,000,000 Gaussians (BASELINE.json metric / configs[3]).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`, `ms_per_step` and the figures of
+those same steps).  --full adds what takes runs of its own: the same steps timed again after iteration 200 and with the
+lean backward pass, the PSNR at iteration 199 against the CPU oracle's trajectory, the roofline and VALU-rate figures (one
+extra counting pass) and the CPU baseline.  --dump-outputs DIR (one GPU) writes what the last timed step computes from inputs
+that are the same in every run (replay_last_step(), dump_outputs()).
 
 One process per GPU.  With N > 1 and no launcher environment (WORLD_SIZE unset) this process only SPAWNS the N
 ranks -- `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py ...`
@@ -90,6 +96,62 @@ def cpu_baseline(W, H, n, threads):
 def kernel_source_digest():
     """Ties a recorded profile (profiles/traffic.json) to the kernels it measured: comments and whitespace do not count."""
     return importlib.import_module("2dgaussiansplatting_amd._build").kernel_source_digest()
+
+
+# --dump-outputs: rows kept per array (at most ~50 MB in all at the default workload)
+DUMP_ROWS = {"splats": 1 << 20, "adam": 1 << 17, "image": 1 << 18}
+
+
+def replay_last_step(S2D, t, one_step, args, device):
+    """--dump-outputs: the last timed step once more -- the same call of the same context, float-atomic gradient sums as
+    timed -- from inputs that are the same in every run.  The timed steps themselves cannot give those: their atomics add
+    each splat's per-tile gradients in an order that varies from run to run, and Adam with the reference's epsilon of
+    1e-15 (main.cpp:154) steps by about lr * sign(m) whatever the size of the gradient, so the last-bit differences of
+    gradients that cancel to almost nothing grow into whole learning-rate steps: after 25 iterations at 4096^2 / 10^6 two
+    runs differ by up to 0.17 in a few hundred parameters.  So the parameters and Adam state entering the last timed
+    iteration are recomputed with gradients summed in a fixed order (S2D_CFG_DETERMINISTIC, a context of its own), loaded
+    into the timed context, and that one iteration is run again by one_step().  From identical inputs one float-atomic step
+    differs between runs only by rounding (see dump_outputs).  Returns the iteration's MSE; the context then holds what
+    dump_outputs() writes."""
+    it = t.stats()["iterations"] - 1   # index of the last timed iteration (warm-up + steps - 1)
+    with S2D.Trainer(args.width, args.height, args.splats, device=device, rebin_interval=args.rebin_interval,
+                     fp16_images=args.fp16_images, deterministic=True) as d:
+        d.set_target_synthetic()
+        d.init()
+        d.step(it, want_mse=False)
+        splats, (adams, beta1t, beta2t, done) = d.get_splats(), d.get_adam()
+    t.set_splats(splats)
+    t.set_adam(adams, beta1t, beta2t, done)
+    one_step()
+    t.synchronize()
+    return t.sqerr_trace(done, 1) / (args.width * args.height * 3)
+
+
+def dump_outputs(out_dir, t, mse):
+    """What the timed step hands its caller (replay_last_step() has just run it), as .npy files in out_dir:
+      mse.npy     float64 [1]       the step's MSE (what main.cpp:807 prints)
+      splats.npy  float32 [k, 9]    the parameters after its Adam step (struct Splat's nine floats)
+      adam.npy    float32 [k, 18]   their Adam moments
+      image.npy   float32 [k, 4]    image0, the framebuffer of its forward pass, at k pixels
+    (The gradients are not an output: the Adam step zeroes them for the next iteration.)  Two runs with the same arguments
+    agree to rounding: framebuffer and MSE bit for bit; parameters and moments within about one ulp of each column's largest
+    magnitude (measured: 1.5e-7 of it), so compare those with a tolerance such as 1e-6 of it.  An array with more rows
+    than DUMP_ROWS allows keeps a fixed sample: the rows np.random.default_rng(0).choice(rows, k, replace=False), sorted --
+    the same rows in every run with the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def rows(a, budget):
+        if len(a) <= budget:
+            return a
+        return a[np.sort(np.random.default_rng(0).choice(len(a), budget, replace=False))]
+
+    arrays = {"mse": np.asarray(mse, dtype=np.float64),
+              "splats": rows(t.get_splats().view(np.float32).reshape(t.n, 9), DUMP_ROWS["splats"]),
+              "adam": rows(t.get_adam()[0].view(np.float32).reshape(t.n, 18), DUMP_ROWS["adam"]),
+              "image": rows(t.get_image_rows().reshape(-1, 4), DUMP_ROWS["image"])}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 STAGES = ["spawn", "start", "init", "selftest", "warmup", "timed", "psnr", "side-block", "report", "done"]
@@ -248,6 +310,108 @@ def spawn_ranks(n, argv, args):
     return res["rc"] if res["rc"] not in (None, 0) else 4
 
 
+def full_report(out, args, t, S2D, device, its, bwd_ms, lean, late, psnr_iter, sq200, slab_rows):
+    """--full: the figures beside the headline one, added to rank 0's record `out`: the side blocks (lean backward, the
+    nine-gradient steps after iteration 200), PSNR at iteration 199 against the CPU oracle's trajectory, the HBM roofline
+    (with the recorded PMC figures when they match this build), the VALU rate from one counting pass, the CPU baseline."""
+    import numpy as np
+    W, H, n, world = args.width, args.height, args.splats, out["n_gpus"]
+    # dominant kernel: raster_fused_kernel = forward + backward walk of every tile.  Algorithmic bytes per launch
+    # (DESIGN.md section 4, SURVEY.md section 8d's per-unit figures): per pixel of the slab the forward part writes
+    # the framebuffer (16 B), the backward part reads it (16 B) and the target (16 B); per splat the parameters are
+    # read once per pass (2 x 36 B) and the 9 gradient floats written once (36 B).  (The events also span the
+    # ~6 us squared-error reduction queued behind it.)
+    bwd_bytes = (24.0 if args.fp16_images else 48.0) * W * slab_rows + 108.0 * n  # fp16 images: 8 B per pixel access
+    bwd_s = bwd_ms * 1e-3
+    achieved = bwd_bytes / bwd_s / 1e9 if bwd_s > 0 else 0.0
+    # HBM traffic of that kernel from the PMC counters: a RECORDED figure (rocprofv3 cannot run inside this
+    # process), valid only for the kernel build and the launch it was measured on -- dropped otherwise
+    traffic, traffic_note, pmc = None, "no PMC pass recorded for this build / launch", None
+    tp = os.path.join(ROOT, "profiles", "traffic.json")
+    if os.path.exists(tp) and world == 1 and (W, H, n) == (4096, 4096, 1000000) and not args.fp16_images:
+        try:
+            tj = json.load(open(tp))
+            if tj.get("kernel_source_digest") == kernel_source_digest():
+                traffic = tj.get("dominant_kernel_bytes_per_launch")
+                traffic_note = "recorded: %s" % tj.get("source")
+                pmc = tj
+            else:
+                traffic_note = "profiles/traffic.json was measured on another kernel build (digest %s): dropped" % tj.get("kernel_source_digest")
+        except Exception:
+            pass
+    # "PSNR vs ref": the CPU oracle's trajectory on this very workload (tools/make_bench_reference_trace.py)
+    psnr_ref = None
+    rp = os.path.join(ROOT, "tests", "golden", "bench_reference_trace.json")
+    if os.path.exists(rp):
+        rj = json.load(open(rp))
+        if (rj["width"], rj["height"], rj["n_splats"]) == (W, H, n) and 0 <= psnr_iter < len(rj["mse"]) and not args.fp16_images:
+            psnr_ref = 10.0 * float(np.log10(255.0 ** 2 / rj["mse"][psnr_iter]))
+    psnr_gpu = (10.0 * float(np.log10(255.0 ** 2 / (float(sq200[0].item()) / (H * W * 3)))) if sq200 is not None and float(sq200[0].item()) > 0 else None)
+    out.update({
+        # side block, NOT in `value`: the same steps with dL/d(opacity) skipped (nothing reads it while "Optimize opacity" is
+        # off, main.cpp:317,735; what s2d_step does by itself), timed the same way
+        "iterations_per_s_lean": lean["iterations_per_s"] if lean else None,
+        "lean_backward": lean,
+        # the nine-gradient iteration again, later in the same run (NOT `value`): iterations get cheaper as training goes on
+        "iterations_per_s_after_200_iterations": late["iterations_per_s"] if late else None,
+        "nine_gradients_after_200_iterations": late,
+        "psnr_db_at_iteration": psnr_iter,
+        "psnr_db": psnr_gpu,
+        "psnr_ref_db": psnr_ref,  # the CPU oracle (reference loop) at the same iteration of the same workload
+        "psnr_delta_db": (psnr_gpu - psnr_ref) if (psnr_gpu is not None and psnr_ref is not None) else None,
+        # SURVEY.md section 8d prices this path in HBM bytes, so `roofline` is the HBM one; what actually bounds the kernel is
+        # named beside it (`bound_measured`): it issues vector instructions, the framebuffer traffic is ~6 % of the pipe
+        "roofline": {"bound": "hbm", "kernel": "raster_fused_kernel (all nine gradients: its NEED_OP instantiation)",
+                     "achieved": achieved, "peak": 8000.0,
+                     "unit": "GB/s", "frac": achieved / 8000.0, "traffic": traffic, "traffic_note": traffic_note,
+                     "kernel_ms": bwd_ms, "algorithmic_bytes_per_launch": bwd_bytes,
+                     "kernel_ms_note": "mean over the launches that did work; rocprofv3's AverageNs for this kernel also counts "
+                                       "one void ~20 us launch per list rebuild (profiles/r04/README.md)",
+                     "bound_measured": "valu-issue",
+                     "bound_measured_note": "vector-instruction issue, with the LDS pipe and per-wave latency within ~1.3x of it "
+                                            "(perturbation experiments, profiles/r03/r03_bound_experiments.txt; priced instruction "
+                                            "account ~93 % vector issue, profiles/r03/r03_tile_clock.txt); HBM is the idle resource"},
+    })
+    if pmc is not None and pmc.get("SQ_INSTS_VALU_per_launch"):
+        # counter-derived, from the same digest-tied PMC passes as `traffic` (per working launch of the dominant kernel)
+        valu = float(pmc["SQ_INSTS_VALU_per_launch"])
+        out["roofline"]["valu"] = {"wave_instructions_per_launch": valu, "gpu_cycles_per_launch": pmc.get("gpu_cycles_per_launch"),
+                                   "simd_cycles_per_valu_instruction": pmc.get("simd_cycles_per_valu_instruction"),
+                                   "lds_wave_instructions_per_launch": pmc.get("SQ_INSTS_LDS_per_launch"),
+                                   "salu_wave_instructions_per_launch": pmc.get("SQ_INSTS_SALU_per_launch"),
+                                   "source": pmc.get("sq_source")}
+    if world == 1:
+        # The path has no dense contraction (no MFMA) and the raster kernels are nowhere near bandwidth-bound, so beside the
+        # HBM roofline report the useful fp32 VALU rate: active (pixel, splat) pairs per pass, counted by the
+        # kernels in one extra untimed iteration, x 30 flop (forward, main.cpp:523-533) + 110 flop (backward,
+        # main.cpp:607-709) per pair (SURVEY.md section 8d), against the 157.3 TFLOP/s fp32 vector peak.
+        sp = t.get_splats()
+        with S2D.Trainer(W, H, n, device=device, count_pairs=True, fp16_images=args.fp16_images) as tc:
+            tc.set_target_synthetic()
+            tc.set_splats(sp)
+            tc.forward()
+            tc.backward()   # a counting context runs the two separate kernels (same walks as the fused one)
+            tc.synchronize()
+            cs = tc.stats()
+        flops = 30.0 * cs["fwd_active"] + 110.0 * cs["bwd_active"]
+        if "valu" in out["roofline"]:
+            # useful flops / issued lane-operations (64 lanes per wave instruction; no FMA contraction: one flop per lane-op)
+            out["roofline"]["valu"]["useful_lane_fraction"] = flops / (out["roofline"]["valu"]["wave_instructions_per_launch"] * 64.0)
+        out["compute"] = {"unit": "TFLOP/s", "achieved": flops * its / 1e12, "peak": 157.3,
+                          "frac": flops * its / 1e12 / 157.3, "active_pairs_per_pass": cs["bwd_active"],
+                          "visited_pairs_per_pass": cs["bwd_visited"], "staged_list_entries_per_pass": cs["bwd_staged"],
+                          "lanes_per_executed_wave_entry": cs["bwd_active"] / max(cs["bwd_wave_execs"], 1),
+                          "executed_wave_entries_per_pass": cs["bwd_wave_execs"],
+                          "note": "useful fp32 VALU flops only (no FMA contraction is allowed: one flop per instruction); the raster kernel sits "
+                                  "between vector issue, the LDS pipe and per-wave latency (DESIGN.md section 4, "
+                                  "profiles/r03/r03_bound_experiments.txt)"}
+    if world == 1 and not args.no_cpu_baseline:
+        threads = args.cpu_threads or host_cores()
+        out["cpu_baseline"] = cpu_baseline(W, H, n, threads)
+    else:
+        out["cpu_baseline"] = None
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -262,8 +426,14 @@ def main():
     ap.add_argument("--lean-block", dest="lean_block", action="store_true", default=None,
                     help="after the timed block (whose backward pass accumulates all nine gradients, like main.cpp:595-710), time the "
                          "same steps again with dL/d(opacity) skipped (what s2d_step does while optimizeOpacity is off, "
-                         "main.cpp:317,735) and report iterations_per_s_lean beside value.  Default: on for one GPU")
+                         "main.cpp:317,735) and report iterations_per_s_lean beside value.  With --full only; default: on for one GPU")
     ap.add_argument("--no-lean-block", dest="lean_block", action="store_false")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the side blocks (after iteration 200, lean backward), PSNR vs the oracle's "
+                         "trajectory, roofline / VALU-rate figures and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="one GPU: after the timed steps, run the last one again from inputs that are the same in every run "
+                         "and write what it computed to DIR/<name>.npy (see replay_last_step, dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--exchange", default=None, choices=["halo", "dense"],
@@ -280,6 +450,8 @@ def main():
                     help="only check the multi-process launch path: the ranks rendezvous, all-reduce their rank numbers "
                          "and rank 0 prints one JSON line; needs no GPU (tests/test_distributed_cpu.py)")
     args = ap.parse_args()
+    if args.dump_outputs and max(args.gpus, int(os.environ.get("WORLD_SIZE", "1"))) > 1:
+        sys.exit("bench.py: --dump-outputs needs --gpus 1 (replay_last_step recomputes one context's state)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:], args))
@@ -450,21 +622,29 @@ def main():
 
     done = t.stats()["iterations"]
     first = done - args.steps
-    # PSNR after a fixed 200 iterations: keep training, untimed, up to iteration 200, and
-    # read iteration 199's squared error from the device-side trace ring (it holds the last 65536 iterations)
-    stage(rank, "psnr")
-    extra = max(0, 200 - done)
-    for _ in range(extra):
-        one_step()
-    torch.cuda.synchronize()
-    psnr_iter = 199 if done + extra - 200 < 60000 else done + extra - 1
-    sq200 = torch.from_numpy(t.sqerr_trace(psnr_iter, 1)).cuda()
+    # the timed steps' squared errors, read from the device-side trace ring (it holds the last 65536 iterations); a rank's
+    # are those of its slab: summed over the ranks
+    sq = torch.from_numpy(t.sqerr_trace(first, args.steps)).cuda()
+    if dist is not None:
+        D.reduce_sqerr(sq, dist)
+    mse_last = float(sq[-1].item()) / (H * W * 3) if args.steps else float("nan")
+    sq200 = None
+    if args.full:
+        # PSNR after a fixed 200 iterations: keep training, untimed, up to iteration 200, and
+        # read iteration 199's squared error from the trace ring
+        stage(rank, "psnr")
+        extra = max(0, 200 - done)
+        for _ in range(extra):
+            one_step()
+        torch.cuda.synchronize()
+        psnr_iter = 199 if done + extra - 200 < 60000 else done + extra - 1
+        sq200 = torch.from_numpy(t.sqerr_trace(psnr_iter, 1)).cuda()
     # Side block, outside `value`: the same steps with dL/d(opacity) left out (S2D_BWD_SKIP_OPACITY_GRAD: what s2d_step
     # does by itself while "Optimize opacity" is off, because Adam reads dSplats.opacity only with it on, main.cpp:735) --
     # same trajectory, the NEED_OP = false instantiation of the raster kernel.
     lean = None
     late = None
-    want_lean = args.lean_block if args.lean_block is not None else world == 1
+    want_lean = args.full and (args.lean_block if args.lean_block is not None else world == 1)
     if want_lean and args.steps > 0:
         # ... and, first, the SAME nine-gradient steps timed again here, after iteration 200: an iteration gets cheaper as
         # training goes on (front splats sharpen, pixels saturate earlier), so `value` -- timed over the first iterations after
@@ -491,46 +671,10 @@ def main():
     stage(rank, "report")
     if dist is not None and sq200 is not None:
         D.reduce_sqerr(sq200, dist)
-    sq = torch.from_numpy(t.sqerr_trace(first, args.steps)).cuda()
-    bwd_ms = blk["kernel_ms"]
-    if dist is not None:
-        D.reduce_sqerr(sq, dist)
-    mse_last = float(sq[-1].item()) / (H * W * 3) if args.steps else float("nan")
     stats = t.stats()
 
     if rank == 0:
         its = args.steps / dt
-        # dominant kernel: raster_fused_kernel = forward + backward walk of every tile.  Algorithmic bytes per launch
-        # (SURVEY.md section 8d's per-unit figures): per pixel of the slab the forward part writes
-        # the framebuffer (16 B), the backward part reads it (16 B) and the target (16 B); per splat the parameters are
-        # read once per pass (2 x 36 B) and the 9 gradient floats written once (36 B).  (The events also span the
-        # ~6 us squared-error reduction queued behind it.)
-        bwd_bytes = (24.0 if args.fp16_images else 48.0) * W * (r1 - r0) + 108.0 * n  # fp16 images: 8 B per pixel access
-        bwd_s = bwd_ms * 1e-3
-        achieved = bwd_bytes / bwd_s / 1e9 if bwd_s > 0 else 0.0
-        # HBM traffic of that kernel from the PMC counters: a RECORDED figure (rocprofv3 cannot run inside this
-        # process), valid only for the kernel build and the launch it was measured on -- dropped otherwise
-        traffic, traffic_note, pmc = None, "no PMC pass recorded for this build / launch", None
-        tp = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tp) and world == 1 and (W, H, n) == (4096, 4096, 1000000) and not args.fp16_images:
-            try:
-                tj = json.load(open(tp))
-                if tj.get("kernel_source_digest") == kernel_source_digest():
-                    traffic = tj.get("dominant_kernel_bytes_per_launch")
-                    traffic_note = "recorded: %s" % tj.get("source")
-                    pmc = tj
-                else:
-                    traffic_note = "profiles/traffic.json was measured on another kernel build (digest %s): dropped" % tj.get("kernel_source_digest")
-            except Exception:
-                pass
-        # "PSNR vs ref": the CPU oracle's trajectory on this very workload (tools/make_bench_reference_trace.py)
-        psnr_ref = None
-        rp = os.path.join(ROOT, "tests", "golden", "bench_reference_trace.json")
-        if os.path.exists(rp):
-            rj = json.load(open(rp))
-            if (rj["width"], rj["height"], rj["n_splats"]) == (W, H, n) and 0 <= psnr_iter < len(rj["mse"]) and not args.fp16_images:
-                psnr_ref = 10.0 * float(np.log10(255.0 ** 2 / rj["mse"][psnr_iter]))
-        psnr_gpu = (10.0 * float(np.log10(255.0 ** 2 / (float(sq200[0].item()) / (H * W * 3)))) if sq200 is not None and float(sq200[0].item()) > 0 else None)
         steady = step_ms[~rebuilds] if (~rebuilds).any() else step_ms
         out = {
             "metric": "train iters/sec (fwd+bwd+Adam) + PSNR vs ref; 4K img, 1M splats",
@@ -546,13 +690,6 @@ def main():
             "iterations_per_s_steady_state": (1e3 / float(steady.mean())) if args.steps else None,
             "steps_with_list_rebuild": int(rebuilds.sum()),
             "backward_in_value": "all nine gradients of main.cpp:595-710: dL/dpos, dL/dsx, dL/dsy, dL/drot, dL/dcolour, dL/dopacity",
-            # side block, NOT in `value`: the same steps with dL/d(opacity) skipped (nothing reads it while "Optimize opacity" is
-            # off, main.cpp:317,735; what s2d_step does by itself), timed the same way
-            "iterations_per_s_lean": lean["iterations_per_s"] if lean else None,
-            "lean_backward": lean,
-            # the nine-gradient iteration again, later in the same run (NOT `value`): iterations get cheaper as training goes on
-            "iterations_per_s_after_200_iterations": late["iterations_per_s"] if late else None,
-            "nine_gradients_after_200_iterations": late,
             "value_window": "iterations %d..%d after init() (the dearest of a run)" % (first, first + args.steps - 1),
             "higher_is_better": True,
             "scaling": "strong",
@@ -576,10 +713,6 @@ def main():
                        "exchange": exchange},
             "mse_last": mse_last,
             "psnr_db_last": (10.0 * float(np.log10(255.0 ** 2 / mse_last)) if mse_last > 0 else None),
-            "psnr_db_at_iteration": psnr_iter,
-            "psnr_db": psnr_gpu,
-            "psnr_ref_db": psnr_ref,  # the CPU oracle (reference loop) at the same iteration of the same workload
-            "psnr_delta_db": (psnr_gpu - psnr_ref) if (psnr_gpu is not None and psnr_ref is not None) else None,
             "iterations_total": stats["iterations"],
             "exchange_rank0": ({"scheme": "halo", "held_fraction": float(((step.mask >> rank) & 1).float().mean().item()),
                                 "rows_exchanged_per_iteration": int(sum(step.splits)), "state_handovers": int(step.handed_over)}
@@ -587,57 +720,11 @@ def main():
                                {"scheme": "dense" if use_dist else "none", "replica_checksum_checks": getattr(step, "checks", 0)}),
             "pairs_binned_rank0": stats["pairs_binned"],
             "rebins_rank0": stats["rebins"],
-            # SURVEY.md section 8d prices this path in HBM bytes, so `roofline` is the HBM one; what actually bounds the kernel is
-            # named beside it (`bound_measured`): it issues vector instructions, the framebuffer traffic is ~6 % of the pipe
-            "roofline": {"bound": "hbm", "kernel": "raster_fused_kernel (all nine gradients: its NEED_OP instantiation)",
-                         "achieved": achieved, "peak": 8000.0,
-                         "unit": "GB/s", "frac": achieved / 8000.0, "traffic": traffic, "traffic_note": traffic_note,
-                         "kernel_ms": bwd_ms, "algorithmic_bytes_per_launch": bwd_bytes,
-                         "kernel_ms_note": "mean over the launches that did work; rocprofv3's AverageNs for this kernel also counts "
-                                           "one void ~20 us launch per list rebuild (profiles/r04/README.md)",
-                         "bound_measured": "valu-issue",
-                         "bound_measured_note": "vector-instruction issue, with the LDS pipe and per-wave latency within ~1.3x of it "
-                                                "(perturbation experiments, profiles/r03/r03_bound_experiments.txt; priced instruction "
-                                                "account ~93 % vector issue, profiles/r03/r03_tile_clock.txt); HBM is the idle resource"},
         }
-        if pmc is not None and pmc.get("SQ_INSTS_VALU_per_launch"):
-            # counter-derived, from the same digest-tied PMC passes as `traffic` (per working launch of the dominant kernel)
-            valu = float(pmc["SQ_INSTS_VALU_per_launch"])
-            out["roofline"]["valu"] = {"wave_instructions_per_launch": valu, "gpu_cycles_per_launch": pmc.get("gpu_cycles_per_launch"),
-                                       "simd_cycles_per_valu_instruction": pmc.get("simd_cycles_per_valu_instruction"),
-                                       "lds_wave_instructions_per_launch": pmc.get("SQ_INSTS_LDS_per_launch"),
-                                       "salu_wave_instructions_per_launch": pmc.get("SQ_INSTS_SALU_per_launch"),
-                                       "source": pmc.get("sq_source")}
-        if world == 1:
-            # The path has no dense contraction (no MFMA) and the raster kernels are nowhere near bandwidth-bound, so beside the
-            # HBM roofline report the useful fp32 VALU rate: active (pixel, splat) pairs per pass, counted by the
-            # kernels in one extra untimed iteration, x 30 flop (forward, main.cpp:523-533) + 110 flop (backward,
-            # main.cpp:607-709) per pair, against the 157.3 TFLOP/s fp32 vector peak.
-            sp = t.get_splats()
-            with S2D.Trainer(W, H, n, device=device, count_pairs=True, fp16_images=args.fp16_images) as tc:
-                tc.set_target_synthetic()
-                tc.set_splats(sp)
-                tc.forward()
-                tc.backward()   # a counting context runs the two separate kernels (same walks as the fused one)
-                tc.synchronize()
-                cs = tc.stats()
-            flops = 30.0 * cs["fwd_active"] + 110.0 * cs["bwd_active"]
-            if "valu" in out["roofline"]:
-                # useful flops / issued lane-operations (64 lanes per wave instruction; no FMA contraction: one flop per lane-op)
-                out["roofline"]["valu"]["useful_lane_fraction"] = flops / (out["roofline"]["valu"]["wave_instructions_per_launch"] * 64.0)
-            out["compute"] = {"unit": "TFLOP/s", "achieved": flops * its / 1e12, "peak": 157.3,
-                              "frac": flops * its / 1e12 / 157.3, "active_pairs_per_pass": cs["bwd_active"],
-                              "visited_pairs_per_pass": cs["bwd_visited"], "staged_list_entries_per_pass": cs["bwd_staged"],
-                              "lanes_per_executed_wave_entry": cs["bwd_active"] / max(cs["bwd_wave_execs"], 1),
-                              "executed_wave_entries_per_pass": cs["bwd_wave_execs"],
-                              "note": "useful fp32 VALU flops only (no FMA contraction is allowed: one flop per instruction); the raster kernel sits "
-                                      "between vector issue, the LDS pipe and per-wave latency (DESIGN.md section 4, "
-                                      "profiles/r03/r03_bound_experiments.txt)"}
-        if world == 1 and not args.no_cpu_baseline:
-            threads = args.cpu_threads or host_cores()
-            out["cpu_baseline"] = cpu_baseline(W, H, n, threads)
-        else:
-            out["cpu_baseline"] = None
+        if args.full:
+            full_report(out, args, t, S2D, device, its, blk["kernel_ms"], lean, late, psnr_iter, sq200, r1 - r0)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, t, replay_last_step(S2D, t, one_step, args, device))
         if dog is not None:
             dog.cancel()
         print(json.dumps(out))

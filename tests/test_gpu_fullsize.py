@@ -303,7 +303,7 @@ def test_bench_plain_command_two_ranks_gloo():
     for exchange in ("halo", "dense"):
         p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--exchange",
                             exchange, "--steps", "6", "--warmup", "2", "--width", "1024", "--height", "768", "--splats",
-                            "60000", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                            "60000", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900)
         assert p.returncode == 0, p.stderr[-3000:]
         lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
         assert len(lines) == 1, lines
@@ -322,7 +322,7 @@ def test_bench_one_rank_through_rccl_as_the_driver_launches_it():
     steps.  The result must be the single-process trajectory."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    common = ["--steps", "70", "--warmup", "2", "--width", "1024", "--height", "768", "--splats", "60000", "--no-cpu-baseline"]
+    common = ["--steps", "70", "--warmup", "2", "--width", "1024", "--height", "768", "--splats", "60000", "--no-cpu-baseline", "--full"]
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1"] + common, env=env, capture_output=True,
                        text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -346,6 +346,61 @@ def test_bench_one_rank_through_rccl_as_the_driver_launches_it():
         if exchange == "dense":
             assert out["exchange_rank0"]["replica_checksum_checks"] >= 1
         assert abs(out["psnr_db"] - plain["psnr_db"]) < 0.02, (out["psnr_db"], plain["psnr_db"])
+
+
+def _bench(*extra):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--width", "1024", "--height", "768",
+                        "--splats", "60000"] + [str(a) for a in extra], env=env, capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_times_only_its_steps():
+    """The command run for every change, `bench.py --gpus 1 --steps N --warmup W`: the warm-up and the timed steps and nothing
+    else (no side blocks, no PSNR run-on, no counting pass, no CPU baseline), and the headline fields."""
+    steps, warmup = 7, 2
+    out = _bench("--steps", steps, "--warmup", warmup)
+    assert out["metric"] == "train iters/sec (fwd+bwd+Adam) + PSNR vs ref; 4K img, 1M splats" and out["unit"] == "iterations/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "f32" and out["value"] > 0 and out["steps"] == steps
+    assert abs(out["ms_per_step"] - 1e3 / out["value"]) <= 1e-9 * out["ms_per_step"]
+    assert out["iterations_total"] == warmup + steps
+    assert not {"cpu_baseline", "psnr_db", "roofline", "compute", "lean_backward"} & set(out), sorted(out)
+
+
+def test_bench_dump_outputs_are_the_last_timed_step_from_the_same_inputs(tmp_path):
+    """--dump-outputs writes what the last timed step computes from inputs that are the same in every run: two runs agree to
+    rounding (framebuffer and MSE bit for bit), and against the same iterations run through s2d_step with gradients summed in
+    a fixed order they differ only by the order of the last step's gradient sums."""
+    W, H, n, steps, warmup = 1024, 768, 60000, 7, 2
+    runs = []
+    for run in ("a", "b"):
+        out = _bench("--steps", steps, "--warmup", warmup, "--dump-outputs", tmp_path / run)
+        assert out["iterations_total"] == warmup + steps and out["steps"] == steps
+        runs.append({name: np.load(tmp_path / run / (name + ".npy")) for name in ("mse", "splats", "adam", "image")})
+    a, b = runs
+    assert a["mse"].dtype == np.float64 and a["mse"].shape == (1,)
+    for name, shape in (("splats", (n, 9)), ("adam", (min(n, 1 << 17), 18)), ("image", (min(W * H, 1 << 18), 4))):
+        assert a[name].dtype == np.float32 and a[name].shape == shape and np.isfinite(a[name]).all(), (name, a[name].dtype, a[name].shape)
+    assert a["mse"].tobytes() == b["mse"].tobytes() and a["image"].tobytes() == b["image"].tobytes()
+
+    def close(x, y):   # column by column, against the column's largest magnitude
+        scale = np.maximum(np.abs(x).max(axis=0), 1e-30)
+        return (np.abs(x - y).max(axis=0) / scale).max()
+
+    _report("bench dump: two runs", {"splats": close(a["splats"], b["splats"]), "adam": close(a["adam"], b["adam"])})
+    assert close(a["splats"], b["splats"]) <= 1e-6 and close(a["adam"], b["adam"]) <= 1e-6
+    with S2D.Trainer(W, H, n, deterministic=True) as t:
+        t.set_target_synthetic()
+        t.init()
+        want = t.step(warmup + steps)
+        sp = t.get_splats().view(np.float32).reshape(n, 9)
+    assert abs(a["mse"][0] - want[-1]) <= 1e-9 * want[-1], (a["mse"], want[-1])
+    _report("bench dump vs s2d_step", {"splats": close(a["splats"], sp)})
+    assert close(a["splats"], sp) <= 1e-6
 
 
 def _fp16(a):

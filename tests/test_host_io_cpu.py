@@ -101,12 +101,12 @@ def test_jpeg_greyscale_and_corrupt(exe, tmp_path):
     conv(exe, tmp_path / "trunc.jpg", tmp_path / "t.ppm", ok=False)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/bin/squirrel_cls_mini.jpg"), reason="reference tree not present (GPU box)")
 def test_decoding_the_reference_jpegs_reproduces_the_committed_fixtures(exe, tmp_path):
-    """The host tool reads the reference's own inputs (main.cpp:257) and lands on exactly the pixels of
-    tests/golden/*.s2di (decoded once with PIL), i.e. on the sha256 prefixes recorded in SURVEY.md section 8c."""
+    """The host tool reads the reference's own inputs (main.cpp:257; copies of its bin/*.jpg in tests/golden) and lands on
+    exactly the pixels of tests/golden/*.s2di (decoded once with PIL), i.e. on the sha256 prefixes recorded in SURVEY.md
+    section 8c."""
     for jpg, fixture in (("squirrel_cls_mini.jpg", "squirrel_cls_mini_268x213.s2di"), ("squirrel_cls.jpg", "squirrel_cls_535x426.s2di")):
-        conv(exe, "/root/reference/bin/" + jpg, tmp_path / "o.s2di")
+        conv(exe, os.path.join(O.GOLDEN, jpg), tmp_path / "o.s2di")
         assert open(tmp_path / "o.s2di", "rb").read() == open(os.path.join(O.GOLDEN, fixture), "rb").read()
 
 

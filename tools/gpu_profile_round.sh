@@ -13,7 +13,7 @@ mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 run() { # name, rocprof args...
     local name=$1; shift
-    timeout -k 10 420 rocprofv3 "$@" --output-format csv -d "$out/$name" -- python3 bench.py --steps "$STEPS" --warmup 10 --no-cpu-baseline > "$out/$name.log" 2>&1 || { echo "$name FAILED"; tail -5 "$out/$name.log"; return 1; }
+    timeout -k 10 420 rocprofv3 "$@" --output-format csv -d "$out/$name" -- python3 bench.py --steps "$STEPS" --warmup 10 --full --no-cpu-baseline > "$out/$name.log" 2>&1 || { echo "$name FAILED"; tail -5 "$out/$name.log"; return 1; }
     echo "$name ok"
 }
 STEPS=200 run stats --kernel-trace --stats || exit 1
