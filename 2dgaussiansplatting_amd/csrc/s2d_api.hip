@@ -314,6 +314,37 @@ int rebuild_lists(s2d_ctx* c, int first = 0, int count = -1)
     return S2D_OK;
 }
 
+// What a raster pass of the context works on, for the lists of the splats [first, first + count) (count < 0: all of them).
+// A range's lists hold indices relative to its first splat, so every per-splat array is handed over from that splat on.
+RasterArgs raster_args(const s2d_ctx* c, int first = 0, int count = -1)
+{
+    RasterArgs a;
+    a.tile_off = c->d_tile_off; a.list = c->d_list; a.wave_masks = c->d_wave_masks;
+    a.proj = c->d_proj + first; a.grads = c->d_grads + (size_t)first * 9;
+    a.image0 = c->d_image0; a.image_ref = c->d_ref; a.tile_sqerr = c->d_tile_sqerr;
+    a.g = c->g; a.status = c->d_status; a.iteration = c->iterations; a.counters = c->d_counters;
+    a.state = c->d_state; a.any_alive = c->d_chunk_alive;
+    if (c->deterministic) // (det.now stays 0, no gather, until with_backward_walk)
+        a.det = DetGather{c->d_rects + first, c->d_offsets + first, c->d_counts + first, c->d_det_data, c->d_det_stamp,
+                          c->d_det_touched + first, 0u, count < 0 ? c->n : count};
+    a.half_images = c->half_images; a.count = (c->cfg.flags & S2D_CFG_COUNT_PAIRS) != 0; a.exact_exp = (c->cfg.flags & S2D_CFG_EXACT_EXP) != 0;
+    return a;
+}
+
+// The pass has a backward walk.  Deterministic mode: a fresh stamp for its slots (those of earlier passes become invalid).
+void with_backward_walk(s2d_ctx* c, RasterArgs& a, bool need_opacity_grad)
+{
+    a.need_opacity_grad = need_opacity_grad;
+    if (c->deterministic) a.det.now = ++c->det_epoch;
+}
+
+// The sum of the tile errors into ring slot `slot` of the trace, riding on another launch (slot < 0: none).
+SqerrJob sqerr_job(const s2d_ctx* c, int slot)
+{
+    if (slot < 0) return SqerrJob{nullptr, 0, nullptr, nullptr};
+    return SqerrJob{c->d_tile_sqerr, c->g.num_tiles, c->d_sqerr_trace + slot, c->d_tile_sqerr + c->g.num_tiles};
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Index-range ("chunked") rendering.  The reference's loops have no limit on the number of (pixel, splat) pairs
 // (main.cpp:492-536); 32-bit list positions have one, and long before it the list and mask buffers have a price.  A scene
@@ -343,12 +374,16 @@ int plan_chunks(s2d_ctx* c)
     return S2D_OK;
 }
 
-int build_chunk(s2d_ctx* c, int k)
+// The lists of range k (built unless the buffers hold them already), and what a raster pass over them works on.
+int build_chunk(s2d_ctx* c, int k, RasterArgs* a)
 {
-    if (c->chunk_built == k) return S2D_OK;
-    c->chunk_built = -1;
-    if (int rc = rebuild_lists(c, c->chunks[(size_t)k], c->chunks[(size_t)k + 1] - c->chunks[(size_t)k])) return rc;
-    c->chunk_built = k;
+    const int first = c->chunks[(size_t)k], count = c->chunks[(size_t)k + 1] - first;
+    if (c->chunk_built != k) {
+        c->chunk_built = -1;
+        if (int rc = rebuild_lists(c, first, count)) return rc;
+        c->chunk_built = k;
+    }
+    *a = raster_args(c, first, count); a->first = k == 0;
     return S2D_OK;
 }
 
@@ -356,16 +391,14 @@ int build_chunk(s2d_ctx* c, int k)
 // throughput cut-off any more (main.cpp:520: nothing later could change a pixel).
 int chunked_forward(s2d_ctx* c)
 {
-    const bool exact = (c->cfg.flags & S2D_CFG_EXACT_EXP) != 0;
     const int K = (int)c->chunks.size() - 1;
     c->chunks_used = 0;
     c->chunk_built = -1;
     for (int k = 0; k < K; k++) {
-        if (int rc = build_chunk(c, k)) return rc;
+        RasterArgs a;
+        if (int rc = build_chunk(c, k, &a)) return rc;
         S2D_HIP(c, hipMemsetAsync(c->d_chunk_alive, 0, sizeof(uint32_t), c->stream));
-        S2D_HIP(c, launch_raster_forward_chunk(c->d_tile_off, c->d_list, c->d_proj + c->chunks[(size_t)k], c->d_image0, c->half_images,
-                                               c->d_state, k == 0, c->d_wave_masks, c->g, c->d_status, c->iterations,
-                                               c->d_chunk_alive, exact, c->stream));
+        S2D_HIP(c, launch_raster(RasterPass::ForwardRange, a, c->stream));
         c->chunks_used = k + 1;
         if (k + 1 < K) {
             S2D_HIP(c, hipMemcpyAsync(c->h_total + 2, c->d_chunk_alive, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -379,20 +412,11 @@ int chunked_forward(s2d_ctx* c)
 // Backward pass over the same ranges (main.cpp:548-712), from a fresh per-pixel state; image0 holds the final colours.
 int chunked_backward(s2d_ctx* c, bool need_opacity_grad)
 {
-    const bool exact = (c->cfg.flags & S2D_CFG_EXACT_EXP) != 0;
     for (int k = 0; k < c->chunks_used; k++) {
-        if (int rc = build_chunk(c, k)) return rc;
-        const int first = c->chunks[(size_t)k], count = c->chunks[(size_t)k + 1] - first;
-        DetGather dg{};
-        if (c->deterministic) {
-            c->det_epoch++;
-            dg = DetGather{c->d_rects + first, c->d_offsets + first, c->d_counts + first, c->d_det_data, c->d_det_stamp,
-                           c->d_det_touched + first, c->det_epoch, count};
-        }
-        S2D_HIP(c, launch_raster_backward_chunk(c->d_tile_off, c->d_list, c->d_proj + first, c->d_image0, c->d_ref, c->half_images,
-                                                c->d_state, k == 0, c->d_wave_masks, c->d_grads + (size_t)first * 9, c->d_tile_sqerr,
-                                                c->g, need_opacity_grad, c->deterministic ? &dg : nullptr, c->d_status,
-                                                c->iterations, exact, c->stream));
+        RasterArgs a;
+        if (int rc = build_chunk(c, k, &a)) return rc;
+        with_backward_walk(c, a, need_opacity_grad);
+        S2D_HIP(c, launch_raster(RasterPass::BackwardRange, a, c->stream));
     }
     return S2D_OK;
 }
@@ -406,28 +430,16 @@ struct RasterJob {
     bool sum_sqerr = false;    // fused only, small images: the launch's last tile also adds up the tile errors
 };
 
-int launch_raster(s2d_ctx* c, bool optimistic, const RasterJob& job)
+int launch_job(s2d_ctx* c, bool optimistic, const RasterJob& job)
 {
-    const int abort_stamp = optimistic ? c->check_seq : 0;
-    const bool count = (c->cfg.flags & S2D_CFG_COUNT_PAIRS) != 0, exact = (c->cfg.flags & S2D_CFG_EXACT_EXP) != 0;
-    if (!job.fused) {
-        S2D_HIP(c, launch_raster_forward(c->d_tile_off, c->d_list, c->d_proj, c->d_image0, c->half_images, c->d_wave_masks,
-                                         c->g, c->d_status, abort_stamp, c->iterations, c->d_counters, count, exact, c->stream));
-        return S2D_OK;
+    RasterArgs a = raster_args(c);
+    a.abort_stamp = optimistic ? c->check_seq : 0;
+    if (job.fused) {
+        with_backward_walk(c, a, job.need_opacity_grad);
+        a.write_image = job.write_image;
+        a.sq = sqerr_job(c, job.sum_sqerr ? c->iterations % c->trace_cap : -1);
     }
-    DetGather dg{};
-    if (c->deterministic) {
-        c->det_epoch++; // a fresh stamp per backward pass (slots of earlier passes become invalid)
-        dg = DetGather{c->d_rects, c->d_offsets, c->d_counts, c->d_det_data, c->d_det_stamp, c->d_det_touched, c->det_epoch, c->n};
-    }
-    S2D_HIP(c, launch_raster_fused(c->d_tile_off, c->d_list, c->d_proj, c->d_image0, c->d_ref, c->half_images, c->d_wave_masks,
-                                   c->d_grads, c->d_tile_sqerr, c->g, job.need_opacity_grad, c->deterministic ? &dg : nullptr,
-                                   c->d_status, abort_stamp, c->iterations, job.write_image, exact,
-                                   job.sum_sqerr ? SqerrJob{c->d_tile_sqerr, c->g.num_tiles,
-                                                            c->d_sqerr_trace + c->iterations % c->trace_cap,
-                                                            c->d_tile_sqerr + c->g.num_tiles}
-                                                 : SqerrJob{nullptr, 0, nullptr, nullptr},
-                                   c->stream));
+    S2D_HIP(c, launch_raster(job.fused ? RasterPass::Fused : RasterPass::Forward, a, c->stream));
     return S2D_OK;
 }
 
@@ -481,7 +493,7 @@ int queue_raster(s2d_ctx* c, const RasterJob& job)
             S2D_HIP(c, hipEventRecord(c->ev_flag, c->stream));
             c->proj_fresh = true;
         }
-        if (int rc = launch_raster(c, true, job)) return rc;
+        if (int rc = launch_job(c, true, job)) return rc;
         S2D_HIP(c, hipEventSynchronize(c->ev_flag)); // the checking kernel, not the raster kernel
         rebuild = *(volatile int*)c->h_rebin_stamp == c->check_seq;
     }
@@ -509,7 +521,7 @@ int queue_raster(s2d_ctx* c, const RasterJob& job)
         if (rc != S2D_OK) return rc;
         c->proj_fresh = true;
         c->check_seq++; // the new lists cover the current parameters: a stamp that asked for them matches nothing now
-        if (int rc2 = launch_raster(c, false, job)) return rc2;
+        if (int rc2 = launch_job(c, false, job)) return rc2;
     }
     c->have_forward = !job.fused || job.write_image; // a fused launch told not to store image0 leaves an older frame there
     c->have_backward = false;
@@ -518,20 +530,24 @@ int queue_raster(s2d_ctx* c, const RasterJob& job)
 
 int queue_forward(s2d_ctx* c) { return queue_raster(c, RasterJob{}); }
 
+int flush_sqerr(s2d_ctx* c)
+{
+    if (!c->sqerr_deferred) return S2D_OK;
+    c->sqerr_deferred = false;
+    S2D_HIP(c, launch_sqerr_finalize(sqerr_job(c, c->last_sqerr_slot), c->d_status, c->iterations, c->stream));
+    return S2D_OK;
+}
+
 // Sum of the tile errors of the backward pass just queued -> ring slot of this iteration.  defer: leave it to the next
 // Adam launch, whose first workgroups do it on the way (one dispatch less per iteration); whoever wants the value
 // before that (s2d_get_mse, s2d_get_sqerr_trace) flushes it with the standalone kernel (flush_sqerr).
 int queue_sqerr(s2d_ctx* c, bool defer = false)
 {
-    const int slot = c->iterations % c->trace_cap;
-    c->last_sqerr_slot = slot;
+    c->last_sqerr_slot = c->iterations % c->trace_cap;
     c->have_backward = true;
+    c->sqerr_deferred = true;
     // (worth it only when the Adam launch has a workgroup per chunk: a 4-workgroup launch would walk 16 chunks each)
-    c->sqerr_deferred = defer && (c->n + 255) / 256 >= kSqerrChunks;
-    if (c->sqerr_deferred) return S2D_OK;
-    S2D_HIP(c, launch_sqerr_finalize(c->d_tile_sqerr, c->g.num_tiles, c->d_sqerr_trace + slot, c->d_tile_sqerr + c->g.num_tiles,
-                                     c->d_status, c->iterations, c->stream));
-    return S2D_OK;
+    return defer && (c->n + 255) / 256 >= kSqerrChunks ? S2D_OK : flush_sqerr(c);
 }
 
 int queue_backward(s2d_ctx* c, bool need_opacity_grad)
@@ -541,26 +557,10 @@ int queue_backward(s2d_ctx* c, bool need_opacity_grad)
         if (int rc = chunked_backward(c, need_opacity_grad)) return rc;
         return queue_sqerr(c);
     }
-    DetGather dg{};
-    if (c->deterministic) {
-        c->det_epoch++; // a fresh stamp per backward pass (slots of earlier passes become invalid)
-        dg = DetGather{c->d_rects, c->d_offsets, c->d_counts, c->d_det_data, c->d_det_stamp, c->d_det_touched, c->det_epoch, c->n};
-    }
-    S2D_HIP(c, launch_raster_backward(c->d_tile_off, c->d_list, c->d_proj, c->d_image0, c->d_ref, c->half_images,
-                                      c->d_wave_masks, c->d_grads,
-                                      c->d_tile_sqerr, c->g, need_opacity_grad, c->deterministic ? &dg : nullptr,
-                                      c->d_status, c->iterations, c->d_counters, (c->cfg.flags & S2D_CFG_COUNT_PAIRS) != 0,
-                                      (c->cfg.flags & S2D_CFG_EXACT_EXP) != 0, c->stream));
+    RasterArgs a = raster_args(c);
+    with_backward_walk(c, a, need_opacity_grad);
+    S2D_HIP(c, launch_raster(RasterPass::Backward, a, c->stream));
     return queue_sqerr(c);
-}
-
-int flush_sqerr(s2d_ctx* c)
-{
-    if (!c->sqerr_deferred) return S2D_OK;
-    c->sqerr_deferred = false;
-    S2D_HIP(c, launch_sqerr_finalize(c->d_tile_sqerr, c->g.num_tiles, c->d_sqerr_trace + c->last_sqerr_slot,
-                                     c->d_tile_sqerr + c->g.num_tiles, c->d_status, c->iterations, c->stream));
-    return S2D_OK;
 }
 
 // Forward + backward (+ squared error) of the current parameters through the fused kernel.  Pair counting is a
@@ -604,10 +604,7 @@ int queue_adam(s2d_ctx* c, uint32_t flags)
                            ((flags & S2D_STEP_OPTIMIZE_OPACITY) ? 1 : 0) | ((c->cfg.flags & S2D_CFG_ADAM_FP32) ? 2 : 0),
                            c->iterations, c->d_status,
                            fuse ? c->d_proj : nullptr, c->d_rects, c->check_seq, c->h_rebin_stamp, c->d_dormant,
-                           c->sqerr_deferred ? SqerrJob{c->d_tile_sqerr, c->g.num_tiles, c->d_sqerr_trace + c->last_sqerr_slot,
-                                                        c->d_tile_sqerr + c->g.num_tiles}
-                                             : SqerrJob{nullptr, 0, nullptr, nullptr},
-                           compact, c->stream));
+                           sqerr_job(c, c->sqerr_deferred ? c->last_sqerr_slot : -1), compact, c->stream));
     if (compact) c->compact_dirty = true;
     c->sqerr_deferred = false;
     if (fuse) S2D_HIP(c, hipEventRecord(c->ev_flag, c->stream));

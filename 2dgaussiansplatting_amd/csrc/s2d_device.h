@@ -182,13 +182,6 @@ hipError_t launch_tile_lists_from_rows(const uint32_t* entries, const uint32_t* 
                                        hipStream_t stream);
 
 // raster (s2d_raster.hip)
-// abort_stamp != 0: when status->rebin_needed equals it at kernel start the launch does nothing -- the lists it would
-// walk are stale and the host rebuilds them and launches again.  Every kernel of an iteration does nothing once a
-// parameter went non-finite in an earlier iteration (status->first_nonfinite_iter < iteration).
-hipError_t launch_raster_forward(const uint32_t* tile_off, const uint32_t* list, const ProjRec* proj, void* image0,
-                                 bool half_images, unsigned long long* wave_masks, Geometry g, const DeviceStatus* status,
-                                 int abort_stamp, int iteration, PairCounters* counters, bool count, bool exact_exp,
-                                 hipStream_t stream);
 // Deterministic gradient accumulation (S2D_CFG_DETERMINISTIC): instead of float atomics every tile stores its
 // partial gradient of a splat into the slot offsets[splat] + (position of the tile in the splat's emission
 // rectangle), stamped with the iteration and announced in the splat's `touched` word; a gather kernel then sums each
@@ -201,32 +194,50 @@ struct DetGather {
     float* data;      // [pair capacity][kDetStride]
     uint32_t* stamp;  // [pair capacity]
     uint32_t* touched; // [n]: per splat, which of its slots were written in this pass (zero between passes)
-    uint32_t now;     // iteration + 1 (never 0: 0 marks a slot that was never written)
+    uint32_t now;     // iteration + 1 (never 0: 0 marks a slot that was never written, and a pass without a gather)
     int n;
 };
-hipError_t launch_raster_backward(const uint32_t* tile_off, const uint32_t* list, const ProjRec* proj,
-                                  const void* image0, const void* image_ref, bool half_images,
-                                  const unsigned long long* wave_masks, float* grads, double* tile_sqerr, Geometry g,
-                                  bool need_opacity_grad, const DetGather* dg, const DeviceStatus* status, int iteration,
-                                  PairCounters* counters, bool count, bool exact_exp, hipStream_t stream);
-// Forward + backward walk of every tile in one launch (same results as the two launches above).
-hipError_t launch_raster_fused(const uint32_t* tile_off, const uint32_t* list, const ProjRec* proj, void* image0,
-                               const void* image_ref, bool half_images, unsigned long long* wave_masks, float* grads,
-                               double* tile_sqerr, Geometry g, bool need_opacity_grad, const DetGather* dg,
-                               const DeviceStatus* status, int abort_stamp, int iteration, bool write_image, bool exact_exp,
-                               SqerrJob sq, hipStream_t stream);
-// Index-range rendering (scenes beyond one set of lists; s2d_raster.hip "chunked", s2d_api.hip chunked_raster): the lists are
-// those of ONE index range of the splats (proj / grads / the DetGather arrays point at the range's first splat, list words
-// count from it); `state` carries (r, g, b, T) per pixel from range to range; first: start from (0, 0, 0, 1).
-hipError_t launch_raster_forward_chunk(const uint32_t* tile_off, const uint32_t* list, const ProjRec* proj, void* image0,
-                                       bool half_images, float4* state, bool first, unsigned long long* wave_masks, Geometry g,
-                                       const DeviceStatus* status, int iteration, uint32_t* any_alive, bool exact_exp,
-                                       hipStream_t stream);
-hipError_t launch_raster_backward_chunk(const uint32_t* tile_off, const uint32_t* list, const ProjRec* proj, const void* image0,
-                                        const void* image_ref, bool half_images, float4* state, bool first,
-                                        unsigned long long* wave_masks, float* grads, double* tile_sqerr, Geometry g,
-                                        bool need_opacity_grad, const DetGather* dg, const DeviceStatus* status, int iteration,
-                                        bool exact_exp, hipStream_t stream);
+enum class RasterPass {
+    Forward,
+    Backward,
+    Fused,         // forward + backward walk of every tile in one launch (same results as the two launches above)
+    ForwardRange,  // index-range rendering (scenes beyond one set of lists; s2d_raster.hip "chunked", s2d_api.hip
+    BackwardRange, // chunked_forward / chunked_backward): the lists are those of ONE index range of the splats
+};
+// What a raster pass works on; a member left at its default is not used.
+struct RasterArgs {
+    const uint32_t* tile_off = nullptr;
+    const uint32_t* list = nullptr; // (an index range's list words count from the range's first splat)
+    const ProjRec* proj = nullptr;  // proj / grads / the arrays of `det` start at the first splat of the lists
+    void* image0 = nullptr;
+    const void* image_ref = nullptr;
+    unsigned long long* wave_masks = nullptr;
+    float* grads = nullptr;
+    double* tile_sqerr = nullptr;
+    Geometry g{};
+    // Every kernel of an iteration does nothing once a parameter went non-finite in an earlier iteration
+    // (status->first_nonfinite_iter < iteration).
+    const DeviceStatus* status = nullptr;
+    int iteration = 0;
+    // != 0 (Forward, Fused): when status->rebin_needed equals it at kernel start the launch does nothing -- the lists it
+    // would walk are stale and the host rebuilds them and launches again.
+    int abort_stamp = 0;
+    PairCounters* counters = nullptr; // Forward, Backward with `count`
+    // index ranges: `state` carries (r, g, b, T) per pixel from range to range; first: start from (0, 0, 0, 1);
+    // *any_alive (ForwardRange) becomes != 0 when a pixel is still above the throughput cut-off behind the range
+    float4* state = nullptr;
+    bool first = false;
+    uint32_t* any_alive = nullptr;
+    bool write_image = false; // Fused: store image0
+    SqerrJob sq{};            // Fused: the launch's last tile also adds up the tile errors
+    DetGather det{};          // backward walks, det.now != 0: partial gradients into slots, then the gather kernel
+    // which variant of the kernel
+    bool half_images = false;
+    bool count = false; // Forward, Backward: pair counting into `counters`
+    bool exact_exp = false;
+    bool need_opacity_grad = false;
+};
+hipError_t launch_raster(RasterPass pass, const RasterArgs& a, hipStream_t stream);
 // slab ownership (s2d_halo.hip): `held` == nullptr means every splat is held (single rank, or replicated state)
 hipError_t launch_halo_masks(const float* splats, const uint8_t* held, int n, int world, const int* row_bounds, float margin,
                              uint32_t* masks, hipStream_t stream);
@@ -318,8 +329,7 @@ __device__ __forceinline__ void sqerr_reduce(const double* __restrict__ tile_sqe
     }
 }
 #endif
-hipError_t launch_sqerr_finalize(const double* tile_sqerr, int num_tiles, double* out, double* scratch,
-                                 const DeviceStatus* status, int iteration, hipStream_t stream);
+hipError_t launch_sqerr_finalize(SqerrJob sq, const DeviceStatus* status, int iteration, hipStream_t stream);
 
 // optimiser / init (s2d_optim.hip)
 hipError_t launch_init_splats(float* splats, float* adams, int n, int W, int H, hipStream_t stream);

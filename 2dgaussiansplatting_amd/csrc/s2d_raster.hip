@@ -29,6 +29,7 @@
 // tile's own slot of that splat, and a gather kernel sums each splat's slots in a fixed order (bitwise
 // reproducible gradients).
 #include <hip/hip_fp16.h>
+#include <type_traits>
 
 #include "s2d_device.h"
 
@@ -954,145 +955,85 @@ __global__ __launch_bounds__(256) void sqerr_finalize_kernel(const double* __res
 
 static inline unsigned raster_grid(int num_tiles) { return (unsigned)(((num_tiles + 7) / 8) * 8); }
 
-hipError_t launch_raster_forward(const uint32_t* tile_off, const uint32_t* list, const ProjRec* proj, void* image0,
-                                 bool half_images, unsigned long long* wave_masks, Geometry g, const DeviceStatus* status,
-                                 int abort_stamp, int iteration, PairCounters* counters, bool count, bool exact_exp,
-                                 hipStream_t stream)
+// Run-time flags -> template arguments: calls f(std::bool_constant<flag>{}...) for the values of (exact, count, half,
+// further flags...); a flag given as a std::bool_constant is not branched on.  Which variants exist is decided here and
+// nowhere else: exact exp is a validation mode on plain fp32 images without pair counting (s2d_create rejects the
+// combinations), so those kernels are never instantiated.  (The order of the flags is the order in which the variants are
+// instantiated, which the compiler's register allocation of two counting kernels was seen to depend on: exact goes first.)
+template <bool EXACT, bool COUNT, bool HALF, bool... MORE, typename F>
+static hipError_t with_variant(F&& f)
 {
-    if (g.num_tiles <= 0) return hipSuccess;
-    const dim3 grid(raster_grid(g.num_tiles)), block(256);
-#define S2D_LAUNCH_FWD(C, H) \
-    hipLaunchKernelGGL((raster_forward_kernel<C, H, false>), grid, block, 0, stream, tile_off, list, proj, image0, wave_masks, g, status, abort_stamp, iteration, counters)
-    if (exact_exp) { // validation mode: plain fp32 images, no pair counting (s2d_create rejects the combinations)
-        hipLaunchKernelGGL((raster_forward_kernel<false, false, true>), grid, block, 0, stream, tile_off, list, proj, image0,
-                           wave_masks, g, status, abort_stamp, iteration, counters);
-    } else if (count) {
-        if (half_images) S2D_LAUNCH_FWD(true, true); else S2D_LAUNCH_FWD(true, false);
-    } else {
-        if (half_images) S2D_LAUNCH_FWD(false, true); else S2D_LAUNCH_FWD(false, false);
+    if constexpr (EXACT && (COUNT || HALF)) return hipErrorInvalidValue;
+    else return f(std::bool_constant<EXACT>{}, std::bool_constant<COUNT>{}, std::bool_constant<HALF>{},
+                  std::bool_constant<MORE>{}...), hipSuccess;
+}
+template <bool... DONE, typename F, typename... REST>
+static hipError_t with_variant(F&& f, bool flag, REST... rest)
+{
+    return flag ? with_variant<DONE..., true>(f, rest...) : with_variant<DONE..., false>(f, rest...);
+}
+template <bool... DONE, typename F, bool FLAG, typename... REST>
+static hipError_t with_variant(F&& f, std::bool_constant<FLAG>, REST... rest)
+{
+    return with_variant<DONE..., FLAG>(f, rest...);
+}
+
+hipError_t launch_raster(RasterPass pass, const RasterArgs& a, hipStream_t stream)
+{
+    if (a.g.num_tiles <= 0) return hipSuccess;
+    const dim3 grid(raster_grid(a.g.num_tiles)), block(256);
+    const DetGather& dg = a.det;
+    const bool gather = dg.now != 0u && pass != RasterPass::Forward && pass != RasterPass::ForwardRange;
+    const DetSlots det{dg.rects, dg.offsets, dg.data, dg.stamp, dg.touched, dg.now};
+    const int first = a.first ? 1 : 0, wi = a.write_image ? 1 : 0;
+    const std::false_type no; // a flag the pass has no variants of
+    hipError_t e = hipErrorInvalidValue;
+    switch (pass) {
+    case RasterPass::Forward:
+        e = with_variant([&](auto exact, auto count, auto half) {
+            hipLaunchKernelGGL((raster_forward_kernel<count, half, exact>), grid, block, 0, stream, a.tile_off, a.list, a.proj,
+                               a.image0, a.wave_masks, a.g, a.status, a.abort_stamp, a.iteration, a.counters);
+        }, a.exact_exp, a.count, a.half_images);
+        break;
+    case RasterPass::Backward:
+        e = with_variant([&](auto exact, auto count, auto half, auto op, auto d) {
+            hipLaunchKernelGGL((raster_backward_kernel<count, op, half, d, exact>), grid, block, 0, stream, a.tile_off, a.list,
+                               a.proj, a.image0, a.image_ref, a.wave_masks, a.grads, a.tile_sqerr, a.g, det, a.status,
+                               a.iteration, a.counters);
+        }, a.exact_exp, a.count, a.half_images, a.need_opacity_grad, gather);
+        break;
+    case RasterPass::Fused: // (pair counting is a property of the separate kernels)
+        e = with_variant([&](auto exact, auto, auto half, auto op, auto d) {
+            hipLaunchKernelGGL((raster_fused_kernel<op, half, d, exact>), grid, block, 0, stream, a.tile_off, a.list, a.proj,
+                               a.image0, a.image_ref, a.wave_masks, a.grads, a.tile_sqerr, a.g, det, a.status, a.abort_stamp,
+                               a.iteration, wi, a.sq);
+        }, a.exact_exp, no, a.half_images, a.need_opacity_grad, gather);
+        break;
+    case RasterPass::ForwardRange:
+        e = with_variant([&](auto exact, auto, auto half) {
+            hipLaunchKernelGGL((raster_forward_chunk_kernel<half, exact>), grid, block, 0, stream, a.tile_off, a.list, a.proj,
+                               a.image0, a.state, first, a.wave_masks, a.g, a.status, a.iteration, a.any_alive);
+        }, a.exact_exp, no, a.half_images);
+        break;
+    case RasterPass::BackwardRange:
+        e = with_variant([&](auto exact, auto, auto half, auto op, auto d) {
+            hipLaunchKernelGGL((raster_backward_chunk_kernel<op, half, d, exact>), grid, block, 0, stream, a.tile_off, a.list,
+                               a.proj, a.image0, a.image_ref, a.state, first, a.wave_masks, a.grads, a.tile_sqerr, a.g, det,
+                               a.status, a.iteration);
+        }, a.exact_exp, no, a.half_images, a.need_opacity_grad, gather);
+        break;
     }
-#undef S2D_LAUNCH_FWD
+    if (e != hipSuccess) return e;
+    if (gather && dg.n > 0)
+        hipLaunchKernelGGL(gather_grads_kernel, dim3((dg.n + 255) / 256), dim3(256), 0, stream, dg.offsets, dg.counts, dg.n,
+                           dg.data, dg.stamp, dg.touched, dg.now, a.grads);
     return hipGetLastError();
 }
 
-hipError_t launch_raster_backward(const uint32_t* tile_off, const uint32_t* list, const ProjRec* proj,
-                                  const void* image0, const void* image_ref, bool half_images,
-                                  const unsigned long long* wave_masks, float* grads, double* tile_sqerr, Geometry g,
-                                  bool need_opacity_grad, const DetGather* dg, const DeviceStatus* status, int iteration,
-                                  PairCounters* counters, bool count, bool exact_exp, hipStream_t stream)
+hipError_t launch_sqerr_finalize(SqerrJob sq, const DeviceStatus* status, int iteration, hipStream_t stream)
 {
-    if (g.num_tiles <= 0) return hipSuccess;
-    DetSlots det{nullptr, nullptr, nullptr, nullptr, nullptr, 0u};
-    if (dg) det = DetSlots{dg->rects, dg->offsets, dg->data, dg->stamp, dg->touched, dg->now};
-    const dim3 grid(raster_grid(g.num_tiles)), block(256);
-#define S2D_LAUNCH_BWD(C, O, H, D)                                                                                       \
-    hipLaunchKernelGGL((raster_backward_kernel<C, O, H, D, false>), grid, block, 0, stream, tile_off, list, proj, image0, image_ref, \
-                       wave_masks, grads, tile_sqerr, g, det, status, iteration, counters)
-#define S2D_LAUNCH_BWD_D(C, O, H) do { if (dg) S2D_LAUNCH_BWD(C, O, H, true); else S2D_LAUNCH_BWD(C, O, H, false); } while (0)
-#define S2D_LAUNCH_BWD_H(C, O) do { if (half_images) S2D_LAUNCH_BWD_D(C, O, true); else S2D_LAUNCH_BWD_D(C, O, false); } while (0)
-    if (exact_exp) {
-#define S2D_LAUNCH_BWD_X(O, D)                                                                                           \
-    hipLaunchKernelGGL((raster_backward_kernel<false, O, false, D, true>), grid, block, 0, stream, tile_off, list, proj, image0, \
-                       image_ref, wave_masks, grads, tile_sqerr, g, det, status, iteration, counters)
-        if (need_opacity_grad) { if (dg) S2D_LAUNCH_BWD_X(true, true); else S2D_LAUNCH_BWD_X(true, false); }
-        else { if (dg) S2D_LAUNCH_BWD_X(false, true); else S2D_LAUNCH_BWD_X(false, false); }
-#undef S2D_LAUNCH_BWD_X
-    } else if (count) {
-        if (need_opacity_grad) S2D_LAUNCH_BWD_H(true, true); else S2D_LAUNCH_BWD_H(true, false);
-    } else {
-        if (need_opacity_grad) S2D_LAUNCH_BWD_H(false, true); else S2D_LAUNCH_BWD_H(false, false);
-    }
-#undef S2D_LAUNCH_BWD_H
-#undef S2D_LAUNCH_BWD_D
-#undef S2D_LAUNCH_BWD
-    if (dg && dg->n > 0)
-        hipLaunchKernelGGL(gather_grads_kernel, dim3((dg->n + 255) / 256), dim3(256), 0, stream, dg->offsets, dg->counts,
-                           dg->n, dg->data, dg->stamp, dg->touched, dg->now, grads);
-    return hipGetLastError();
-}
-
-hipError_t launch_raster_fused(const uint32_t* tile_off, const uint32_t* list, const ProjRec* proj, void* image0,
-                               const void* image_ref, bool half_images, unsigned long long* wave_masks, float* grads,
-                               double* tile_sqerr, Geometry g, bool need_opacity_grad, const DetGather* dg,
-                               const DeviceStatus* status, int abort_stamp, int iteration, bool write_image, bool exact_exp,
-                               SqerrJob sq, hipStream_t stream)
-{
-    if (g.num_tiles <= 0) return hipSuccess;
-    DetSlots det{nullptr, nullptr, nullptr, nullptr, nullptr, 0u};
-    if (dg) det = DetSlots{dg->rects, dg->offsets, dg->data, dg->stamp, dg->touched, dg->now};
-    const dim3 grid(raster_grid(g.num_tiles)), block(256);
-    const int wi = write_image ? 1 : 0;
-#define S2D_LAUNCH_FUSED(O, H, D, X)                                                                                       \
-    hipLaunchKernelGGL((raster_fused_kernel<O, H, D, X>), grid, block, 0, stream, tile_off, list, proj, image0, image_ref, \
-                       wave_masks, grads, tile_sqerr, g, det, status, abort_stamp, iteration, wi, sq)
-#define S2D_LAUNCH_FUSED_D(O, H, X) do { if (dg) S2D_LAUNCH_FUSED(O, H, true, X); else S2D_LAUNCH_FUSED(O, H, false, X); } while (0)
-    if (exact_exp) {
-        if (need_opacity_grad) S2D_LAUNCH_FUSED_D(true, false, true); else S2D_LAUNCH_FUSED_D(false, false, true);
-    } else if (half_images) {
-        if (need_opacity_grad) S2D_LAUNCH_FUSED_D(true, true, false); else S2D_LAUNCH_FUSED_D(false, true, false);
-    } else {
-        if (need_opacity_grad) S2D_LAUNCH_FUSED_D(true, false, false); else S2D_LAUNCH_FUSED_D(false, false, false);
-    }
-#undef S2D_LAUNCH_FUSED_D
-#undef S2D_LAUNCH_FUSED
-    if (dg && dg->n > 0)
-        hipLaunchKernelGGL(gather_grads_kernel, dim3((dg->n + 255) / 256), dim3(256), 0, stream, dg->offsets, dg->counts,
-                           dg->n, dg->data, dg->stamp, dg->touched, dg->now, grads);
-    return hipGetLastError();
-}
-
-hipError_t launch_raster_forward_chunk(const uint32_t* tile_off, const uint32_t* list, const ProjRec* proj, void* image0,
-                                       bool half_images, float4* state, bool first, unsigned long long* wave_masks, Geometry g,
-                                       const DeviceStatus* status, int iteration, uint32_t* any_alive, bool exact_exp,
-                                       hipStream_t stream)
-{
-    if (g.num_tiles <= 0) return hipSuccess;
-    const dim3 grid(raster_grid(g.num_tiles)), block(256);
-    const int f = first ? 1 : 0;
-#define S2D_LAUNCH_FC(H, X) \
-    hipLaunchKernelGGL((raster_forward_chunk_kernel<H, X>), grid, block, 0, stream, tile_off, list, proj, image0, state, f, wave_masks, g, status, iteration, any_alive)
-    if (exact_exp) S2D_LAUNCH_FC(false, true);
-    else if (half_images) S2D_LAUNCH_FC(true, false);
-    else S2D_LAUNCH_FC(false, false);
-#undef S2D_LAUNCH_FC
-    return hipGetLastError();
-}
-
-hipError_t launch_raster_backward_chunk(const uint32_t* tile_off, const uint32_t* list, const ProjRec* proj, const void* image0,
-                                        const void* image_ref, bool half_images, float4* state, bool first,
-                                        unsigned long long* wave_masks, float* grads, double* tile_sqerr, Geometry g,
-                                        bool need_opacity_grad, const DetGather* dg, const DeviceStatus* status, int iteration,
-                                        bool exact_exp, hipStream_t stream)
-{
-    if (g.num_tiles <= 0) return hipSuccess;
-    DetSlots det{nullptr, nullptr, nullptr, nullptr, nullptr, 0u};
-    if (dg) det = DetSlots{dg->rects, dg->offsets, dg->data, dg->stamp, dg->touched, dg->now};
-    const dim3 grid(raster_grid(g.num_tiles)), block(256);
-    const int f = first ? 1 : 0;
-#define S2D_LAUNCH_BC(O, H, D, X)                                                                                              \
-    hipLaunchKernelGGL((raster_backward_chunk_kernel<O, H, D, X>), grid, block, 0, stream, tile_off, list, proj, image0, image_ref, \
-                       state, f, wave_masks, grads, tile_sqerr, g, det, status, iteration)
-#define S2D_LAUNCH_BC_D(O, H, X) do { if (dg) S2D_LAUNCH_BC(O, H, true, X); else S2D_LAUNCH_BC(O, H, false, X); } while (0)
-    if (exact_exp) {
-        if (need_opacity_grad) S2D_LAUNCH_BC_D(true, false, true); else S2D_LAUNCH_BC_D(false, false, true);
-    } else if (half_images) {
-        if (need_opacity_grad) S2D_LAUNCH_BC_D(true, true, false); else S2D_LAUNCH_BC_D(false, true, false);
-    } else {
-        if (need_opacity_grad) S2D_LAUNCH_BC_D(true, false, false); else S2D_LAUNCH_BC_D(false, false, false);
-    }
-#undef S2D_LAUNCH_BC_D
-#undef S2D_LAUNCH_BC
-    if (dg && dg->n > 0)
-        hipLaunchKernelGGL(gather_grads_kernel, dim3((dg->n + 255) / 256), dim3(256), 0, stream, dg->offsets, dg->counts,
-                           dg->n, dg->data, dg->stamp, dg->touched, dg->now, grads);
-    return hipGetLastError();
-}
-
-hipError_t launch_sqerr_finalize(const double* tile_sqerr, int num_tiles, double* out, double* scratch,
-                                 const DeviceStatus* status, int iteration, hipStream_t stream)
-{
-    hipLaunchKernelGGL(sqerr_finalize_kernel, dim3(kSqerrChunks), dim3(256), 0, stream, tile_sqerr, num_tiles, out, scratch,
-                       status, iteration);
+    hipLaunchKernelGGL(sqerr_finalize_kernel, dim3(kSqerrChunks), dim3(256), 0, stream, sq.tile_sqerr, sq.num_tiles, sq.out,
+                       sq.scratch, status, iteration);
     return hipGetLastError();
 }
 
