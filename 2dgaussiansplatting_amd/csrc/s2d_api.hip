@@ -23,6 +23,7 @@
 #include <new>
 
 #include "s2d_device.h"
+#include "s2d_owned.h"
 
 using namespace s2d;
 
@@ -36,38 +37,37 @@ struct s2d_ctx {
     float lr = 0.05f;
 
     // parameters / optimiser state / gradients (AoS, the reference's layouts)
-    float* d_splats = nullptr;   // n * 9
-    float* d_adams = nullptr;    // n * 18
-    uint8_t* d_dormant = nullptr; // n: 1 = all of the splat's Adam moments are zero (adam_kernel keeps it; cleared with every outside write)
-    float* d_grads_own = nullptr;
+    DevBuf<float> d_splats;      // n * 9
+    DevBuf<float> d_adams;       // n * 18
+    DevBuf<uint8_t> d_dormant;   // n: 1 = all of the splat's Adam moments are zero (adam_kernel keeps it; cleared with every outside write)
+    DevBuf<float> d_grads_own;
     float* d_grads = nullptr;    // buffer in use (own or bound)
     // projection + binning
-    ProjRec* d_proj = nullptr;
-    TileRect* d_rects = nullptr;
-    uint32_t* d_counts = nullptr;
-    uint32_t* d_offsets = nullptr;
-    uint32_t* d_scan_temp = nullptr;
-    uint32_t* d_total = nullptr;
-    uint32_t* d_keys[2] = {nullptr, nullptr};
-    uint32_t* d_vals[2] = {nullptr, nullptr};
-    uint32_t* d_sort_temp = nullptr;
-    unsigned long long* d_wave_masks = nullptr; // 4 x u64 per listed pair: forward -> backward lane masks
+    DevBuf<ProjRec> d_proj;
+    DevBuf<TileRect> d_rects;
+    DevBuf<uint32_t> d_counts;
+    DevBuf<uint32_t> d_offsets;
+    DevBuf<uint32_t> d_scan_temp;
+    DevBuf<uint32_t> d_total;
+    DevBuf<uint32_t> d_keys[2];
+    DevBuf<uint32_t> d_vals[2];
+    DevBuf<uint32_t> d_sort_temp;
+    DevBuf<unsigned long long> d_wave_masks;    // 4 x u64 per listed pair: forward -> backward lane masks
     bool deterministic = false;                 // S2D_CFG_DETERMINISTIC
-    float* d_det_data = nullptr;                // [pair capacity][9] per-(tile, splat) partial gradients
-    uint32_t* d_det_stamp = nullptr;            // [pair capacity]
-    uint32_t* d_det_touched = nullptr;          // [n]: which of a splat's slots the current pass wrote (zero between passes)
+    DevBuf<float> d_det_data;                   // [pair capacity][9] per-(tile, splat) partial gradients
+    DevBuf<uint32_t> d_det_stamp;               // [pair capacity]
+    DevBuf<uint32_t> d_det_touched;             // [n]: which of a splat's slots the current pass wrote (zero between passes)
     uint32_t det_epoch = 0;                     // stamps written so far (monotone; 0 = never)
     uint64_t pair_capacity = 0;
-    uint32_t* d_tile_off = nullptr;
-    uint32_t* d_tile_first = nullptr; // per tile id (padded to a power of two): position of its first pair (last radix pass)
+    DevBuf<uint32_t> d_tile_off;
+    DevBuf<uint32_t> d_tile_first;    // per tile id (padded to a power of two): position of its first pair (last radix pass)
     // tile lists in two levels (s2d_tilelists.hip): (splat, tile row) entries sorted by row, then per-row counting sort by column
     bool two_level = false;            // tiles_x <= kTlMaxColumns and not S2D_CFG_GENERIC_BINNING
-    uint32_t* d_row_counts = nullptr;  // per splat: tile rows its rectangle covers
-    uint32_t* d_row_offsets = nullptr; // ... scanned
-    uint32_t* d_row_off = nullptr;     // [tiles_y + 1]: where each tile row's entries begin
-    uint32_t* d_chunk_base = nullptr;  // [tiles_y + 1]
-    uint32_t* d_tl_hist = nullptr;     // per (row, column, chunk) counts + scan workspace
-    size_t tl_hist_capacity = 0;       // words
+    DevBuf<uint32_t> d_row_counts;     // per splat: tile rows its rectangle covers
+    DevBuf<uint32_t> d_row_offsets;    // ... scanned
+    DevBuf<uint32_t> d_row_off;        // [tiles_y + 1]: where each tile row's entries begin
+    DevBuf<uint32_t> d_chunk_base;     // [tiles_y + 1]
+    DevBuf<uint32_t> d_tl_hist;        // per (row, column, chunk) counts + scan workspace
     uint32_t* d_list = nullptr; // == one of d_vals after the sort
     // Index-range ("chunked") rendering: when the (tile, splat) pairs of a scene exceed chunk_pairs -- at the latest 2^32 - 65536,
     // what 32-bit list positions can address -- the splats are cut into consecutive index ranges of at most that many
@@ -76,50 +76,50 @@ struct s2d_ctx {
     std::vector<int> chunks;             // range k = splats [chunks[k], chunks[k+1]); empty: one set of lists
     int chunks_used = 0;                 // ranges the last forward pass walked before every pixel was saturated
     int chunk_built = -1;                // the range whose lists are in the buffers now
-    float4* d_state = nullptr;           // per pixel of the slab: (r, g, b, T) carried from range to range
-    uint32_t* d_chunk_alive = nullptr;   // != 0: some pixel is still above the throughput cut-off after this range
+    DevBuf<float4> d_state;              // per pixel of the slab: (r, g, b, T) carried from range to range
+    DevBuf<uint32_t> d_chunk_alive;      // != 0: some pixel is still above the throughput cut-off after this range
     uint64_t pairs = 0;
     uint64_t rebins = 0;
     bool lists_valid = false;
     bool proj_fresh = false; // d_proj and d_status->rebin_needed describe the CURRENT parameters
-    hipEvent_t ev_total = nullptr; // recorded behind the copy of the pair count to the host (rebuild_lists)
-    hipEvent_t ev_flag = nullptr;  // recorded behind the kernel that ran the latest containment check
+    Event ev_total;                // recorded behind the copy of the pair count to the host (rebuild_lists)
+    Event ev_flag;                 // recorded behind the kernel that ran the latest containment check
     int check_seq = 1;             // its sequence number (both stamp words start at 0: nothing matches before a check): the stamp that kernel writes if a splat left its rectangle
-    int* h_rebin_stamp = nullptr;  // host-mapped copy of that stamp (written by the kernel, read after ev_flag)
+    HostBuf<int> h_rebin_stamp;    // host-mapped copy of that stamp (written by the kernel, read after ev_flag)
     int rebin_interval = 1;
     int since_rebin = 0;
     float margin = 0.0f;
     // images
     // image0 / imageRef (main.cpp:310, :254): the rows [row_begin, row_end) of this context's slab only -- a context
     // never touches another row, so a 1/8 slab of 8192^2 holds 2 x 134 MB instead of 2 x 1.07 GB
-    void* d_image0 = nullptr;  // RGBA32F, or 4 x fp16 per pixel with S2D_CFG_FP16_IMAGES
-    void* d_ref = nullptr;
+    DevBuf<uint8_t> d_image0;  // bytes: RGBA32F, or 4 x fp16 per pixel with S2D_CFG_FP16_IMAGES
+    DevBuf<uint8_t> d_ref;
     bool half_images = false;
     size_t pixel_bytes = sizeof(float4);
-    double* d_tile_sqerr = nullptr;
-    uint32_t* d_held_ids = nullptr;   // ... and their ascending id list, *d_held_count long, for the Adam kernel
-    uint32_t* d_held_count = nullptr;
-    uint32_t* d_held_work = nullptr;  // n words of scan workspace
+    DevBuf<double> d_tile_sqerr;
+    DevBuf<uint32_t> d_held_ids;      // ... and their ascending id list, *d_held_count long, for the Adam kernel
+    DevBuf<uint32_t> d_held_count;
+    DevBuf<uint32_t> d_held_work;     // n words of scan workspace
     // Compact held state: with slab ownership the Adam step touches only the splats the rank holds -- a seventh of them at
     // eight ranks, scattered through the id-indexed arrays (36- and 72-byte records, a cache line or two each).  Their
     // parameters and moments are therefore kept in compact arrays in the order of d_held_ids, which the Adam kernel reads
     // and writes in whole lines; the id-indexed arrays are brought up to date (compact_flush) before anything else reads
     // them -- a projection pass, a hold-set refresh, a row transfer, a read-back -- and the compact copy is made afresh
     // (compact_load) whenever the held set or the id-indexed arrays change from outside.
-    float* d_csplats = nullptr;  // n * 9 (capacity: every splat)
-    float* d_cadams = nullptr;   // n * 18
+    DevBuf<float> d_csplats;     // n * 9 (capacity: every splat)
+    DevBuf<float> d_cadams;      // n * 18
     bool compact_live = false;   // the compact arrays mirror the held splats
     bool compact_dirty = false;  // ... and are ahead of the id-indexed arrays (Adam steps since the last flush)
     bool compact_enabled = true; // S2D_COMPACT_HELD=0 turns it off (A/B)
-    uint8_t* d_held = nullptr; // slab ownership: 1 = this rank holds (updates) the splat; nullptr = all (s2d_halo_commit)
-    double* d_sqerr_trace = nullptr;
+    DevBuf<uint8_t> d_held;      // slab ownership: 1 = this rank holds (updates) the splat; nullptr = all (s2d_halo_commit)
+    DevBuf<double> d_sqerr_trace;
     int trace_cap = 1 << 16;
-    DeviceStatus* d_status = nullptr;
-    PairCounters* d_counters = nullptr;
+    DevBuf<DeviceStatus> d_status;
+    DevBuf<PairCounters> d_counters;
     // pinned host mirrors
-    uint32_t* h_total = nullptr;
-    DeviceStatus* h_status = nullptr;
-    double* h_trace = nullptr;          // kHostTrace squared errors: s2d_step reads its trace and the status word in ONE round trip
+    HostBuf<uint32_t> h_total;
+    HostBuf<DeviceStatus> h_status;
+    HostBuf<double> h_trace;            // kHostTrace squared errors: s2d_step reads its trace and the status word in ONE round trip
 
     // host-side state of the reference's main()
     float beta1t = 1.0f, beta2t = 1.0f; // main.cpp:274-275
@@ -132,6 +132,7 @@ struct s2d_ctx {
     bool sqerr_deferred = false; // the squared-error reduction of the last backward pass rides on the next Adam launch
     int last_sqerr_slot = -1;
     char err[512] = {0};
+    S2D_LOCAL ~s2d_ctx() = default; // (named only to keep it out of the library's exports, like the owners it runs)
 };
 
 namespace {
@@ -156,11 +157,12 @@ int fail(s2d_ctx* c, int code, const char* fmt, ...)
             return fail((c), S2D_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-template <typename T>
-hipError_t dev_alloc(T** p, size_t count)
-{
-    return hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
-}
+// Declared behind a temporary device buffer that work queued on `stream` uses: the stream is idle before the buffer
+// is freed, on whichever way the function is left.
+struct IdleAtExit {
+    hipStream_t stream;
+    ~IdleAtExit() { (void)hipStreamSynchronize(stream); }
+};
 
 int use_device(s2d_ctx* c)
 {
@@ -182,29 +184,18 @@ int ensure_pair_capacity(s2d_ctx* c, uint64_t need)
     uint64_t cap = std::max<uint64_t>(need + need / 4 + 4096, 1 << 16);
     if (cap > 0xFFFF0000ull) cap = 0xFFFF0000ull;
     S2D_HIP(c, hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 2; k++) c->d_keys[k].release(), c->d_vals[k].release(); // all six go before the first comes back
+    c->d_sort_temp.release(), c->d_wave_masks.release(), c->d_det_data.release(), c->d_det_stamp.release();
+    c->pair_capacity = 0; // (what is left if an allocation below fails)
     for (int k = 0; k < 2; k++) {
-        if (c->d_keys[k]) S2D_HIP(c, hipFree(c->d_keys[k]));
-        if (c->d_vals[k]) S2D_HIP(c, hipFree(c->d_vals[k]));
-        c->d_keys[k] = c->d_vals[k] = nullptr;
+        S2D_HIP(c, c->d_keys[k].alloc(cap));
+        S2D_HIP(c, c->d_vals[k].alloc(cap));
     }
-    if (c->d_sort_temp) S2D_HIP(c, hipFree(c->d_sort_temp));
-    if (c->d_wave_masks) S2D_HIP(c, hipFree(c->d_wave_masks));
-    if (c->d_det_data) S2D_HIP(c, hipFree(c->d_det_data));
-    if (c->d_det_stamp) S2D_HIP(c, hipFree(c->d_det_stamp));
-    c->d_sort_temp = nullptr;
-    c->d_wave_masks = nullptr;
-    c->d_det_data = nullptr;
-    c->d_det_stamp = nullptr;
-    c->pair_capacity = 0;
-    for (int k = 0; k < 2; k++) {
-        S2D_HIP(c, dev_alloc(&c->d_keys[k], cap));
-        S2D_HIP(c, dev_alloc(&c->d_vals[k], cap));
-    }
-    S2D_HIP(c, dev_alloc(&c->d_sort_temp, sort_temp_words((int64_t)cap)));
-    S2D_HIP(c, dev_alloc(&c->d_wave_masks, (size_t)cap * 4));
+    S2D_HIP(c, c->d_sort_temp.alloc(sort_temp_words((int64_t)cap)));
+    S2D_HIP(c, c->d_wave_masks.alloc((size_t)cap * 4));
     if (c->deterministic) {
-        S2D_HIP(c, dev_alloc(&c->d_det_data, (size_t)cap * kDetStride));
-        S2D_HIP(c, dev_alloc(&c->d_det_stamp, (size_t)cap));
+        S2D_HIP(c, c->d_det_data.alloc((size_t)cap * kDetStride));
+        S2D_HIP(c, c->d_det_stamp.alloc((size_t)cap));
         S2D_HIP(c, hipMemsetAsync(c->d_det_stamp, 0, (size_t)cap * sizeof(uint32_t), c->stream));
     }
     c->pair_capacity = cap;
@@ -215,14 +206,9 @@ int ensure_pair_capacity(s2d_ctx* c, uint64_t need)
 int ensure_tl_hist(s2d_ctx* c, uint64_t entries)
 {
     const size_t need = tl_workspace_words(entries, c->g.tiles_x, c->g.tiles_y);
-    if (need <= c->tl_hist_capacity) return S2D_OK;
+    if (need <= c->d_tl_hist.capacity()) return S2D_OK;
     S2D_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->d_tl_hist) S2D_HIP(c, hipFree(c->d_tl_hist));
-    c->d_tl_hist = nullptr;
-    c->tl_hist_capacity = 0;
-    const size_t cap = need + need / 4 + 4096;
-    S2D_HIP(c, dev_alloc(&c->d_tl_hist, cap));
-    c->tl_hist_capacity = cap;
+    S2D_HIP(c, c->d_tl_hist.alloc(need + need / 4 + 4096));
     return S2D_OK;
 }
 
@@ -369,8 +355,8 @@ int plan_chunks(s2d_ctx* c)
         acc += cnt[(size_t)i];
     }
     c->chunks.push_back(c->n);
-    if (!c->d_state) S2D_HIP(c, dev_alloc(&c->d_state, (size_t)c->g.W * (size_t)(c->g.row_end - c->g.row_begin)));
-    if (!c->d_chunk_alive) S2D_HIP(c, dev_alloc(&c->d_chunk_alive, 1));
+    if (!c->d_state) S2D_HIP(c, c->d_state.alloc((size_t)c->g.W * (size_t)(c->g.row_end - c->g.row_begin)));
+    if (!c->d_chunk_alive) S2D_HIP(c, c->d_chunk_alive.alloc(1));
     return S2D_OK;
 }
 
@@ -443,6 +429,37 @@ int launch_job(s2d_ctx* c, bool optimistic, const RasterJob& job)
     return S2D_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// What is current, and what makes it stale.  Three things are derived from the parameters, each from the one before:
+// the projection with its containment check (proj_fresh), the tile lists (lists_valid), and the frames -- image0 and
+// the gradients (have_forward, have_backward).  The functions that produce them set these flags (rebuild_lists,
+// queue_raster, queue_sqerr / queue_forward_backward, queue_adam); everything else names an event, and invalidate()
+// clears what the event reaches: Frames < Projection < Lists, a level with everything below it.
+//   target replaced (s2d_set_target, _synthetic): Frames.
+//   all splats replaced (s2d_init_splats, s2d_set_splats): Lists; splats_replaced() = state_written() + a fresh status
+//     word.  init also zeroes the gradients and restarts the counters, and flushes no compact copy first: every
+//     record, moments included, is new.
+//   some splat rows replaced (s2d_rows_scatter): Projection; state_written().  Not Lists: a row moves a splat a little,
+//     and the containment check of the projection that follows asks for new lists if it left its rectangle.
+//   moments replaced (s2d_set_adam, s2d_rows_scatter): nothing, what is drawn depends on the parameters only; state_written().
+//   held set changed (s2d_halo_commit): Lists if splats arrived, on the first commit and on the return to holding
+//     everything (the lists hold the held splats only); departures alone leave lists that still cover every held splat.
+//     compact_off() before, compact_load() after.
+//   Adam step queued (queue_adam): Projection, which the step itself renews when it projects (lists in re-use).
+//   non-finite step judged (judge_status): Frames; the counters are wound back to the failing step.
+//   index-range pass finished (queue_raster): the last range's lists are no lists of the scene, lists_valid stays false.
+// Before the id-indexed arrays are read or written from outside: compact_flush().  Before the iteration count changes
+// from outside: flush_sqerr(), whose ring slot is named by it.
+// ---------------------------------------------------------------------------------------------------------------------
+enum class Stale { Frames, Projection, Lists };
+
+void invalidate(s2d_ctx* c, Stale reach)
+{
+    c->have_forward = c->have_backward = false;
+    if (reach >= Stale::Projection) c->proj_fresh = false;
+    if (reach >= Stale::Lists) c->lists_valid = false;
+}
+
 // Compact held state (see s2d_ctx): bring the id-indexed parameter / moment arrays up to date ...
 int compact_flush(s2d_ctx* c)
 {
@@ -453,6 +470,14 @@ int compact_flush(s2d_ctx* c)
     return S2D_OK;
 }
 
+// ... for good: the held set is about to change, the id-indexed arrays take over until compact_load ...
+int compact_off(s2d_ctx* c)
+{
+    if (int rc = compact_flush(c)) return rc;
+    c->compact_live = false;
+    return S2D_OK;
+}
+
 // ... and make the compact copy afresh from them (the held set, or the arrays, changed from outside).
 int compact_load(s2d_ctx* c)
 {
@@ -460,12 +485,34 @@ int compact_load(s2d_ctx* c)
     c->compact_dirty = false;
     if (!c->d_held || !c->compact_enabled || c->n <= 0) return S2D_OK;
     if (!c->d_csplats) {
-        S2D_HIP(c, dev_alloc(&c->d_csplats, (size_t)c->n * 9));
-        S2D_HIP(c, dev_alloc(&c->d_cadams, (size_t)c->n * 18));
+        S2D_HIP(c, c->d_csplats.alloc((size_t)c->n * 9));
+        S2D_HIP(c, c->d_cadams.alloc((size_t)c->n * 18));
     }
     S2D_HIP(c, launch_compact_copy(c->d_splats, 9, c->d_held_ids, c->d_held_count, c->n, c->d_csplats, true, c->stream));
     S2D_HIP(c, launch_compact_copy(c->d_adams, 18, c->d_held_ids, c->d_held_count, c->n, c->d_cadams, true, c->stream));
     c->compact_live = true;
+    return S2D_OK;
+}
+
+// Splats or Adam moments have been written (queued) from outside the Adam kernel, all of them or some rows: the compact
+// copy is made again -- rows of held splats may be among them -- and nothing is known to be dormant any more (the next
+// step of every splat is a full one, which also applies the constraints to whatever was loaded).
+int state_written(s2d_ctx* c, bool all_rows)
+{
+    if (all_rows || c->compact_live)
+        if (int rc = compact_load(c)) return rc;
+    if (c->n > 0) S2D_HIP(c, hipMemsetAsync(c->d_dormant, 0, (size_t)c->n, c->stream));
+    return S2D_OK;
+}
+
+constexpr DeviceStatus kFreshStatus{0, INT_MAX, 0, 0}; // rebin_needed 0 matches no check (sequence numbers start at 1)
+
+// New parameters (init / set_splats): a non-finite event of the old ones no longer stops the queue.
+int splats_replaced(s2d_ctx* c)
+{
+    if (int rc = state_written(c, true)) return rc;
+    S2D_HIP(c, hipMemcpyAsync(c->d_status, &kFreshStatus, sizeof(DeviceStatus), hipMemcpyHostToDevice, c->stream));
+    invalidate(c, Stale::Lists);
     return S2D_OK;
 }
 
@@ -484,6 +531,7 @@ int queue_raster(s2d_ctx* c, const RasterJob& job)
     if (!c->have_target) return fail(c, S2D_E_STATE, "no target image set (s2d_set_target)");
     const bool scheduled = !c->lists_valid || c->rebin_interval <= 1 || c->since_rebin >= c->rebin_interval;
     bool rebuild = scheduled;
+    bool stored_image0 = !job.fused || job.write_image; // a fused launch told not to store image0 leaves an older frame there
     if (!scheduled) {
         if (!c->proj_fresh) { // parameters changed without a fused projection: project + check now
             if (int rc = compact_flush(c)) return rc;
@@ -503,27 +551,24 @@ int queue_raster(s2d_ctx* c, const RasterJob& job)
                                   c->two_level ? c->d_row_counts : nullptr, c->d_status, 0, nullptr, c->stream));
         c->chunks.clear();
         int rc = rebuild_lists(c);
+        if (rc != S2D_OK && rc != kNeedChunks) return rc;
+        if (rc == kNeedChunks && (c->cfg.flags & S2D_CFG_COUNT_PAIRS))
+            return fail(c, S2D_E_NOMEM, "pair counting (S2D_CFG_COUNT_PAIRS) is not available for scenes beyond %llu (tile, splat) pairs",
+                        (unsigned long long)c->chunk_pairs);
+        c->proj_fresh = true;
+        c->check_seq++; // the new lists cover the current parameters: a stamp that asked for them matches nothing now
         if (rc == kNeedChunks) {
             // more pairs than one set of lists may hold: render by index ranges (every pass rebuilds: lists_valid stays false)
-            if (c->cfg.flags & S2D_CFG_COUNT_PAIRS)
-                return fail(c, S2D_E_NOMEM, "pair counting (S2D_CFG_COUNT_PAIRS) is not available for scenes beyond %llu (tile, splat) pairs",
-                            (unsigned long long)c->chunk_pairs);
             c->lists_valid = false;
-            c->proj_fresh = true;
-            c->check_seq++;
             if ((rc = plan_chunks(c)) != S2D_OK) return rc;
             if ((rc = chunked_forward(c)) != S2D_OK) return rc;
             if (job.fused && (rc = chunked_backward(c, job.need_opacity_grad)) != S2D_OK) return rc;
-            c->have_forward = true; // the forward pass over the ranges always stores image0
-            c->have_backward = false;
-            return S2D_OK;
+            stored_image0 = true; // the forward pass over the ranges always stores it
+        } else if ((rc = launch_job(c, false, job)) != S2D_OK) {
+            return rc;
         }
-        if (rc != S2D_OK) return rc;
-        c->proj_fresh = true;
-        c->check_seq++; // the new lists cover the current parameters: a stamp that asked for them matches nothing now
-        if (int rc2 = launch_job(c, false, job)) return rc2;
     }
-    c->have_forward = !job.fused || job.write_image; // a fused launch told not to store image0 leaves an older frame there
+    c->have_forward = stored_image0;
     c->have_backward = false;
     return S2D_OK;
 }
@@ -608,40 +653,31 @@ int queue_adam(s2d_ctx* c, uint32_t flags)
     if (compact) c->compact_dirty = true;
     c->sqerr_deferred = false;
     if (fuse) S2D_HIP(c, hipEventRecord(c->ev_flag, c->stream));
-    c->proj_fresh = fuse;
+    invalidate(c, Stale::Projection);
+    c->proj_fresh = fuse; // (then the step projected what it wrote)
     c->iterations++; // main.cpp:809
     c->since_rebin++;
-    c->have_forward = false;
-    c->have_backward = false;
     return S2D_OK;
 }
 
-// Splats or Adam moments are about to be written from outside the Adam kernel: nothing is known to be dormant any more
-// (the next step of every splat is a full one, which also applies the constraints to whatever was loaded).
-int clear_dormant(s2d_ctx* c)
+int queue_status_read(s2d_ctx* c) // -> h_status, valid once the stream has been synchronised
 {
-    if (c->n > 0) S2D_HIP(c, hipMemsetAsync(c->d_dormant, 0, (size_t)c->n, c->stream));
+    S2D_HIP(c, hipMemcpyAsync(c->h_status, c->d_status, sizeof(DeviceStatus), hipMemcpyDeviceToHost, c->stream));
     return S2D_OK;
 }
 
-// New parameters (init / set_splats): a non-finite event of the old ones no longer stops the queue.
-int reset_status(s2d_ctx* c)
+// Entries [first, first + count) of the squared-error trace (a ring of trace_cap slots) -> out, queued.
+int queue_trace_read(s2d_ctx* c, int first, int count, double* out)
 {
-    static const DeviceStatus fresh{0, INT_MAX, 0, 0}; // rebin_needed 0 matches no check (sequence numbers start at 1)
-    S2D_HIP(c, hipMemcpyAsync(c->d_status, &fresh, sizeof(DeviceStatus), hipMemcpyHostToDevice, c->stream));
+    for (int got = 0; got < count;) {
+        const int slot = (first + got) % c->trace_cap, run = std::min(count - got, c->trace_cap - slot);
+        S2D_HIP(c, hipMemcpyAsync(out + got, c->d_sqerr_trace + slot, (size_t)run * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        got += run;
+    }
     return S2D_OK;
 }
 
 // The status word has been copied to h_status and the stream synchronised: act on it.
-int judge_status(s2d_ctx* c);
-
-int check_status(s2d_ctx* c)
-{
-    S2D_HIP(c, hipMemcpyAsync(c->h_status, c->d_status, sizeof(DeviceStatus), hipMemcpyDeviceToHost, c->stream));
-    S2D_HIP(c, hipStreamSynchronize(c->stream));
-    return judge_status(c);
-}
-
 int judge_status(s2d_ctx* c)
 {
     if (c->h_status->nonfinite) {
@@ -654,7 +690,7 @@ int judge_status(s2d_ctx* c)
             c->beta1t = b1;
             c->beta2t = b2;
             c->iterations = k + 1;
-            c->have_forward = c->have_backward = false;
+            invalidate(c, Stale::Frames);
         }
         return fail(c, S2D_E_NONFINITE, "non-finite parameter after iteration %d (the reference abort()s, main.cpp:752-785)", k);
     }
@@ -662,6 +698,13 @@ int judge_status(s2d_ctx* c)
     c->good_beta2t = c->beta2t;
     c->good_iterations = c->iterations;
     return S2D_OK;
+}
+
+int check_status(s2d_ctx* c)
+{
+    if (int rc = queue_status_read(c)) return rc;
+    S2D_HIP(c, hipStreamSynchronize(c->stream));
+    return judge_status(c);
 }
 
 double mse_norm(const s2d_ctx* c) { return (double)((long long)c->g.H * c->g.W * 3); }
@@ -718,19 +761,19 @@ int s2d_create(const s2d_config* cfg, s2d_ctx** out)
 
     const size_t n = std::max<size_t>((size_t)c->n, 1);           // >= 1 so that n == 0 still has buffers
     const size_t px = (size_t)g.W * (size_t)(g.row_end - g.row_begin); // pixels of the slab: all this context stores
-    S2D_HIP(c, dev_alloc(&c->d_splats, n * 9));
-    S2D_HIP(c, dev_alloc(&c->d_adams, n * 18));
-    S2D_HIP(c, dev_alloc(&c->d_dormant, n));
-    S2D_HIP(c, dev_alloc(&c->d_grads_own, n * 9));
+    S2D_HIP(c, c->d_splats.alloc(n * 9));
+    S2D_HIP(c, c->d_adams.alloc(n * 18));
+    S2D_HIP(c, c->d_dormant.alloc(n));
+    S2D_HIP(c, c->d_grads_own.alloc(n * 9));
     c->d_grads = c->d_grads_own;
-    S2D_HIP(c, dev_alloc(&c->d_proj, n));
-    S2D_HIP(c, dev_alloc(&c->d_rects, n));
-    S2D_HIP(c, dev_alloc(&c->d_counts, n));
-    S2D_HIP(c, dev_alloc(&c->d_offsets, n));
-    S2D_HIP(c, dev_alloc(&c->d_scan_temp, scan_temp_words((int64_t)n)));
-    S2D_HIP(c, dev_alloc(&c->d_total, 4)); // [0] pairs, [1] (splat, tile row) entries
-    S2D_HIP(c, dev_alloc(&c->d_tile_off, (size_t)g.num_tiles + 1));
-    S2D_HIP(c, dev_alloc(&c->d_tile_first, ((size_t)1 << key_bits_for(g.num_tiles)) + tile_first_temp_words(g.num_tiles))); // + chunk minima
+    S2D_HIP(c, c->d_proj.alloc(n));
+    S2D_HIP(c, c->d_rects.alloc(n));
+    S2D_HIP(c, c->d_counts.alloc(n));
+    S2D_HIP(c, c->d_offsets.alloc(n));
+    S2D_HIP(c, c->d_scan_temp.alloc(scan_temp_words((int64_t)n)));
+    S2D_HIP(c, c->d_total.alloc(4)); // [0] pairs, [1] (splat, tile row) entries
+    S2D_HIP(c, c->d_tile_off.alloc((size_t)g.num_tiles + 1));
+    S2D_HIP(c, c->d_tile_first.alloc(((size_t)1 << key_bits_for(g.num_tiles)) + tile_first_temp_words(g.num_tiles))); // + chunk minima
     c->two_level = g.tiles_x <= kTlMaxColumns && !(cfg->flags & S2D_CFG_GENERIC_BINNING);
     if (const char* e = getenv("S2D_COMPACT_HELD")) c->compact_enabled = atoi(e) != 0;
     if (const char* e = getenv("S2D_CHUNK_PAIRS")) { // pairs per index range (tests; default 2^30, never beyond 32-bit positions)
@@ -738,31 +781,31 @@ int s2d_create(const s2d_config* cfg, s2d_ctx** out)
         if (v > 0) c->chunk_pairs = std::min<unsigned long long>(v, 0xFFFF0000ull - 1);
     }
     if (c->two_level) {
-        S2D_HIP(c, dev_alloc(&c->d_row_counts, n));
-        S2D_HIP(c, dev_alloc(&c->d_row_offsets, n));
-        S2D_HIP(c, dev_alloc(&c->d_row_off, (size_t)g.tiles_y + 1));
-        S2D_HIP(c, dev_alloc(&c->d_chunk_base, (size_t)g.tiles_y + 1));
+        S2D_HIP(c, c->d_row_counts.alloc(n));
+        S2D_HIP(c, c->d_row_offsets.alloc(n));
+        S2D_HIP(c, c->d_row_off.alloc((size_t)g.tiles_y + 1));
+        S2D_HIP(c, c->d_chunk_base.alloc((size_t)g.tiles_y + 1));
     }
     c->deterministic = (cfg->flags & S2D_CFG_DETERMINISTIC) != 0;
     if (c->deterministic) {
-        S2D_HIP(c, dev_alloc(&c->d_det_touched, n));
+        S2D_HIP(c, c->d_det_touched.alloc(n));
         S2D_HIP(c, hipMemset(c->d_det_touched, 0, n * sizeof(uint32_t)));
     }
     c->half_images = (cfg->flags & S2D_CFG_FP16_IMAGES) != 0;
     c->pixel_bytes = c->half_images ? 8 : sizeof(float4);
-    S2D_HIP(c, hipMalloc(&c->d_image0, px * c->pixel_bytes));
-    S2D_HIP(c, hipMalloc(&c->d_ref, px * c->pixel_bytes));
-    S2D_HIP(c, dev_alloc(&c->d_tile_sqerr, (size_t)g.num_tiles + kSqerrScratchDoubles)); // + finalize scratch
+    S2D_HIP(c, c->d_image0.alloc(px * c->pixel_bytes));
+    S2D_HIP(c, c->d_ref.alloc(px * c->pixel_bytes));
+    S2D_HIP(c, c->d_tile_sqerr.alloc((size_t)g.num_tiles + kSqerrScratchDoubles)); // + finalize scratch
     S2D_HIP(c, hipMemset(c->d_tile_sqerr + g.num_tiles, 0, kSqerrScratchDoubles * sizeof(double)));
-    S2D_HIP(c, dev_alloc(&c->d_sqerr_trace, (size_t)c->trace_cap));
-    S2D_HIP(c, dev_alloc(&c->d_status, 1));
-    S2D_HIP(c, dev_alloc(&c->d_counters, 1));
-    S2D_HIP(c, hipEventCreateWithFlags(&c->ev_flag, hipEventDisableTiming));
-    S2D_HIP(c, hipEventCreateWithFlags(&c->ev_total, hipEventDisableTiming));
-    S2D_HIP(c, hipHostMalloc((void**)&c->h_total, 64, hipHostMallocMapped));
-    S2D_HIP(c, hipHostMalloc((void**)&c->h_status, sizeof(DeviceStatus), hipHostMallocDefault));
-    S2D_HIP(c, hipHostMalloc((void**)&c->h_trace, kHostTrace * sizeof(double), hipHostMallocDefault));
-    S2D_HIP(c, hipHostMalloc((void**)&c->h_rebin_stamp, 64, hipHostMallocMapped));
+    S2D_HIP(c, c->d_sqerr_trace.alloc((size_t)c->trace_cap));
+    S2D_HIP(c, c->d_status.alloc(1));
+    S2D_HIP(c, c->d_counters.alloc(1));
+    S2D_HIP(c, c->ev_flag.create(hipEventDisableTiming));
+    S2D_HIP(c, c->ev_total.create(hipEventDisableTiming));
+    S2D_HIP(c, c->h_total.alloc(16, hipHostMallocMapped)); // 64 bytes each for the two words kernels write through
+    S2D_HIP(c, c->h_status.alloc(1, hipHostMallocDefault));
+    S2D_HIP(c, c->h_trace.alloc(kHostTrace, hipHostMallocDefault));
+    S2D_HIP(c, c->h_rebin_stamp.alloc(16, hipHostMallocMapped));
     *c->h_rebin_stamp = 0;
 
     S2D_HIP(c, hipMemsetAsync(c->d_splats, 0, n * 9 * sizeof(float), c->stream));
@@ -773,8 +816,7 @@ int s2d_create(const s2d_config* cfg, s2d_ctx** out)
     S2D_HIP(c, hipMemsetAsync(c->d_ref, 0, px * c->pixel_bytes, c->stream));
     S2D_HIP(c, hipMemsetAsync(c->d_sqerr_trace, 0, (size_t)c->trace_cap * sizeof(double), c->stream));
     S2D_HIP(c, hipMemsetAsync(c->d_counters, 0, sizeof(PairCounters), c->stream));
-    DeviceStatus st0{0, INT_MAX, 0, 0};
-    *c->h_status = st0;
+    *c->h_status = kFreshStatus;
     S2D_HIP(c, hipMemcpyAsync(c->d_status, c->h_status, sizeof(DeviceStatus), hipMemcpyHostToDevice, c->stream));
     S2D_HIP(c, hipStreamSynchronize(c->stream));
     // ~16 tiles per splat at init() scales; grown on demand
@@ -786,24 +828,12 @@ int s2d_create(const s2d_config* cfg, s2d_ctx** out)
 void s2d_destroy(s2d_ctx* c)
 {
     if (!c) return;
-    if (hipSetDevice(c->device) == hipSuccess) {
-        if (c->stream) (void)hipStreamSynchronize(c->stream);
-        void* ptrs[] = {c->d_splats, c->d_adams, c->d_dormant, c->d_grads_own, c->d_proj, c->d_rects, c->d_counts, c->d_offsets,
-                        c->d_scan_temp, c->d_total, c->d_keys[0], c->d_keys[1], c->d_vals[0], c->d_vals[1],
-                        c->d_sort_temp, c->d_wave_masks, c->d_det_data, c->d_det_stamp, c->d_det_touched, c->d_tile_off, c->d_tile_first, c->d_row_counts, c->d_row_offsets, c->d_row_off,
-                        c->d_chunk_base, c->d_tl_hist, c->d_image0, c->d_ref, c->d_tile_sqerr, c->d_held, c->d_held_ids, c->d_held_count, c->d_held_work, c->d_sqerr_trace,
-                        c->d_status, c->d_counters, c->d_state, c->d_chunk_alive, c->d_csplats, c->d_cadams};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-        if (c->ev_flag) (void)hipEventDestroy(c->ev_flag);
-        if (c->ev_total) (void)hipEventDestroy(c->ev_total);
-        if (c->h_total) (void)hipHostFree(c->h_total);
-        if (c->h_status) (void)hipHostFree(c->h_status);
-        if (c->h_trace) (void)hipHostFree(c->h_trace);
-        if (c->h_rebin_stamp) (void)hipHostFree(c->h_rebin_stamp);
-        if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-    }
+    // the buffers, pinned mirrors and events go with their members: on the context's device, behind everything queued on
+    // the stream, and before a stream of the context's own (also when the device cannot be selected: freeing needs none)
+    if (hipSetDevice(c->device) == hipSuccess && c->stream) (void)hipStreamSynchronize(c->stream);
+    const hipStream_t own = c->own_stream ? c->stream : nullptr;
     delete c;
+    if (own) (void)hipStreamDestroy(own);
 }
 
 const char* s2d_last_error(const s2d_ctx* c) { return c ? c->err : "null context"; }
@@ -816,19 +846,18 @@ int s2d_set_target(s2d_ctx* c, const float* rgba32f)
     const size_t px = slab_pixels(c), bytes = px * sizeof(float4);
     const float* src = rgba32f + (size_t)c->g.row_begin * c->g.W * 4;
     if (c->half_images) { // floats cross the boundary; the device keeps them as fp16 (round to nearest even)
-        float4* tmp = nullptr;
-        S2D_HIP(c, hipMalloc((void**)&tmp, bytes));
-        hipError_t e = hipMemcpyAsync(tmp, src, bytes, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = launch_convert_f32_to_f16(tmp, c->d_ref, px, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(tmp);
-        S2D_HIP(c, e);
+        DevBuf<float4> tmp;
+        S2D_HIP(c, tmp.alloc(px));
+        const IdleAtExit idle{c->stream}; // (before tmp goes)
+        S2D_HIP(c, hipMemcpyAsync(tmp, src, bytes, hipMemcpyHostToDevice, c->stream));
+        S2D_HIP(c, launch_convert_f32_to_f16(tmp, c->d_ref, px, c->stream));
+        S2D_HIP(c, hipStreamSynchronize(c->stream));
     } else {
         S2D_HIP(c, hipMemcpyAsync(c->d_ref, src, bytes, hipMemcpyHostToDevice, c->stream));
         S2D_HIP(c, hipStreamSynchronize(c->stream));
     }
     c->have_target = true;
-    c->have_forward = c->have_backward = false;
+    invalidate(c, Stale::Frames);
     return S2D_OK;
 }
 
@@ -838,7 +867,7 @@ int s2d_set_target_synthetic(s2d_ctx* c)
     if (int rc = use_device(c)) return rc;
     S2D_HIP(c, launch_synthetic_target(c->d_ref, c->half_images, c->g.W, c->g.H, c->g.row_begin, c->g.row_end, c->stream));
     c->have_target = true;
-    c->have_forward = c->have_backward = false;
+    invalidate(c, Stale::Frames);
     return S2D_OK;
 }
 
@@ -848,16 +877,11 @@ int s2d_init_splats(s2d_ctx* c)
     if (int rc = use_device(c)) return rc;
     if (int rc = flush_sqerr(c)) return rc;
     S2D_HIP(c, launch_init_splats(c->d_splats, c->d_adams, c->n, c->g.W, c->g.H, c->stream));
-    if (int rc = compact_load(c)) return rc; // (every record is new: nothing of the old compact copy is worth flushing)
-    if (int rc = clear_dormant(c)) return rc;
+    if (int rc = splats_replaced(c)) return rc; // (every record is new: nothing of the old compact copy is worth flushing)
     if (c->n > 0) S2D_HIP(c, hipMemsetAsync(c->d_grads, 0, (size_t)c->n * 9 * sizeof(float), c->stream));
-    if (int rc = reset_status(c)) return rc;
     c->beta1t = c->good_beta1t = 1.0f; // main.cpp:283-284
     c->beta2t = c->good_beta2t = 1.0f;
     c->iterations = c->good_iterations = 0; // main.cpp:281
-    c->lists_valid = false;
-    c->proj_fresh = false;
-    c->have_forward = c->have_backward = false;
     return S2D_OK;
 }
 
@@ -867,13 +891,8 @@ int s2d_set_splats(s2d_ctx* c, const s2d_splat* splats)
     if (int rc = use_device(c)) return rc;
     if (int rc = compact_flush(c)) return rc; // the moments of the held splats must not be lost with the compact copy
     S2D_HIP(c, hipMemcpyAsync(c->d_splats, splats, (size_t)c->n * sizeof(s2d_splat), hipMemcpyHostToDevice, c->stream));
-    if (int rc = compact_load(c)) return rc;
-    if (int rc = clear_dormant(c)) return rc;
-    if (int rc = reset_status(c)) return rc;
+    if (int rc = splats_replaced(c)) return rc;
     S2D_HIP(c, hipStreamSynchronize(c->stream));
-    c->lists_valid = false;
-    c->proj_fresh = false;
-    c->have_forward = c->have_backward = false;
     return S2D_OK;
 }
 
@@ -894,8 +913,7 @@ int s2d_set_adam(s2d_ctx* c, const s2d_splat_adam* adams, float beta1t, float be
     if (int rc = flush_sqerr(c)) return rc; // (its ring slot is named by the iteration count about to change)
     if (int rc = compact_flush(c)) return rc; // the parameters of the held splats must not be lost with the compact copy
     S2D_HIP(c, hipMemcpyAsync(c->d_adams, adams, (size_t)c->n * sizeof(s2d_splat_adam), hipMemcpyHostToDevice, c->stream));
-    if (int rc = compact_load(c)) return rc;
-    if (int rc = clear_dormant(c)) return rc;
+    if (int rc = state_written(c, true)) return rc;
     S2D_HIP(c, hipStreamSynchronize(c->stream));
     c->beta1t = c->good_beta1t = beta1t;
     c->beta2t = c->good_beta2t = beta2t;
@@ -931,13 +949,12 @@ int s2d_get_image_rows(s2d_ctx* c, float* rgba32f_rows)
     if (int rc = use_device(c)) return rc;
     const size_t px = slab_pixels(c), bytes = px * sizeof(float4);
     if (c->half_images) {
-        float4* tmp = nullptr;
-        S2D_HIP(c, hipMalloc((void**)&tmp, bytes));
-        hipError_t e = launch_convert_f16_to_f32(c->d_image0, tmp, px, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(rgba32f_rows, tmp, bytes, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(tmp);
-        S2D_HIP(c, e);
+        DevBuf<float4> tmp;
+        S2D_HIP(c, tmp.alloc(px));
+        const IdleAtExit idle{c->stream}; // (before tmp goes)
+        S2D_HIP(c, launch_convert_f16_to_f32(c->d_image0, tmp, px, c->stream));
+        S2D_HIP(c, hipMemcpyAsync(rgba32f_rows, tmp, bytes, hipMemcpyDeviceToHost, c->stream));
+        S2D_HIP(c, hipStreamSynchronize(c->stream));
         return S2D_OK;
     }
     S2D_HIP(c, hipMemcpyAsync(rgba32f_rows, c->d_image0, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -1007,13 +1024,8 @@ int s2d_step(s2d_ctx* c, int32_t iters, uint32_t flags, double* mse_out)
         if (mse_out && last_chunk && chunk <= kHostTrace) {
             // the usual call (a frame, or a batch of frames, of the host loop): trace and status word in one round trip
             if (int rc = flush_sqerr(c)) return rc;
-            for (int got = 0; got < chunk;) {
-                const int slot = (first_iter + got) % c->trace_cap, run = std::min(chunk - got, c->trace_cap - slot);
-                S2D_HIP(c, hipMemcpyAsync(c->h_trace + got, c->d_sqerr_trace + slot, (size_t)run * sizeof(double),
-                                          hipMemcpyDeviceToHost, c->stream));
-                got += run;
-            }
-            S2D_HIP(c, hipMemcpyAsync(c->h_status, c->d_status, sizeof(DeviceStatus), hipMemcpyDeviceToHost, c->stream));
+            if (int rc = queue_trace_read(c, first_iter, chunk, c->h_trace)) return rc;
+            if (int rc = queue_status_read(c)) return rc;
             S2D_HIP(c, hipStreamSynchronize(c->stream));
             for (int k = 0; k < chunk; k++) mse_out[done + k] = c->h_trace[k] / norm; // main.cpp:805
             status_read = true;
@@ -1075,38 +1087,27 @@ int s2d_halo_commit(s2d_ctx* c, const uint32_t* masks_device, int32_t rank, int3
 {
     if (!c || rank < 0 || rank > 31) return S2D_E_INVALID;
     if (int rc = use_device(c)) return rc;
-    if (int rc = compact_flush(c)) return rc; // the held set is about to change: the id-indexed arrays take over
-    c->compact_live = false;
+    if (int rc = compact_off(c)) return rc;
     if (!masks_device) { // back to holding every splat (the caller has made this context's copy complete again)
         if (c->d_held) {
             S2D_HIP(c, hipStreamSynchronize(c->stream));
-            void* ptrs[] = {c->d_held, c->d_held_ids, c->d_held_work, c->d_held_count};
-            for (void* q : ptrs) (void)hipFree(q);
-            c->d_held = nullptr;
-            c->d_held_ids = c->d_held_work = c->d_held_count = nullptr;
-            c->lists_valid = false;
-            c->proj_fresh = false;
-            c->have_forward = c->have_backward = false;
+            c->d_held.release(), c->d_held_ids.release(), c->d_held_work.release(), c->d_held_count.release();
+            invalidate(c, Stale::Lists);
         }
         return S2D_OK;
     }
-    const bool first = c->d_held == nullptr;
+    const bool first = !c->d_held;
     if (first) {
-        S2D_HIP(c, dev_alloc(&c->d_held, (size_t)c->n));
-        S2D_HIP(c, dev_alloc(&c->d_held_ids, (size_t)c->n));
-        S2D_HIP(c, dev_alloc(&c->d_held_work, (size_t)c->n));
-        S2D_HIP(c, dev_alloc(&c->d_held_count, 4));
+        S2D_HIP(c, c->d_held.alloc((size_t)c->n));
+        S2D_HIP(c, c->d_held_ids.alloc((size_t)c->n));
+        S2D_HIP(c, c->d_held_work.alloc((size_t)c->n));
+        S2D_HIP(c, c->d_held_count.alloc(4));
     }
     S2D_HIP(c, launch_halo_commit(masks_device, c->n, rank, c->d_held, c->d_held_ids, c->d_held_count, c->d_held_work,
                                   c->d_scan_temp, c->stream));
     if (int rc = compact_load(c)) return rc;
-    if (added || first) {
-        // splats arrived: project the held ones and rebuild the tile lists before the next forward
-        c->lists_valid = false;
-        c->proj_fresh = false;
-        c->have_forward = false;
-        c->have_backward = false;
-    }
+    // splats arrived: project the held ones and rebuild the tile lists before the next forward
+    if (added || first) invalidate(c, Stale::Lists);
     return S2D_OK;
 }
 
@@ -1143,16 +1144,9 @@ int s2d_rows_scatter(s2d_ctx* c, int32_t what, const int32_t* ids_device, int32_
     if (what != S2D_ROWS_GRADS)
         if (int rc = compact_flush(c)) return rc;
     S2D_HIP(c, launch_rows_scatter(base, w, ids_device, count, c->n, in_device, c->stream));
-    if (what == S2D_ROWS_SPLATS || what == S2D_ROWS_ADAM) {
-        if (c->compact_live)
-            if (int rc = compact_load(c)) return rc; // rows of held splats may be among them
-        if (int rc = clear_dormant(c)) return rc;
-    }
-    if (what == S2D_ROWS_SPLATS) { // parameters changed behind the projection
-        c->proj_fresh = false;
-        c->have_forward = false;
-        c->have_backward = false;
-    }
+    if (what != S2D_ROWS_GRADS)
+        if (int rc = state_written(c, false)) return rc;
+    if (what == S2D_ROWS_SPLATS) invalidate(c, Stale::Projection); // parameters changed behind the projection
     return S2D_OK;
 }
 
@@ -1170,14 +1164,7 @@ int s2d_get_sqerr_trace(s2d_ctx* c, int32_t first_iteration, int32_t count, doub
     if (!c || !out || count < 0 || first_iteration < 0 || count > c->trace_cap) return S2D_E_INVALID;
     if (int rc = use_device(c)) return rc;
     if (int rc = flush_sqerr(c)) return rc;
-    int done = 0;
-    while (done < count) {
-        const int slot = (first_iteration + done) % c->trace_cap;
-        const int run = std::min(count - done, c->trace_cap - slot);
-        S2D_HIP(c, hipMemcpyAsync(out + done, c->d_sqerr_trace + slot, (size_t)run * sizeof(double),
-                                  hipMemcpyDeviceToHost, c->stream));
-        done += run;
-    }
+    if (int rc = queue_trace_read(c, first_iteration, count, out)) return rc;
     S2D_HIP(c, hipStreamSynchronize(c->stream));
     return S2D_OK;
 }
@@ -1196,7 +1183,7 @@ int s2d_get_stats(s2d_ctx* c, s2d_stats* out)
     if (int rc = use_device(c)) return rc;
     PairCounters pc;
     S2D_HIP(c, hipMemcpyAsync(&pc, c->d_counters, sizeof(pc), hipMemcpyDeviceToHost, c->stream));
-    S2D_HIP(c, hipMemcpyAsync(c->h_status, c->d_status, sizeof(DeviceStatus), hipMemcpyDeviceToHost, c->stream));
+    if (int rc = queue_status_read(c)) return rc;
     S2D_HIP(c, hipStreamSynchronize(c->stream));
     // filled in a full-size copy, handed back at the caller's size: a caller built against an older, shorter struct is
     // never written past its end
@@ -1252,80 +1239,59 @@ int s2d_debug_get_tile_lists(s2d_ctx* c, int32_t* tiles_x, int32_t* tiles_y, uin
 }
 
 // ---- test hooks -----------------------------------------------------------------------------------
-#define S2D_HIP0(expr)                         \
-    do {                                       \
-        if ((expr) != hipSuccess) { rc = S2D_E_HIP; goto done; } \
-    } while (0)
-
+// (no context: S2D_HIP(nullptr, ...) reports S2D_E_HIP without a message; the owners free on every way out)
 int s2d_test_sincos(int32_t device, const float* x, int32_t n, float* sin_out, float* cos_out)
 {
     if (!x || !sin_out || !cos_out || n < 0) return S2D_E_INVALID;
-    int rc = S2D_OK;
-    float *dx = nullptr, *ds = nullptr, *dc = nullptr;
-    const size_t bytes = std::max<size_t>(n, 1) * sizeof(float);
-    S2D_HIP0(hipSetDevice(device));
-    S2D_HIP0(hipMalloc((void**)&dx, bytes));
-    S2D_HIP0(hipMalloc((void**)&ds, bytes));
-    S2D_HIP0(hipMalloc((void**)&dc, bytes));
-    S2D_HIP0(hipMemcpy(dx, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-    S2D_HIP0(launch_test_sincos(dx, n, ds, dc, nullptr));
-    S2D_HIP0(hipDeviceSynchronize());
-    S2D_HIP0(hipMemcpy(sin_out, ds, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    S2D_HIP0(hipMemcpy(cos_out, dc, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-done:
-    if (dx) (void)hipFree(dx);
-    if (ds) (void)hipFree(ds);
-    if (dc) (void)hipFree(dc);
-    return rc;
+    DevBuf<float> dx, ds, dc;
+    S2D_HIP(nullptr, hipSetDevice(device));
+    S2D_HIP(nullptr, dx.alloc((size_t)n));
+    S2D_HIP(nullptr, ds.alloc((size_t)n));
+    S2D_HIP(nullptr, dc.alloc((size_t)n));
+    S2D_HIP(nullptr, hipMemcpy(dx, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    S2D_HIP(nullptr, launch_test_sincos(dx, n, ds, dc, nullptr));
+    S2D_HIP(nullptr, hipDeviceSynchronize());
+    S2D_HIP(nullptr, hipMemcpy(sin_out, ds, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    S2D_HIP(nullptr, hipMemcpy(cos_out, dc, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return S2D_OK;
 }
 
 int s2d_test_sort_pairs(int32_t device, uint32_t* keys, uint32_t* values, int64_t n, int32_t key_bits)
 {
     if (!keys || !values || n < 0 || key_bits < 0 || key_bits > 32) return S2D_E_INVALID;
-    int rc = S2D_OK;
-    uint32_t *k[2] = {nullptr, nullptr}, *v[2] = {nullptr, nullptr}, *temp = nullptr, *ko = nullptr, *vo = nullptr;
-    const size_t bytes = std::max<size_t>((size_t)n, 1) * sizeof(uint32_t);
-    S2D_HIP0(hipSetDevice(device));
+    DevBuf<uint32_t> k[2], v[2], temp;
+    uint32_t *ko = nullptr, *vo = nullptr;
+    S2D_HIP(nullptr, hipSetDevice(device));
     for (int i = 0; i < 2; i++) {
-        S2D_HIP0(hipMalloc((void**)&k[i], bytes));
-        S2D_HIP0(hipMalloc((void**)&v[i], bytes));
+        S2D_HIP(nullptr, k[i].alloc((size_t)n));
+        S2D_HIP(nullptr, v[i].alloc((size_t)n));
     }
-    S2D_HIP0(hipMalloc((void**)&temp, sort_temp_words(n) * sizeof(uint32_t)));
-    S2D_HIP0(hipMemcpy(k[0], keys, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    S2D_HIP0(hipMemcpy(v[0], values, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    S2D_HIP0(sort_pairs_u32(k[0], v[0], k[1], v[1], n, key_bits, temp, &ko, &vo, nullptr, nullptr));
-    S2D_HIP0(hipDeviceSynchronize());
-    S2D_HIP0(hipMemcpy(keys, ko, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    S2D_HIP0(hipMemcpy(values, vo, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-done:
-    for (int i = 0; i < 2; i++) {
-        if (k[i]) (void)hipFree(k[i]);
-        if (v[i]) (void)hipFree(v[i]);
-    }
-    if (temp) (void)hipFree(temp);
-    return rc;
+    S2D_HIP(nullptr, temp.alloc(sort_temp_words(n)));
+    S2D_HIP(nullptr, hipMemcpy(k[0], keys, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    S2D_HIP(nullptr, hipMemcpy(v[0], values, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    S2D_HIP(nullptr, sort_pairs_u32(k[0], v[0], k[1], v[1], n, key_bits, temp, &ko, &vo, nullptr, nullptr));
+    S2D_HIP(nullptr, hipDeviceSynchronize());
+    S2D_HIP(nullptr, hipMemcpy(keys, ko, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    S2D_HIP(nullptr, hipMemcpy(values, vo, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return S2D_OK;
 }
 
 int s2d_test_exclusive_scan(int32_t device, uint32_t* data, int64_t n, uint64_t* total)
 {
     if (!data || n < 0) return S2D_E_INVALID;
-    int rc = S2D_OK;
-    uint32_t *d = nullptr, *temp = nullptr, *tot = nullptr, htot = 0;
-    S2D_HIP0(hipSetDevice(device));
-    S2D_HIP0(hipMalloc((void**)&d, std::max<size_t>((size_t)n, 1) * sizeof(uint32_t)));
-    S2D_HIP0(hipMalloc((void**)&temp, scan_temp_words(n) * sizeof(uint32_t)));
-    S2D_HIP0(hipMalloc((void**)&tot, sizeof(uint32_t)));
-    S2D_HIP0(hipMemcpy(d, data, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    S2D_HIP0(exclusive_scan_u32(d, d, n, temp, tot, nullptr));
-    S2D_HIP0(hipDeviceSynchronize());
-    S2D_HIP0(hipMemcpy(data, d, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    S2D_HIP0(hipMemcpy(&htot, tot, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    DevBuf<uint32_t> d, temp, tot;
+    uint32_t htot = 0;
+    S2D_HIP(nullptr, hipSetDevice(device));
+    S2D_HIP(nullptr, d.alloc((size_t)n));
+    S2D_HIP(nullptr, temp.alloc(scan_temp_words(n)));
+    S2D_HIP(nullptr, tot.alloc(1));
+    S2D_HIP(nullptr, hipMemcpy(d, data, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    S2D_HIP(nullptr, exclusive_scan_u32(d, d, n, temp, tot, nullptr));
+    S2D_HIP(nullptr, hipDeviceSynchronize());
+    S2D_HIP(nullptr, hipMemcpy(data, d, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    S2D_HIP(nullptr, hipMemcpy(&htot, tot, sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (total) *total = htot;
-done:
-    if (d) (void)hipFree(d);
-    if (temp) (void)hipFree(temp);
-    if (tot) (void)hipFree(tot);
-    return rc;
+    return S2D_OK;
 }
 
 } // extern "C"

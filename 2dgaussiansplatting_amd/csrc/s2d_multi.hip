@@ -42,7 +42,12 @@
 #include <thread>
 #include <vector>
 
+#include "s2d_owned.h"
+
 namespace {
+
+using s2d::DevBuf; // here: arrays that only grow (reserve), re-allocated while the rank's stream is idle
+using s2d::Event;
 
 struct Rccl {
     void* lib = nullptr;
@@ -162,30 +167,6 @@ struct Progress {                 // one per rank, written by its thread only
     std::atomic<int> iteration{0};
 };
 
-// Device array that only grows (freed and re-allocated while the rank's stream is idle).
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t count)
-    {
-        if (count <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = std::max<size_t>(count + count / 4, 256);
-        const hipError_t e = hipMalloc((void**)&p, want * sizeof(T));
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
 // Slab ownership, one rank's side (the host logic of distributed.HaloStep, here inside the library).
 struct HaloRank {
     std::vector<uint32_t> mask;           // per splat: bit q = rank q holds it; 0 = this rank does not (its copy is stale)
@@ -196,7 +177,7 @@ struct HaloRank {
     DevBuf<int32_t> d_send_ids, d_rows, d_src;
     DevBuf<float> d_send[2], d_recv;      // two send buffers: a peer may still be copying iteration k while k + 1 is gathered
     DevBuf<uint32_t> d_mask;              // n words: s2d_halo_masks output / s2d_halo_commit input
-    hipEvent_t ev_sent[2] = {nullptr, nullptr};
+    Event ev_sent[2];
     unsigned seq = 0;                     // exchanges since the hold sets were made (its parity picks the send buffer)
     // a refresh: state rows on their way to ranks that newly hold a splat
     std::vector<uint32_t> fresh;                 // masks from the current parameters (0 where not held)
@@ -206,16 +187,6 @@ struct HaloRank {
     DevBuf<int32_t> d_pay_ids, d_in_ids;
     DevBuf<float> d_pay_sp, d_pay_ad, d_in_sp, d_in_ad;
     long long handed = 0;                 // state rows sent or received so far (diagnostic)
-    void release()
-    {
-        d_send_ids.release(), d_rows.release(), d_src.release(), d_send[0].release(), d_send[1].release(), d_recv.release();
-        d_mask.release(), d_pay_ids.release(), d_in_ids.release(), d_pay_sp.release(), d_pay_ad.release(), d_in_sp.release();
-        d_in_ad.release();
-        for (hipEvent_t& e : ev_sent) {
-            if (e) (void)hipEventDestroy(e);
-            e = nullptr;
-        }
-    }
 };
 
 } // namespace
@@ -531,10 +502,10 @@ int plan(s2d_multi* m, int r)
     MHIP(m, r, H.d_recv.reserve((size_t)total * 9));
     MHIP(m, r, H.d_rows.reserve(rows.size()));
     MHIP(m, r, H.d_src.reserve(src.size()));
-    if (total) MHIP(m, r, hipMemcpyAsync(H.d_send_ids.p, send_ids.data(), (size_t)total * 4, hipMemcpyHostToDevice, stream));
+    if (total) MHIP(m, r, hipMemcpyAsync(H.d_send_ids, send_ids.data(), (size_t)total * 4, hipMemcpyHostToDevice, stream));
     if (!rows.empty()) {
-        MHIP(m, r, hipMemcpyAsync(H.d_rows.p, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, stream));
-        MHIP(m, r, hipMemcpyAsync(H.d_src.p, src.data(), src.size() * 4, hipMemcpyHostToDevice, stream));
+        MHIP(m, r, hipMemcpyAsync(H.d_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, stream));
+        MHIP(m, r, hipMemcpyAsync(H.d_src, src.data(), src.size() * 4, hipMemcpyHostToDevice, stream));
     }
     return drain_now(m, r, "uploading its exchange plan"); // the host vectors go away
 }
@@ -563,8 +534,8 @@ int hold_fresh(s2d_multi* m, int r)
     hipStream_t stream = (hipStream_t)s2d_stream(c);
     const size_t n = (size_t)m->n;
     MHIP(m, r, hipSetDevice(m->devices[(size_t)r]));
-    for (hipEvent_t& e : H.ev_sent)
-        if (!e) MHIP(m, r, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (Event& e : H.ev_sent)
+        if (!e) MHIP(m, r, e.create(hipEventDisableTiming));
     if (int rc = s2d_halo_commit(c, nullptr, r, 0)) return rc; // hold everything: the masks below cover every splat
     MHIP(m, r, H.d_mask.reserve(n));
     H.fresh.resize(n);
@@ -573,16 +544,16 @@ int hold_fresh(s2d_multi* m, int r)
     H.out_ids.assign((size_t)m->world, {});
     H.out_mask.assign((size_t)m->world, {});
     H.out_off.assign((size_t)m->world, 0);
-    if (int rc = s2d_halo_masks(c, m->world, m->bounds.data(), m->margin, H.d_mask.p)) return rc;
-    MHIP(m, r, hipMemcpyAsync(H.fresh.data(), H.d_mask.p, n * 4, hipMemcpyDeviceToHost, stream));
+    if (int rc = s2d_halo_masks(c, m->world, m->bounds.data(), m->margin, H.d_mask)) return rc;
+    MHIP(m, r, hipMemcpyAsync(H.fresh.data(), H.d_mask, n * 4, hipMemcpyDeviceToHost, stream));
     if (int rc = drain_now(m, r, "reading the hold-set words")) return rc;
     for (size_t i = 0; i < n; i++)
         if ((H.fresh[i] >> r) & 1u) {
             H.mask[i] = H.fresh[i];
             H.held.push_back((int32_t)i);
         }
-    MHIP(m, r, hipMemcpyAsync(H.d_mask.p, H.mask.data(), n * 4, hipMemcpyHostToDevice, stream));
-    if (int rc = s2d_halo_commit(c, H.d_mask.p, r, 1)) return rc;
+    MHIP(m, r, hipMemcpyAsync(H.d_mask, H.mask.data(), n * 4, hipMemcpyHostToDevice, stream));
+    if (int rc = s2d_halo_commit(c, H.d_mask, r, 1)) return rc;
     if (int rc = plan(m, r)) return rc;
     if (int rc = meet_rank(m, r, "hold sets")) return rc;
     return settle_plans(m, r);
@@ -601,8 +572,8 @@ int refresh(s2d_multi* m, int r)
     const uint32_t me = 1u << r;
     if (int rc = drain_now(m, r, "finishing the iterations before a hold-set refresh")) return rc; // up to `interval` iterations of device work
     if (int rc = s2d_synchronize(c)) return rc; // the finite guard; and every copy this rank queued has landed
-    if (int rc = s2d_halo_masks(c, world, m->bounds.data(), m->margin, H.d_mask.p)) return rc;
-    MHIP(m, r, hipMemcpyAsync(H.fresh.data(), H.d_mask.p, n * 4, hipMemcpyDeviceToHost, stream));
+    if (int rc = s2d_halo_masks(c, world, m->bounds.data(), m->margin, H.d_mask)) return rc;
+    MHIP(m, r, hipMemcpyAsync(H.fresh.data(), H.d_mask, n * 4, hipMemcpyDeviceToHost, stream));
     if (int rc = drain_now(m, r, "reading the hold-set words")) return rc;
     for (int q = 0; q < world; q++) {
         H.out_ids[(size_t)q].clear();
@@ -639,9 +610,9 @@ int refresh(s2d_multi* m, int r)
         MHIP(m, r, H.d_pay_ids.reserve((size_t)k_out));
         MHIP(m, r, H.d_pay_sp.reserve((size_t)k_out * 9));
         MHIP(m, r, H.d_pay_ad.reserve((size_t)k_out * 18));
-        MHIP(m, r, hipMemcpyAsync(H.d_pay_ids.p, pay_ids.data(), (size_t)k_out * 4, hipMemcpyHostToDevice, stream));
-        if (int rc = s2d_rows_gather(c, S2D_ROWS_SPLATS, H.d_pay_ids.p, k_out, H.d_pay_sp.p)) return rc;
-        if (int rc = s2d_rows_gather(c, S2D_ROWS_ADAM, H.d_pay_ids.p, k_out, H.d_pay_ad.p)) return rc;
+        MHIP(m, r, hipMemcpyAsync(H.d_pay_ids, pay_ids.data(), (size_t)k_out * 4, hipMemcpyHostToDevice, stream));
+        if (int rc = s2d_rows_gather(c, S2D_ROWS_SPLATS, H.d_pay_ids, k_out, H.d_pay_sp)) return rc;
+        if (int rc = s2d_rows_gather(c, S2D_ROWS_ADAM, H.d_pay_ids, k_out, H.d_pay_ad)) return rc;
         if (int rc = drain_now(m, r, "gathering the state rows it hands over")) return rc;
     }
     if (int rc = meet_rank(m, r, "hold-set refresh (state rows out)")) return rc; // every rank's outgoing rows are in place, every stream is idle
@@ -660,19 +631,19 @@ int refresh(s2d_multi* m, int r)
         MHIP(m, r, H.d_in_ids.reserve((size_t)k_in));
         MHIP(m, r, H.d_in_sp.reserve((size_t)k_in * 9));
         MHIP(m, r, H.d_in_ad.reserve((size_t)k_in * 18));
-        MHIP(m, r, hipMemcpyAsync(H.d_in_ids.p, in_ids.data(), (size_t)k_in * 4, hipMemcpyHostToDevice, stream));
+        MHIP(m, r, hipMemcpyAsync(H.d_in_ids, in_ids.data(), (size_t)k_in * 4, hipMemcpyHostToDevice, stream));
         size_t off = 0;
         for (int p = 0; p < world; p++)
             if (p != r) {
                 const HaloRank& P = m->halo[(size_t)p];
                 const size_t cnt = P.out_ids[(size_t)r].size(), from = (size_t)P.out_off[(size_t)r];
                 if (!cnt) continue;
-                MHIP(m, r, rank_copy(m, H.d_in_sp.p + off * 9, r, P.d_pay_sp.p + from * 9, p, cnt * 9 * sizeof(float), stream));
-                MHIP(m, r, rank_copy(m, H.d_in_ad.p + off * 18, r, P.d_pay_ad.p + from * 18, p, cnt * 18 * sizeof(float), stream));
+                MHIP(m, r, rank_copy(m, H.d_in_sp + off * 9, r, P.d_pay_sp + from * 9, p, cnt * 9 * sizeof(float), stream));
+                MHIP(m, r, rank_copy(m, H.d_in_ad + off * 18, r, P.d_pay_ad + from * 18, p, cnt * 18 * sizeof(float), stream));
                 off += cnt;
             }
         std::vector<float> sp((size_t)k_in * 9);
-        MHIP(m, r, hipMemcpyAsync(sp.data(), H.d_in_sp.p, sp.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
+        MHIP(m, r, hipMemcpyAsync(sp.data(), H.d_in_sp, sp.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
         if (int rc = drain_now(m, r, "fetching the state rows handed to it")) return rc;
         // a splat that arrives already touching this rank's rows was rasterised here without being listed: the margin
         // did not outlast the interval
@@ -690,16 +661,16 @@ int refresh(s2d_multi* m, int r)
                                             "over (%d on rank %d): the margin of %.1f rows did not outlast %d iterations",
                          m->late.load(), late, r, (double)m->margin, m->interval);
     if (k_in) {
-        if (int rc = s2d_rows_scatter(c, S2D_ROWS_SPLATS, H.d_in_ids.p, k_in, H.d_in_sp.p)) return rc;
-        if (int rc = s2d_rows_scatter(c, S2D_ROWS_ADAM, H.d_in_ids.p, k_in, H.d_in_ad.p)) return rc;
+        if (int rc = s2d_rows_scatter(c, S2D_ROWS_SPLATS, H.d_in_ids, k_in, H.d_in_sp)) return rc;
+        if (int rc = s2d_rows_scatter(c, S2D_ROWS_ADAM, H.d_in_ids, k_in, H.d_in_ad)) return rc;
         for (int j = 0; j < k_in; j++) H.mask[(size_t)in_ids[(size_t)j]] = in_mask[(size_t)j];
         keep.insert(keep.end(), in_ids.begin(), in_ids.end());
         std::sort(keep.begin(), keep.end());
     }
     H.held.swap(keep);
     H.handed += k_out + k_in;
-    MHIP(m, r, hipMemcpyAsync(H.d_mask.p, H.mask.data(), n * 4, hipMemcpyHostToDevice, stream));
-    if (int rc = s2d_halo_commit(c, H.d_mask.p, r, k_in > 0)) return rc; // departures alone leave the tile lists valid
+    MHIP(m, r, hipMemcpyAsync(H.d_mask, H.mask.data(), n * 4, hipMemcpyHostToDevice, stream));
+    if (int rc = s2d_halo_commit(c, H.d_mask, r, k_in > 0)) return rc; // departures alone leave the tile lists valid
     if (int rc = plan(m, r)) return rc;
     if (int rc = meet_rank(m, r, "hold-set refresh (plans)")) return rc; // plans are in; the outgoing buffers may be re-used
     return settle_plans(m, r);
@@ -755,7 +726,7 @@ int exchange_grads(s2d_multi* m, int r)
     const unsigned seq = ++H.seq;
     const int b = (int)((seq - 1u) & 1u);
     if (H.total) {
-        if (int rc = s2d_rows_gather(c, S2D_ROWS_GRADS, H.d_send_ids.p, H.total, H.d_send[b].p)) return rc;
+        if (int rc = s2d_rows_gather(c, S2D_ROWS_GRADS, H.d_send_ids, H.total, H.d_send[b])) return rc;
         MHIP(m, r, hipEventRecord(H.ev_sent[b], stream));
     }
     m->sent_seq[(size_t)r].store(seq, std::memory_order_release);
@@ -765,11 +736,11 @@ int exchange_grads(s2d_multi* m, int r)
         if (int rc = wait_issued(m, r, p, seq)) return rc;
         const HaloRank& P = m->halo[(size_t)p];
         MHIP(m, r, hipStreamWaitEvent(stream, P.ev_sent[b], 0));
-        MHIP(m, r, rank_copy(m, H.d_recv.p + (size_t)H.offsets[(size_t)p] * 9, r, P.d_send[b].p + (size_t)P.offsets[(size_t)r] * 9, p,
+        MHIP(m, r, rank_copy(m, H.d_recv + (size_t)H.offsets[(size_t)p] * 9, r, P.d_send[b] + (size_t)P.offsets[(size_t)r] * 9, p,
                              (size_t)cnt * 9 * sizeof(float), stream));
     }
     if (H.n_rows)
-        if (int rc = s2d_grads_combine(c, H.d_rows.p, H.n_rows, H.d_src.p, m->world, H.d_recv.p)) return rc;
+        if (int rc = s2d_grads_combine(c, H.d_rows, H.n_rows, H.d_src, m->world, H.d_recv)) return rc;
     return S2D_OK;
 }
 
@@ -868,7 +839,7 @@ void worker_main(s2d_multi* m, int rank)
         }
         if (cmd == CMD_QUIT) {
             (void)hipSetDevice(m->devices[(size_t)rank]);
-            m->halo[(size_t)rank].release();
+            m->halo[(size_t)rank] = HaloRank(); // its device buffers and events go here, on their device, not with the handle
             return;
         }
         int rc = S2D_OK;

@@ -79,6 +79,7 @@ def test_the_harness_sees_a_seeded_race(sim, tmp_path):
     exe = str(tmp_path / "multi_sim_mutant")
     build = os.path.join(SIM, "_build")
     subprocess.check_call([_tsan_compiler(), "-O1", "-g", "-std=c++17", "-fPIC", "-pthread", "-fsanitize=thread", "-I" + os.path.join(SIM, "include"),
+                           "-I" + os.path.dirname(MULTI),  # the mutant lies outside the tree: s2d_owned.h is beside the original
                            "-o", exe, os.path.join(SIM, "multi_sim_main.cpp"), os.path.join(SIM, "sim_ctx.cpp"), "-x", "c++", str(mut), "-x", "none",
                            os.path.join(build, "s2d_oracle.o"), "-L" + build, "-lsimhip", "-Wl,--no-as-needed", "-l:librccl.so.1", "-Wl,--as-needed",
                            "-ldl", "-lm", "-Wl,--disable-new-dtags", "-Wl,-rpath," + build])
