@@ -52,7 +52,11 @@ struct s2d_ctx {
     DevBuf<uint32_t> d_keys[2];
     DevBuf<uint32_t> d_vals[2];
     DevBuf<uint32_t> d_sort_temp;
-    DevBuf<unsigned long long> d_wave_masks;    // 4 x u64 per listed pair: forward -> backward lane masks
+    DevBuf<unsigned long long> d_wave_masks;    // 4 x u64 per listed pair (capacity; written per executed pair): forward -> backward lane masks
+    DevBuf<uint32_t> d_exec_list;               // per listed pair (capacity): splat indices of a tile's executed entries, compacted
+    DevBuf<uint32_t> d_tile_exec;               // [tiles]: how many entries the tile's last forward walk handed over
+    DevBuf<uint32_t> d_retire_hint;             // [tiles]: list position at which the tile retired in the last launch (0xFFFFFFFF: unknown);
+                                                // a hint for batch sizes only, so it survives list rebuilds and new splats (measured better than a reset)
     bool deterministic = false;                 // S2D_CFG_DETERMINISTIC
     DevBuf<float> d_det_data;                   // [pair capacity][9] per-(tile, splat) partial gradients
     DevBuf<uint32_t> d_det_stamp;               // [pair capacity]
@@ -185,7 +189,7 @@ int ensure_pair_capacity(s2d_ctx* c, uint64_t need)
     if (cap > 0xFFFF0000ull) cap = 0xFFFF0000ull;
     S2D_HIP(c, hipStreamSynchronize(c->stream));
     for (int k = 0; k < 2; k++) c->d_keys[k].release(), c->d_vals[k].release(); // all six go before the first comes back
-    c->d_sort_temp.release(), c->d_wave_masks.release(), c->d_det_data.release(), c->d_det_stamp.release();
+    c->d_sort_temp.release(), c->d_wave_masks.release(), c->d_exec_list.release(), c->d_det_data.release(), c->d_det_stamp.release();
     c->pair_capacity = 0; // (what is left if an allocation below fails)
     for (int k = 0; k < 2; k++) {
         S2D_HIP(c, c->d_keys[k].alloc(cap));
@@ -193,6 +197,7 @@ int ensure_pair_capacity(s2d_ctx* c, uint64_t need)
     }
     S2D_HIP(c, c->d_sort_temp.alloc(sort_temp_words((int64_t)cap)));
     S2D_HIP(c, c->d_wave_masks.alloc((size_t)cap * 4));
+    S2D_HIP(c, c->d_exec_list.alloc((size_t)cap));
     if (c->deterministic) {
         S2D_HIP(c, c->d_det_data.alloc((size_t)cap * kDetStride));
         S2D_HIP(c, c->d_det_stamp.alloc((size_t)cap));
@@ -306,6 +311,7 @@ RasterArgs raster_args(const s2d_ctx* c, int first = 0, int count = -1)
 {
     RasterArgs a;
     a.tile_off = c->d_tile_off; a.list = c->d_list; a.wave_masks = c->d_wave_masks;
+    a.exec_list = c->d_exec_list; a.tile_exec = c->d_tile_exec; a.retire_hint = c->d_retire_hint;
     a.proj = c->d_proj + first; a.grads = c->d_grads + (size_t)first * 9;
     a.image0 = c->d_image0; a.image_ref = c->d_ref; a.tile_sqerr = c->d_tile_sqerr;
     a.g = c->g; a.status = c->d_status; a.iteration = c->iterations; a.counters = c->d_counters;
@@ -796,6 +802,9 @@ int s2d_create(const s2d_config* cfg, s2d_ctx** out)
     S2D_HIP(c, c->d_image0.alloc(px * c->pixel_bytes));
     S2D_HIP(c, c->d_ref.alloc(px * c->pixel_bytes));
     S2D_HIP(c, c->d_tile_sqerr.alloc((size_t)g.num_tiles + kSqerrScratchDoubles)); // + finalize scratch
+    S2D_HIP(c, c->d_tile_exec.alloc((size_t)g.num_tiles));
+    S2D_HIP(c, c->d_retire_hint.alloc((size_t)g.num_tiles));
+    S2D_HIP(c, hipMemset(c->d_retire_hint, 0xFF, (size_t)g.num_tiles * sizeof(uint32_t)));
     S2D_HIP(c, hipMemset(c->d_tile_sqerr + g.num_tiles, 0, kSqerrScratchDoubles * sizeof(double)));
     S2D_HIP(c, c->d_sqerr_trace.alloc((size_t)c->trace_cap));
     S2D_HIP(c, c->d_status.alloc(1));

@@ -211,7 +211,12 @@ struct RasterArgs {
     const ProjRec* proj = nullptr;  // proj / grads / the arrays of `det` start at the first splat of the lists
     void* image0 = nullptr;
     const void* image_ref = nullptr;
+    // forward -> backward walk: lane masks and splat indices of the entries the forward walk executed, compacted to the
+    // front of each tile's list range, and their number per tile (s2d_raster.hip forward_tile)
     unsigned long long* wave_masks = nullptr;
+    uint32_t* exec_list = nullptr;
+    uint32_t* tile_exec = nullptr;
+    uint32_t* retire_hint = nullptr; // per tile: where its forward walk retired in the previous launch (a hint for batch sizes)
     float* grads = nullptr;
     double* tile_sqerr = nullptr;
     Geometry g{};

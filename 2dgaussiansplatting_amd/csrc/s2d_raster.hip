@@ -7,9 +7,10 @@
 //   * forward walk: 4 threads per entry load the 64-byte projected record and evaluate the reference's exact per-row
 //     column range (solve_quadratic + int truncation, main.cpp:498-509) for 4 tile rows each, producing one
 //     64-bit lane mask per (entry, wave): bit l set <=> the reference's loops visit that pixel for that
-//     splat.  The quadratic is solved once per (entry, row), not per pixel.  The masks are also stored (32 B per
-//     staged pair); the backward walk, which goes through exactly the same batches, loads them instead of solving
-//     the quadratics again.
+//     splat.  The quadratic is solved once per (entry, row), not per pixel.  At the end of a batch the masks and
+//     splat indices of the entries whose body ran in at least one wave are stored, compacted to the front of the
+//     tile's own range (32 + 4 B per executed pair); the backward walk goes through those entries only, in batches
+//     of its own, and loads the masks instead of solving the quadratics again.
 //   * after the barrier lane l of every wave fetches the mask of entry l; a ballot of "mask touches a live pixel" is
 //     the set of entries this wave has to look at, and the blend loop iterates over its set bits only
 //     (scalar bit tricks + v_readlane), skipping an entry with a scalar branch when no lane is live any more.
@@ -37,6 +38,19 @@ namespace s2d {
 
 constexpr int B = kRasterBatch;
 static_assert(B == 64, "lane l of a wave holds the mask of batch entry l");
+
+// Forward batch sizes from where the tile retired in the previous launch (retire_hint[tile]: list position, relative to the
+// tile's first, one past the last executed entry; kNoHint: unknown, or the walk ran to the end of its list).  A tile that
+// retires has otherwise staged half a batch too many, four row solves per staging thread each.  Up to the hint batches are
+// full; the batch the hint falls into ends at it, rounded up to a staging wave's 16 entries (the other waves go straight
+// to the barrier); a tile that lives longer than last time goes on in batches of kHintFollow.  It is a hint and nothing
+// else: every pixel still sees every entry of its list in order until the tile retires, whatever the word holds -- also
+// one left by other lists or other splats, which is why nothing but the walk itself ever writes it.  Measured on top of
+// the compacted hand-over, 4096^2 / 1 M (profiles/r06/ab_exec_handover.txt): slack behind the hint 0 / 4 / 8 / 16 entries
+// +2.3 / +2.1 / +1.8 / +1.0 %, follow-up batches of 16 and 32 the same, and a hint kept across a list rebuild +0.3 % over
+// one reset there.
+constexpr uint32_t kNoHint = 0xFFFFFFFFu;
+constexpr uint32_t kHintFollow = 16;
 
 constexpr int kWaveW = 8;              // pixel columns per wave block (8x8 blocks: measured better than 16x4 strips,
 constexpr int kWaveH = 64 / kWaveW;    // profiles/r01: 34 vs 37 executed entries per wave, 36 vs 33 active lanes)
@@ -196,10 +210,14 @@ __device__ __forceinline__ size_t pixel_index(const TileCtx& c, const Geometry& 
 // LDS of the forward walk: per-entry record, three 16-B rows at one LDS address (one address register for the blend
 // loop's reads):  [0] pos.x, pos.y, a, b   [1] b, d, col_r, col_g   [2] col_b, opacity, -, -
 // (b twice: (a,b) and (b,d) are the two columns of inv_cov)
+// mask and idx (the list word) in two copies, by batch parity: the hand-over to the backward walk reads them behind the
+// last barrier of the batch, while fast threads already stage the next one.
 struct FwdShared {
     float4 rec[B][3];
-    unsigned long long mask[4 * B]; // [wave][entry]
-    int4 alive;                     // per wave: does it still have a live pixel (block_any_alive)
+    unsigned long long mask[2][4 * B]; // [parity][wave][entry]
+    uint32_t idx[2][B];
+    unsigned long long touched[4];     // per wave: bit e = the body of entry e ran (posted with the alive flag)
+    int4 alive;                        // per wave: does it still have a live pixel (block_any_alive)
 };
 
 // "Does any wave of the workgroup still have a live pixel?"  The answer of a wave is already uniform (its alive mask
@@ -214,18 +232,43 @@ __device__ __forceinline__ bool block_any_alive(int4* flags, int w, int lane, un
     return ((f.x | f.y) | (f.z | f.w)) != 0;
 }
 
+// The same exchange at the end of a forward batch, which also carries the entries each wave executed: *exec_mask = bit e
+// set <=> the body of entry e ran in at least one wave (uniform, in scalar registers).
+__device__ __forceinline__ bool block_any_alive_exec(int4* flags, unsigned long long* touched4, int w, int lane,
+                                                     unsigned long long alive_mask, unsigned long long touched,
+                                                     unsigned long long* exec_mask)
+{
+    if (lane == 0) {
+        reinterpret_cast<int*>(flags)[w] = alive_mask != 0ull ? 1 : 0;
+        touched4[w] = touched;
+    }
+    __syncthreads();
+    const int4 f = *flags;
+    const unsigned long long m = (touched4[0] | touched4[1]) | (touched4[2] | touched4[3]);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)m), hi = __builtin_amdgcn_readfirstlane((uint32_t)(m >> 32));
+    *exec_mask = ((unsigned long long)hi << 32) | lo;
+    return ((f.x | f.y) | (f.z | f.w)) != 0;
+}
+
 // One tile's forward walk (main.cpp:419-536 for its pixels): leaves the final colour of this thread's pixel in
-// (crg, cb) and the lane masks of every staged pair in wave_masks.
+// (crg, cb) and hands the entries the backward walk has to run over to it.  The backward walk makes exactly this walk's
+// per-pixel decisions, so the (wave, entry) bodies it will run are the ones that ran here: entry k (k = 0 ..) of them
+// leaves its splat index in exec_list[beg + k] and its four lane masks in wave_masks[(beg + k) * 4 ..], beg = the
+// tile's first list position; their number is returned.  Compacted positions never run ahead of list positions and
+// [beg, end) belongs to this tile alone.  A counting walk (COUNT, whose statistics are defined on staged entries) hands
+// over every staged entry at its list position instead, and the backward walk reads the list.
 // CHUNK (scenes whose (tile, splat) pairs do not fit one set of lists, s2d_api.hip chunked_raster): the list holds the
 // splats of one INDEX RANGE only; the walk continues from the pixel's state after the ranges before it -- (crg, cb) and
 // *T_io on entry -- and leaves the state for the range after it.  The reference's loop is front to back in index order
 // (main.cpp:419), so cutting it at any index and carrying (colour, T) across the cut changes no operation.
 template <bool COUNT, bool EXACT, bool CHUNK = false>
-__device__ __forceinline__ void forward_tile(FwdShared& s, const TileCtx& c, const uint32_t* __restrict__ tile_off,
+__device__ __forceinline__ uint32_t forward_tile(FwdShared& s, const TileCtx& c, const uint32_t* __restrict__ tile_off,
                                              const uint32_t* __restrict__ list, const ProjRec* __restrict__ proj,
-                                             unsigned long long* __restrict__ wave_masks, const Geometry& g,
+                                             unsigned long long* __restrict__ wave_masks, uint32_t* __restrict__ exec_list,
+                                             uint32_t* __restrict__ retire_hint, const Geometry& g,
                                              PairCounters* __restrict__ counters, f2& crg, float& cb, float* T_io = nullptr)
 {
+    constexpr bool HINT = !COUNT && !CHUNK;
     const int tid = c.tid, lane = c.lane, w = c.w;
     const f2 pxy = c.pxy;
     float T = 1.0f;
@@ -243,12 +286,29 @@ __device__ __forceinline__ void forward_tile(FwdShared& s, const TileCtx& c, con
 
     const uint32_t beg = tile_off[c.tile], end = tile_off[c.tile + 1];
     const int se = tid >> 2, sub = tid & 3;
-    for (uint32_t base = beg; base < end; base += B) {
-        const int cnt = (int)min((uint32_t)B, end - base);
+    uint32_t n_out = 0; // entries handed over so far
+    uint32_t hint = kNoHint, last_exec = 0;
+    bool retired = false;
+    if constexpr (HINT) hint = retire_hint[c.tile];
+    int pb = 1;
+    for (uint32_t base = beg, cnt_u = 0; base < end; base += cnt_u) {
+        uint32_t want = B;
+        if constexpr (HINT) {
+            const uint32_t pos = base - beg;
+            if (hint != kNoHint) {
+                if (hint <= pos) want = kHintFollow;
+                else if (hint - pos <= (uint32_t)B) want = (hint - pos + 15u) & ~15u;
+            }
+        }
+        cnt_u = min(want, end - base);
+        const int cnt = (int)cnt_u;
+        pb ^= 1;
+        unsigned long long* const s_mask = s.mask[pb];
         if (se < cnt) {
-            const ProjRec* r = proj + list[base + se];
+            const uint32_t idx = list[base + se];
+            const ProjRec* r = proj + idx;
             const float4 q0 = r->q0, q1 = r->q1, q2 = r->q2;
-            const int rows_hit = stage_masks(reinterpret_cast<uint32_t*>(s.mask), se, sub, q0, q1, __float_as_int(q2.y),
+            const int rows_hit = stage_masks(reinterpret_cast<uint32_t*>(s_mask), se, sub, q0, q1, __float_as_int(q2.y),
                                              __float_as_int(q2.z), c.ty * kTile, c.tx * kTile, g.W, g.row_end);
             if (COUNT) {
                 n_rows_hit += rows_hit;
@@ -259,14 +319,17 @@ __device__ __forceinline__ void forward_tile(FwdShared& s, const TileCtx& c, con
                 s.rec[se][0] = q0;
                 s.rec[se][1] = make_float4(q0.w, q1.x, q1.y, q1.z);
                 s.rec[se][2] = make_float4(q1.w, q2.x, 0.0f, 0.0f);
+                if (!COUNT) s.idx[pb][se] = idx;
             }
         }
         __syncthreads();
-        // keep the lane masks for the backward walk, which goes through exactly these batches (32 B per staged pair)
-        if (se < cnt) wave_masks[(size_t)(base + se) * 4 + sub] = s.mask[sub * B + se];
-        if (COUNT) n_staged += (tid == 0) ? (unsigned long long)cnt : 0ull;
+        if constexpr (COUNT) { // every staged entry, at its list position (32 B per staged pair)
+            if (se < cnt) wave_masks[(size_t)(base + se) * 4 + sub] = s_mask[sub * B + se];
+            n_staged += (tid == 0) ? (unsigned long long)cnt : 0ull;
+        }
+        unsigned long long touched = 0ull; // bit e: the body of entry e ran in this wave
         if (alive_mask != 0ull || COUNT) {
-            const unsigned long long my_mask = (lane < cnt) ? s.mask[w * B + lane] : 0ull;
+            const unsigned long long my_mask = (lane < cnt) ? s_mask[w * B + lane] : 0ull;
             // entries that touch a pixel of this wave's block that is still alive now (the counting build walks
             // every entry that touches the block at all, for its "visited" statistic); pixels only ever die, so
             // nothing is missed, and the per-entry test below still sees the mask of the moment
@@ -279,6 +342,7 @@ __device__ __forceinline__ void forward_tile(FwdShared& s, const TileCtx& c, con
                 const unsigned long long act = wm & alive_mask; // visited (main.cpp:511-514) and not cut off (:520)
                 if (act == 0ull) continue;
                 if (COUNT) n_exec += (lane == 0);
+                else touched |= 1ull << e;
                 // Branch-free body: lanes outside `act` run the same instructions with alpha forced to 0, which
                 // makes c += (T*c)*0 and T *= 1 exact no-ops.  The scalar mask itself is the select predicate.
                 const float4 q0 = s.rec[e][0], q1 = s.rec[e][1], q2 = s.rec[e][2];
@@ -296,9 +360,28 @@ __device__ __forceinline__ void forward_tile(FwdShared& s, const TileCtx& c, con
                 if (COUNT) n_act += (act >> lane) & 1ull;
             }
         }
-        if (!block_any_alive(&s.alive, w, lane, alive_mask)) break; // every pixel of the tile saturated: retire it
+        if constexpr (COUNT) {
+            if (!block_any_alive(&s.alive, w, lane, alive_mask)) break; // every pixel of the tile saturated: retire it
+        } else {
+            unsigned long long exec_mask;
+            const bool any = block_any_alive_exec(&s.alive, s.touched, w, lane, alive_mask, touched, &exec_mask);
+            // the entries some wave executed, compacted behind those of the batches before (nothing for the others)
+            if ((exec_mask >> se) & 1ull) { // (se >= cnt: never executed)
+                const uint32_t at = beg + n_out + (uint32_t)__popcll(exec_mask & ((1ull << se) - 1ull));
+                wave_masks[(size_t)at * 4 + sub] = s_mask[sub * B + se];
+                if (sub == 0) exec_list[at] = s.idx[pb][se];
+            }
+            n_out += (uint32_t)__popcll(exec_mask);
+            if (HINT && exec_mask != 0ull) last_exec = (base - beg) + 64u - (uint32_t)__builtin_clzll(exec_mask);
+            if (!any) { // every pixel of the tile saturated: retire it
+                retired = true;
+                break;
+            }
+        }
     }
     if (CHUNK) *T_io = T;
+    if constexpr (HINT)
+        if (tid == 0) retire_hint[c.tile] = retired ? last_exec : kNoHint;
     if (COUNT) {
         count_add(&counters->fwd_visited, n_vis, lane);
         count_add(&counters->fwd_active, n_act, lane);
@@ -307,6 +390,7 @@ __device__ __forceinline__ void forward_tile(FwdShared& s, const TileCtx& c, con
         count_add(&counters->fwd_rows_hit, n_rows_hit, lane);
         count_add(&counters->fwd_staged_hit, n_staged_hit, lane);
     }
+    return n_out;
 }
 
 // Optimistic launch: the host queues the first raster kernel of an iteration before it has seen the containment flag
@@ -324,8 +408,10 @@ __global__ __launch_bounds__(256) void raster_forward_kernel(const uint32_t* __r
                                                              const uint32_t* __restrict__ list,
                                                              const ProjRec* __restrict__ proj,
                                                              void* __restrict__ image0,
-                                                             unsigned long long* __restrict__ wave_masks, Geometry g,
-                                                             const DeviceStatus* __restrict__ status, int abort_stamp,
+                                                             unsigned long long* __restrict__ wave_masks,
+                                                             uint32_t* __restrict__ exec_list, uint32_t* __restrict__ tile_exec,
+                                                             uint32_t* __restrict__ retire_hint,
+                                                             Geometry g, const DeviceStatus* __restrict__ status, int abort_stamp,
                                                              int iteration, PairCounters* __restrict__ counters)
 {
     __shared__ FwdShared s;
@@ -335,7 +421,8 @@ __global__ __launch_bounds__(256) void raster_forward_kernel(const uint32_t* __r
     const TileCtx c = tile_ctx(tile, g);
     f2 crg;
     float cb;
-    forward_tile<COUNT, EXACT>(s, c, tile_off, list, proj, wave_masks, g, counters, crg, cb);
+    const uint32_t n_exec = forward_tile<COUNT, EXACT>(s, c, tile_off, list, proj, wave_masks, exec_list, retire_hint, g, counters, crg, cb);
+    if (!COUNT && c.tid == 0) tile_exec[tile] = n_exec; // the backward walk is another launch
     if (c.inside) store_pixel<HALF>(image0, pixel_index(c, g), make_float4(crg.x, crg.y, cb, 1.0f)); // .w reset, main.cpp:543-546
 }
 
@@ -456,9 +543,7 @@ struct DetSlots {
 
 // LDS of the backward walk.  Entries per staged batch: 64, or 32 in deterministic mode, whose four per-wave slot sets would
 // otherwise lift the workgroup from 18.9 to ~25 KB of LDS -- six instead of eight workgroups per CU, which alone costs
-// ~14 % (profiles/r03/r03_bound_experiments.txt); with half-size batches it is 17.1 KB.  The forward walk stages 64 either
-// way: the lane masks it leaves behind are indexed by list position, and a walk that looks at its pixels' throughput
-// every 32 entries stops no later than one that looks every 64.
+// ~14 % (profiles/r03/r03_bound_experiments.txt); with half-size batches it is 17.1 KB.
 template <bool DET>
 struct BwdShared {
     static constexpr int kBatch = DET ? 32 : B;
@@ -491,6 +576,8 @@ struct BwdShared {
 
 // One tile's backward walk (main.cpp:552-711 for its pixels) from the pixel's final colour `fin` and target `ref`:
 // adds the tile's partial gradients into grads (or its deterministic slots) and stores the tile's squared error.
+// It walks the n_handed entries the forward walk handed over (exec_list, wave_masks: see forward_tile), every one of which
+// has a body to run in some wave; a counting walk (COUNT) goes through the tile's whole list and ignores both.
 // CHUNK: as in forward_tile -- the list is one index range of the splats, *state_io (running colour r, g, b and T of
 // main.cpp:601-625, :707) is the pixel's state after the ranges before it on entry and after this range on return.
 template <bool COUNT, bool NEED_OP, bool DET, bool EXACT, bool CHUNK = false>
@@ -498,6 +585,7 @@ __device__ __forceinline__ void backward_tile(BwdShared<DET>& s, const TileCtx& 
                                               const uint32_t* __restrict__ tile_off, const uint32_t* __restrict__ list,
                                               const ProjRec* __restrict__ proj,
                                               const unsigned long long* __restrict__ wave_masks,
+                                              const uint32_t* __restrict__ exec_list, uint32_t n_handed,
                                               float* __restrict__ grads, double* __restrict__ tile_sqerr,
                                               const Geometry& g, const DetSlots& det, PairCounters* __restrict__ counters,
                                               const SqerrJob& sq, float4* state_io = nullptr)
@@ -557,16 +645,17 @@ __device__ __forceinline__ void backward_tile(BwdShared<DET>& s, const TileCtx& 
     unsigned long long alive_mask = __ballot(CHUNK ? inside && !(T < kMinThroughput) : inside); // wave-uniform, scalar registers (see the forward kernel)
     unsigned long long n_vis = 0, n_act = 0, n_staged = 0, n_exec = 0;
 
-    const uint32_t beg = tile_off[c.tile], end = tile_off[c.tile + 1];
+    const uint32_t beg = tile_off[c.tile];
+    const uint32_t end = beg + (COUNT ? tile_off[c.tile + 1] - beg : n_handed);
     const int se = tid >> 2, sub = tid & 3;
     for (uint32_t base = beg; base < end; base += BB) {
         const int cnt = (int)min((uint32_t)BB, end - base);
         const int pb = (int)(((base - beg) / (uint32_t)BB) & 1u); // which copy of the per-entry index words this batch uses
         if (se < cnt) {
-            // the forward pass of this iteration staged the same batch and left its lane masks behind
+            // the forward pass of this iteration left the lane masks behind
             s.mask[sub * BB + se] = wave_masks[(size_t)(base + se) * 4 + sub];
             if (sub == 0) {
-                const uint32_t idx = list[base + se];
+                const uint32_t idx = COUNT ? list[base + se] : exec_list[base + se];
                 s.idx[pb][se] = idx;
                 if (DET) { // the slot of this tile in the splat's emission rectangle (row-major), looked up beside the record
                     const TileRect r = det.rects[idx];
@@ -686,7 +775,10 @@ __device__ __forceinline__ void backward_tile(BwdShared<DET>& s, const TileCtx& 
             }
         }
         if (DET && lane == 0) s.touched[w] = touched;
-        const bool any = block_any_alive(&s.alive, w, lane, alive_mask);
+        // (the handed-over entries end with the last one any pixel was alive for: only a counting walk can retire early)
+        bool any = true;
+        if constexpr (COUNT) any = block_any_alive(&s.alive, w, lane, alive_mask);
+        else __syncthreads();
         // one burst per (tile, splat): 9 consecutive floats -- float atomics into grads[idx], or (deterministic
         // mode) plain stores into this tile's own slot of the splat, summed later in a fixed order
         for (int i = tid; i < cnt * 9; i += 256) {
@@ -738,6 +830,8 @@ __global__ __launch_bounds__(256) void raster_backward_kernel(const uint32_t* __
                                                               const void* __restrict__ image0,
                                                               const void* __restrict__ image_ref,
                                                               const unsigned long long* __restrict__ wave_masks,
+                                                              const uint32_t* __restrict__ exec_list,
+                                                              const uint32_t* __restrict__ tile_exec,
                                                               float* __restrict__ grads,
                                                               double* __restrict__ tile_sqerr, Geometry g,
                                                               DetSlots det, const DeviceStatus* __restrict__ status,
@@ -753,15 +847,18 @@ __global__ __launch_bounds__(256) void raster_backward_kernel(const uint32_t* __
         fin = load_pixel<HALF>(image0, pixel_index(c, g));    // finalColor, main.cpp:613
         ref = load_pixel<HALF>(image_ref, pixel_index(c, g));
     }
-    backward_tile<COUNT, NEED_OP, DET, EXACT>(s, c, fin, ref, tile_off, list, proj, wave_masks, grads, tile_sqerr, g, det, counters,
-                                              SqerrJob{nullptr, 0, nullptr, nullptr});
+    const uint32_t n_exec = COUNT ? 0u : tile_exec[tile];
+    backward_tile<COUNT, NEED_OP, DET, EXACT>(s, c, fin, ref, tile_off, list, proj, wave_masks, exec_list, n_exec, grads, tile_sqerr,
+                                              g, det, counters, SqerrJob{nullptr, 0, nullptr, nullptr});
 }
 
 // Forward and backward walk of a tile in ONE launch (what s2d_step and s2d_forward_backward queue): a tile's backward
 // pass needs nothing but its own pixels' final colours, which are still in registers when the forward walk ends.  One
 // dispatch, one ramp-down tail and one read of image0 (16 B per pixel) less per iteration than the two kernels above,
-// which remain for callers that run the passes separately.  The lane masks still travel through wave_masks (written
-// and read back by the same workgroup, so they rarely leave L2).  With S2D_CFG_FP16_IMAGES the backward walk sees the
+// which remain for callers that run the passes separately.  The executed entries still travel through exec_list and
+// wave_masks: written by the entry's staging threads and read back by other threads of the same workgroup (so they rarely
+// leave L2); the __syncthreads() between the walks orders the two at workgroup scope, and their number stays in a
+// register (tile_exec is written for an s2d_backward that may follow).  With S2D_CFG_FP16_IMAGES the backward walk sees the
 // final colour as stored, i.e. rounded to fp16, exactly like the separate kernels.  image0 is written only when
 // `write_image` is set (s2d_step: the last iteration of the call; nothing else reads it).
 template <bool NEED_OP, bool HALF, bool DET, bool EXACT>
@@ -770,6 +867,8 @@ __global__ __launch_bounds__(256, 8) void raster_fused_kernel(const uint32_t* __
                                                            const ProjRec* __restrict__ proj, void* __restrict__ image0,
                                                            const void* __restrict__ image_ref,
                                                            unsigned long long* __restrict__ wave_masks,
+                                                           uint32_t* __restrict__ exec_list, uint32_t* __restrict__ tile_exec,
+                                                           uint32_t* __restrict__ retire_hint,
                                                            float* __restrict__ grads, double* __restrict__ tile_sqerr,
                                                            Geometry g, DetSlots det,
                                                            const DeviceStatus* __restrict__ status, int abort_stamp,
@@ -783,7 +882,9 @@ __global__ __launch_bounds__(256, 8) void raster_fused_kernel(const uint32_t* __
     const TileCtx c = tile_ctx(tile, g);
     f2 crg;
     float cb;
-    forward_tile<false, EXACT>(*reinterpret_cast<FwdShared*>(smem), c, tile_off, list, proj, wave_masks, g, nullptr, crg, cb);
+    const uint32_t n_exec = forward_tile<false, EXACT>(*reinterpret_cast<FwdShared*>(smem), c, tile_off, list, proj, wave_masks,
+                                                       exec_list, retire_hint, g, nullptr, crg, cb);
+    if (c.tid == 0) tile_exec[tile] = n_exec;
     float4 fin = make_float4(crg.x, crg.y, cb, 1.0f), ref = make_float4(0.f, 0.f, 0.f, 0.f);
     if (HALF) { // what the backward pass would read back from the fp16 framebuffer
         const __half2 a = __floats2half2_rn(fin.x, fin.y), b = __floats2half2_rn(fin.z, fin.w);
@@ -796,9 +897,11 @@ __global__ __launch_bounds__(256, 8) void raster_fused_kernel(const uint32_t* __
     } else {
         fin = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    __syncthreads(); // the backward walk re-uses the LDS the forward walk's last flag exchange may still be reading
+    // the backward walk re-uses the LDS the forward walk's hand-over may still be reading, and reads what other threads
+    // of the workgroup handed over through global memory
+    __syncthreads();
     backward_tile<false, NEED_OP, DET, EXACT>(*reinterpret_cast<BwdShared<DET>*>(smem), c, fin, ref, tile_off, list, proj,
-                                              wave_masks, grads, tile_sqerr, g, det, nullptr, sq);
+                                              wave_masks, exec_list, n_exec, grads, tile_sqerr, g, det, nullptr, sq);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -810,7 +913,7 @@ __global__ __launch_bounds__(256, 8) void raster_fused_kernel(const uint32_t* __
 //                  so image0 is final after the last range -- or after the range behind which no pixel is alive any
 //                  more (*any_alive stays 0: the host skips the ranges that follow, in both passes).
 //   backward pass: raster_backward_chunk_kernel per range, from a fresh state: the forward walk of the range (only for its
-//                  lane masks -- the backward walk reads them back, exactly as in the fused kernel) and the backward
+//                  hand-over -- the backward walk reads it back, exactly as in the fused kernel) and the backward
 //                  walk from the same state, with the FINAL colours of the forward pass out of image0.
 // ---------------------------------------------------------------------------------------------------
 template <bool HALF, bool EXACT>
@@ -818,7 +921,8 @@ __global__ __launch_bounds__(256) void raster_forward_chunk_kernel(const uint32_
                                                                    const uint32_t* __restrict__ list,
                                                                    const ProjRec* __restrict__ proj, void* __restrict__ image0,
                                                                    float4* __restrict__ state, int first,
-                                                                   unsigned long long* __restrict__ wave_masks, Geometry g,
+                                                                   unsigned long long* __restrict__ wave_masks,
+                                                                   uint32_t* __restrict__ exec_list, Geometry g,
                                                                    const DeviceStatus* __restrict__ status, int iteration,
                                                                    uint32_t* __restrict__ any_alive)
 {
@@ -831,7 +935,7 @@ __global__ __launch_bounds__(256) void raster_forward_chunk_kernel(const uint32_
     if (!first && c.inside) st = state[pixel_index(c, g)];
     f2 crg = mk2(st.x, st.y);
     float cb = st.z, T = st.w;
-    forward_tile<false, EXACT, true>(s, c, tile_off, list, proj, wave_masks, g, nullptr, crg, cb, &T);
+    forward_tile<false, EXACT, true>(s, c, tile_off, list, proj, wave_masks, exec_list, nullptr, g, nullptr, crg, cb, &T);
     if (c.inside) {
         state[pixel_index(c, g)] = make_float4(crg.x, crg.y, cb, T);
         store_pixel<HALF>(image0, pixel_index(c, g), make_float4(crg.x, crg.y, cb, 1.0f)); // .w reset, main.cpp:543-546
@@ -847,6 +951,7 @@ __global__ __launch_bounds__(256) void raster_backward_chunk_kernel(const uint32
                                                                     const void* __restrict__ image_ref,
                                                                     float4* __restrict__ state, int first,
                                                                     unsigned long long* __restrict__ wave_masks,
+                                                                    uint32_t* __restrict__ exec_list,
                                                                     float* __restrict__ grads, double* __restrict__ tile_sqerr,
                                                                     Geometry g, DetSlots det,
                                                                     const DeviceStatus* __restrict__ status, int iteration)
@@ -864,14 +969,16 @@ __global__ __launch_bounds__(256) void raster_backward_chunk_kernel(const uint32
         fin = load_pixel<HALF>(image0, pixel_index(c, g));    // finalColor, main.cpp:613: of ALL ranges
         ref = load_pixel<HALF>(image_ref, pixel_index(c, g));
     }
-    {   // the lane masks of this range's batches, from the state the backward walk starts from (results discarded)
+    uint32_t n_exec;
+    {   // the executed entries of this range, from the state the backward walk starts from (colours discarded)
         f2 crg = mk2(st.x, st.y);
         float cb = st.z, T = st.w;
-        forward_tile<false, EXACT, true>(*reinterpret_cast<FwdShared*>(smem), c, tile_off, list, proj, wave_masks, g, nullptr, crg, cb, &T);
+        n_exec = forward_tile<false, EXACT, true>(*reinterpret_cast<FwdShared*>(smem), c, tile_off, list, proj, wave_masks, exec_list, nullptr, g,
+                                                  nullptr, crg, cb, &T);
     }
-    __syncthreads(); // the backward walk re-uses the LDS the forward walk's last flag exchange may still be reading
+    __syncthreads(); // as in the fused kernel: LDS re-use, and the hand-over through global memory
     backward_tile<false, NEED_OP, DET, EXACT, true>(*reinterpret_cast<BwdShared<DET>*>(smem), c, fin, ref, tile_off, list, proj,
-                                                    wave_masks, grads, tile_sqerr, g, det, nullptr,
+                                                    wave_masks, exec_list, n_exec, grads, tile_sqerr, g, det, nullptr,
                                                     SqerrJob{nullptr, 0, nullptr, nullptr}, &st);
     if (c.inside) state[pixel_index(c, g)] = st;
 }
@@ -992,34 +1099,35 @@ hipError_t launch_raster(RasterPass pass, const RasterArgs& a, hipStream_t strea
     case RasterPass::Forward:
         e = with_variant([&](auto exact, auto count, auto half) {
             hipLaunchKernelGGL((raster_forward_kernel<count, half, exact>), grid, block, 0, stream, a.tile_off, a.list, a.proj,
-                               a.image0, a.wave_masks, a.g, a.status, a.abort_stamp, a.iteration, a.counters);
+                               a.image0, a.wave_masks, a.exec_list, a.tile_exec, a.retire_hint, a.g, a.status, a.abort_stamp,
+                               a.iteration, a.counters);
         }, a.exact_exp, a.count, a.half_images);
         break;
     case RasterPass::Backward:
         e = with_variant([&](auto exact, auto count, auto half, auto op, auto d) {
             hipLaunchKernelGGL((raster_backward_kernel<count, op, half, d, exact>), grid, block, 0, stream, a.tile_off, a.list,
-                               a.proj, a.image0, a.image_ref, a.wave_masks, a.grads, a.tile_sqerr, a.g, det, a.status,
-                               a.iteration, a.counters);
+                               a.proj, a.image0, a.image_ref, a.wave_masks, a.exec_list, a.tile_exec, a.grads, a.tile_sqerr, a.g,
+                               det, a.status, a.iteration, a.counters);
         }, a.exact_exp, a.count, a.half_images, a.need_opacity_grad, gather);
         break;
     case RasterPass::Fused: // (pair counting is a property of the separate kernels)
         e = with_variant([&](auto exact, auto, auto half, auto op, auto d) {
             hipLaunchKernelGGL((raster_fused_kernel<op, half, d, exact>), grid, block, 0, stream, a.tile_off, a.list, a.proj,
-                               a.image0, a.image_ref, a.wave_masks, a.grads, a.tile_sqerr, a.g, det, a.status, a.abort_stamp,
-                               a.iteration, wi, a.sq);
+                               a.image0, a.image_ref, a.wave_masks, a.exec_list, a.tile_exec, a.retire_hint, a.grads, a.tile_sqerr,
+                               a.g, det, a.status, a.abort_stamp, a.iteration, wi, a.sq);
         }, a.exact_exp, no, a.half_images, a.need_opacity_grad, gather);
         break;
     case RasterPass::ForwardRange:
         e = with_variant([&](auto exact, auto, auto half) {
             hipLaunchKernelGGL((raster_forward_chunk_kernel<half, exact>), grid, block, 0, stream, a.tile_off, a.list, a.proj,
-                               a.image0, a.state, first, a.wave_masks, a.g, a.status, a.iteration, a.any_alive);
+                               a.image0, a.state, first, a.wave_masks, a.exec_list, a.g, a.status, a.iteration, a.any_alive);
         }, a.exact_exp, no, a.half_images);
         break;
     case RasterPass::BackwardRange:
         e = with_variant([&](auto exact, auto, auto half, auto op, auto d) {
             hipLaunchKernelGGL((raster_backward_chunk_kernel<op, half, d, exact>), grid, block, 0, stream, a.tile_off, a.list,
-                               a.proj, a.image0, a.image_ref, a.state, first, a.wave_masks, a.grads, a.tile_sqerr, a.g, det,
-                               a.status, a.iteration);
+                               a.proj, a.image0, a.image_ref, a.state, first, a.wave_masks, a.exec_list, a.grads, a.tile_sqerr,
+                               a.g, det, a.status, a.iteration);
         }, a.exact_exp, no, a.half_images, a.need_opacity_grad, gather);
         break;
     }
