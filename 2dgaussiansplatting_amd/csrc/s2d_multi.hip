@@ -48,6 +48,7 @@ namespace {
 
 using s2d::DevBuf; // here: arrays that only grow (reserve), re-allocated while the rank's stream is idle
 using s2d::Event;
+using s2d::HostBuf;
 
 struct Rccl {
     void* lib = nullptr;
@@ -189,46 +190,76 @@ struct HaloRank {
     long long handed = 0;                 // state rows sent or received so far (diagnostic)
 };
 
+// Everything one rank has.  Its own thread writes it while a command runs, the caller's thread between commands.  What
+// peers and the watchdog read meanwhile is atomic (comm, sent_seq, progress), guarded by s2d_multi::m (done, rc), or
+// read behind a rendezvous only (halo).
+struct Rank {
+    int index = 0, device = 0;
+    s2d_ctx* ctx = nullptr;
+    int row_begin = 0, row_end = 0;
+    HaloRank halo;
+    std::atomic<ncclComm_t> comm{nullptr}; // the communicator slot: see abort_collective for who may empty it
+    // Exchanges (since the hold sets were planned) whose gather and hipEventRecord this rank's thread has ISSUED.  A
+    // receiver may call hipStreamWaitEvent on the event of exchange k only once it is recorded -- the one thing the rank
+    // threads tell each other per iteration, pairwise and without sleeping (no barrier: the streams order the rest)
+    std::atomic<unsigned> sent_seq{0};
+    Progress progress;
+    // The events of the bounded stream waits: [0], [1] mark every 64th iteration of a step (rank_step waits for the one
+    // before last, so a wait never covers more than 128 iterations of device work and never leaves the device idle);
+    // [2] is for one-off drains.
+    Event ev_prog[3];
+    HostBuf<float> staging;    // replicated + share-gpu: pinned copy of the rank's partial gradients; rank 0's receives the sum
+    bool done = false;         // guarded by s2d_multi::m, like rc
+    int rc = S2D_OK;
+    std::string msg;           // failures of this file's own HIP calls (the contexts keep theirs)
+    std::vector<double> sqerr; // [iteration of the call]: partial squared errors
+
+    hipStream_t stream() const { return (hipStream_t)s2d_stream(ctx); }
+    // What the rank owns through the runtime goes on its device, with its stream idle (s2d_owned.h) and before its
+    // context: the worker at CMD_QUIT, or s2d_multi_destroy itself when no worker was ever started.
+    void let_go()
+    {
+        (void)hipSetDevice(device);
+        halo = HaloRank();
+        for (Event& e : ev_prog) e = Event();
+        staging.release();
+    }
+};
+
+// Whether the handle can go on, as the caller's thread knows it between commands (the rank threads and the watchdog
+// only raise the atomics collective_lost and timed_out; this is what the caller derives from them).  Ordered: a worse
+// state is never left for a better one, except NeedsState.
+//   a step failed (s2d_multi_step): NeedsState -- the ranks stand at different iterations; Dead when a communicator was
+//     aborted or a wait ran out on the way (the ranks no longer agree on where the run stands).
+//   every rank's counters set alike (s2d_multi_init_splats, s2d_multi_set_adam): NeedsState back to Usable, nothing else.
+//   the stop was not answered (the watchdog of run_command, in any command): Abandoned -- threads, contexts and device
+//     memory are never freed, no destructor of s2d_multi or Rank runs.
+// refuse() turns it into the status and message of a call that needs better.
+enum class Health { Usable, NeedsState, Dead, Abandoned };
+
 } // namespace
 
 struct s2d_multi {
     int world = 0, W = 0, H = 0, n = 0;
     bool share_gpu = false;
     int scheme = SCHEME_NONE;
-    std::vector<int> devices;
-    std::vector<s2d_ctx*> ctx;
-    std::vector<int> row_begin, row_end;
+    std::vector<Rank> ranks;        // sized once by s2d_multi_create (a Rank holds atomics and cannot move)
     Rccl rccl;
-    // One communicator per rank.  A slot is emptied (exchange(nullptr)) by whoever aborts or destroys it, so exactly one
-    // thread ever frees a communicator and nobody can pick up a freed one (a rank takes its OWN slot's value only).
-    std::unique_ptr<std::atomic<ncclComm_t>[]> comms;
-    int n_comms = 0;
-    std::vector<float*> host_grads; // replicated + share-gpu: pinned copies of the ranks' partial gradients; [0] receives the sum
     // slab ownership
-    std::vector<HaloRank> halo;
-    std::vector<int32_t> bounds;    // world + 1 row bounds
+    std::vector<int32_t> bounds;    // the world + 1 row bounds s2d_halo_masks takes
     int interval = 64;              // iterations between refreshes of the hold sets
     float margin = 0.0f;            // rows; must outlast one interval of Adam steps
     bool hold_valid = false;        // hold sets exist (otherwise every context holds, and has, everything)
     int hold_age = 0;               // iterations since they were made
     std::atomic<int> late{0};
-    // sent_seq[r]: exchanges (since the hold sets were planned) whose gather and hipEventRecord rank r's thread has ISSUED.
-    // A receiver may call hipStreamWaitEvent on r's event of exchange k only once r has recorded it -- the one thing the
-    // rank threads tell each other per iteration, pairwise and without sleeping (no barrier: the streams order the rest)
-    std::unique_ptr<std::atomic<unsigned>[]> sent_seq;
     std::atomic<bool> comms_aborted{false};   // a stop was published during the current command: no rank starts a collective any more
     std::atomic<bool> collective_lost{false}; // some communicator really was aborted
     std::atomic<bool> timed_out{false};       // some wait ran out: the ranks no longer agree on where the run stands
-    bool dead = false;              // a collective was aborted or a rank stopped answering: the handle must be re-created
-    bool failed_step = false;       // the last step failed: the ranks stand at different iterations until the state is set afresh
-    bool stuck = false;             // ... and some worker never came back: its thread and context are abandoned, not freed
+    Health health = Health::Usable;
     // A rank that stops answering (a device wait that never ends, a thread that died) must not hang the caller: every
     // wait of one rank for another, and for its own stream, gives up after this long without progress (milliseconds;
     // S2D_MULTI_STALL_TIMEOUT_MS or s2d_multi_set_stall_timeout; 0 = wait for ever, the behaviour up to round 3)
     std::atomic<int> stall_ms{30000};
-    std::unique_ptr<Progress[]> progress;
-    std::vector<hipEvent_t> ev_prog;      // [rank * 3 + which], see prog_event()
-    std::vector<char> rank_done;          // guarded by m
     // test hook (include/splat2d_test.h): rank `stall_rank` stops before its exchange of iteration `stall_iter`
     int stall_rank = -1, stall_iter = -1, stall_for_ms = 0;
     // command hand-out
@@ -240,9 +271,7 @@ struct s2d_multi {
     uint32_t step_flags = 0;
     int step_first_iter = 0;
     Barrier barrier;
-    std::vector<int> rank_rc;
-    std::vector<std::string> rank_msg; // failures of this file's own HIP calls (the contexts keep theirs)
-    std::vector<std::vector<double>> sqerr; // [rank][iteration of the call]: partial squared errors
+    double mse_norm = 1.0;          // H * W * 3, main.cpp:805
     int iterations = 0;
     char err[1280] = {0};
 };
@@ -258,22 +287,38 @@ int mfail(s2d_multi* m, int code, const char* fmt, ...)
     return code;
 }
 
-int rank_fail(s2d_multi* m, int rank, int code, const char* fmt, ...)
+int rank_fail(Rank& R, int code, const char* fmt, ...)
 {
     char buf[1024];
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(buf, sizeof(buf), fmt, ap);
     va_end(ap);
-    m->rank_msg[(size_t)rank] = buf;
+    R.msg = buf;
     return code;
 }
 
-#define MHIP(m, rank, call)                                                                               \
-    do {                                                                                                  \
-        const hipError_t e_ = (call);                                                                     \
-        if (e_ != hipSuccess) return rank_fail((m), (rank), S2D_E_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
+#define MHIP(R, call)                                                                                 \
+    do {                                                                                              \
+        const hipError_t e_ = (call);                                                                 \
+        if (e_ != hipSuccess) return rank_fail((R), S2D_E_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
     } while (0)
+
+void worsen(s2d_multi* m, Health to) { m->health = std::max(m->health, to); }
+void state_set_afresh(s2d_multi* m) { if (m->health == Health::NeedsState) m->health = Health::Usable; }
+
+// The answer to a call that needs the handle no worse than `limit`.
+int refuse(s2d_multi* m, Health limit)
+{
+    if (m->health <= limit) return S2D_OK;
+    if (m->health == Health::Abandoned) return S2D_E_STATE; // keeps the watchdog's report
+    if (m->health == Health::Dead)
+        return mfail(m, S2D_E_STATE, "%s; s2d_multi_destroy this handle and create a new one",
+                     m->collective_lost.load() ? "a collective of this handle was aborted after a rank failed: its communicators are gone"
+                                               : "a rank of this handle stopped answering and the ranks no longer agree on where the run stands");
+    return mfail(m, S2D_E_STATE, "the last s2d_multi_step failed and left the ranks at different iterations: s2d_multi_init_splats, or "
+                                 "s2d_multi_set_splats + s2d_multi_set_adam, first");
+}
 
 // Rows [r0, r1) of rank `rank`: whole 16-pixel tile rows, as even as possible (== distributed.slab_rows).
 void slab_rows(int height, int rank, int world, int* r0, int* r1)
@@ -284,12 +329,11 @@ void slab_rows(int height, int rank, int world, int* r0, int* r1)
     if (*r1 > height) *r1 = height;
 }
 
-inline void at_phase(s2d_multi* m, int rank, int phase, int iteration)
+inline void at_phase(Rank& R, int phase, int iteration)
 {
-    Progress& P = m->progress[(size_t)rank];
-    P.phase.store(phase, std::memory_order_relaxed);
-    P.iteration.store(iteration, std::memory_order_relaxed);
-    P.ticks.fetch_add(1, std::memory_order_release);
+    R.progress.phase.store(phase, std::memory_order_relaxed);
+    R.progress.iteration.store(iteration, std::memory_order_relaxed);
+    R.progress.ticks.fetch_add(1, std::memory_order_release);
 }
 
 // Where every rank's thread was last seen, for the reports below; and the rank furthest behind -- when a wait runs out
@@ -298,31 +342,32 @@ inline void at_phase(s2d_multi* m, int rank, int phase, int iteration)
 std::string phase_table(s2d_multi* m)
 {
     std::string out;
-    int worst = 0;
+    const Rank* worst = &m->ranks[0];
     long long worst_key = -1;
-    for (int q = 0; q < m->world; q++) {
-        const Progress& P = m->progress[(size_t)q];
-        const int ph = P.phase.load(), it = P.iteration.load();
+    for (const Rank& Q : m->ranks) {
+        const int ph = Q.progress.phase.load(), it = Q.progress.iteration.load();
         char one[96];
-        snprintf(one, sizeof(one), "%srank %d: %s, iteration %d", out.empty() ? "" : "; ", q, phase_name(ph), it);
+        snprintf(one, sizeof(one), "%srank %d: %s, iteration %d", out.empty() ? "" : "; ", Q.index, phase_name(ph), it);
         out += one;
         const long long key = ph == PH_DONE ? (1LL << 60) : (long long)it * 16 + ph;
         if (worst_key < 0 || key < worst_key) {
             worst_key = key;
-            worst = q;
+            worst = &Q;
         }
     }
     char tail[64];
-    snprintf(tail, sizeof(tail), "; furthest behind: rank %d (device %d)", worst, m->devices[(size_t)worst]);
+    snprintf(tail, sizeof(tail), "; furthest behind: rank %d (device %d)", worst->index, worst->device);
     return out + tail;
 }
 
-// This rank's communicator, taken out of its slot and aborted (RCCL then ends the kernels of this rank that wait for a
-// peer which will never arrive).  Whoever empties the slot owns the communicator: no second abort, no destroy afterwards.
-void abort_own_collective(s2d_multi* m, int rank)
+// Slot Q's communicator, taken out and aborted (RCCL then ends the kernels of that rank that wait for a peer which will
+// never arrive): by the rank itself, or by the watchdog for a rank that cannot look up.  Only whoever empties a slot
+// (exchange(nullptr): here, or s2d_multi_destroy) frees what it held, so exactly one thread ever frees a communicator,
+// and a rank submits to its OWN slot's value only, so nobody picks up a freed one.  collective_lost is set exactly when
+// a slot was emptied here.  (Only a replicated handle on several GPUs has communicators; elsewhere the slots are empty.)
+void abort_collective(s2d_multi* m, Rank& Q)
 {
-    if (m->scheme != SCHEME_REPLICATED || m->share_gpu || rank >= m->n_comms) return;
-    const ncclComm_t c = m->comms[(size_t)rank].exchange(nullptr);
+    const ncclComm_t c = Q.comm.exchange(nullptr);
     if (!c) return;
     m->collective_lost.store(true);
     if (m->rccl.CommAbort) (void)m->rccl.CommAbort(c);
@@ -330,54 +375,68 @@ void abort_own_collective(s2d_multi* m, int rank)
 
 // A rank has failed (or stopped answering): publish the stop FIRST -- no rank may start another collective, every rank
 // thread leaves its waits -- and only then give up this rank's own communicator.  The other ranks abort theirs when they
-// notice (stopped()): a communicator is never freed under the thread that may be submitting to it.
-void stop_everybody(s2d_multi* m, int rank)
+// notice (stopped(), all_reduce_grads): a communicator is never freed under the thread that may be submitting to it.
+// With a communicator gone the handle is dead afterwards: s2d_multi_destroy and a new s2d_multi_create bring it back.
+void stop_everybody(s2d_multi* m, Rank& R)
 {
     m->comms_aborted.store(true);
     m->barrier.abort();
-    abort_own_collective(m, rank);
+    abort_collective(m, R);
+}
+
+// A wait of rank R ran out -- for a peer, a rendezvous or its own stream: the ranks no longer agree on where the run
+// stands.  Says so, stops everybody and files R's report (S2D_E_STATE).
+int wait_ran_out(s2d_multi* m, Rank& R, const char* fmt, ...)
+{
+    char buf[1024];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    m->timed_out.store(true);
+    stop_everybody(m, R);
+    R.msg = buf;
+    return S2D_E_STATE;
 }
 
 // Called by a rank thread inside its waits: has somebody stopped the command?  If collectives were declared lost
 // (stop_everybody: a rank failed on the way or stopped answering) this rank gives up its communicator too.  A broken
 // barrier alone does not mean that: the finite guard (main.cpp:752-785) breaks it at the END of a rank's share, with every
 // collective of the call queued by everybody, and the handle stays usable.
-inline bool stopped(s2d_multi* m, int rank)
+inline bool stopped(s2d_multi* m, Rank& R)
 {
     if (!m->barrier.broken.load(std::memory_order_acquire)) return false;
-    if (m->comms_aborted.load()) abort_own_collective(m, rank);
+    if (m->comms_aborted.load()) abort_collective(m, R);
     return true;
 }
 
 // The rendezvous of the rank threads, for a rank: S2D_OK, kStopped (somebody else failed), or S2D_E_STATE when the wait itself ran out -- some rank
 // never arrived; the first rank to notice reports it.
-int meet_rank(s2d_multi* m, int r, const char* where)
+int meet_rank(s2d_multi* m, Rank& R, const char* where)
 {
-    m->barrier.wait(r);
+    m->barrier.wait(R.index);
     if (!m->barrier.broken) return S2D_OK;
     if (m->barrier.timed_out.exchange(false)) {
         const std::string table = phase_table(m);
         std::string who;
         const uint64_t missing = m->barrier.missing.load();
-        for (int q = 0; q < m->world; q++)
-            if ((missing >> q) & 1ull) {
+        for (const Rank& Q : m->ranks)
+            if ((missing >> Q.index) & 1ull) {
                 char one[48];
-                snprintf(one, sizeof(one), "%srank %d (device %d)", who.empty() ? "" : ", ", q, m->devices[(size_t)q]);
+                snprintf(one, sizeof(one), "%srank %d (device %d)", who.empty() ? "" : ", ", Q.index, Q.device);
                 who += one;
             }
-        m->timed_out.store(true);
-        stop_everybody(m, r);
-        return rank_fail(m, r, S2D_E_STATE, "%s did not reach the rendezvous of the %s within %d ms (the ranks now: %s)", who.c_str(), where,
-                         m->barrier.timeout_ms.load(), table.c_str());
+        return wait_ran_out(m, R, "%s did not reach the rendezvous of the %s within %d ms (the ranks now: %s)", who.c_str(), where,
+                            m->barrier.timeout_ms.load(), table.c_str());
     }
-    (void)stopped(m, r);
+    (void)stopped(m, R);
     return kStopped;
 }
 
-// Wait, with a bound, until event `ev` (recorded on rank r's stream) has completed.  hipStreamSynchronize would wait for
+// Wait, with a bound, until event `ev` (recorded on rank R's stream) has completed.  hipStreamSynchronize would wait for
 // ever behind a kernel that never ends (a collective whose peer is gone, a device that stopped); an event and a poll
 // let the thread notice a stop published by another rank, abort its own collective, and give up with a report.
-int wait_event(s2d_multi* m, int r, hipEvent_t ev, const char* what)
+int wait_event(s2d_multi* m, Rank& R, hipEvent_t ev, const char* what)
 {
     const int limit = m->stall_ms.load();
     const auto t0 = std::chrono::steady_clock::now();
@@ -385,69 +444,73 @@ int wait_event(s2d_multi* m, int r, hipEvent_t ev, const char* what)
     for (unsigned spins = 0;; spins++) {
         const hipError_t e = hipEventQuery(ev);
         if (e == hipSuccess) return aborted ? kStopped : S2D_OK;
-        if (e != hipErrorNotReady) return rank_fail(m, r, S2D_E_HIP, "hipEventQuery while %s: %s", what, hipGetErrorString(e));
-        if (!aborted && stopped(m, r)) aborted = true; // keep polling: with its collective aborted the stream drains
+        if (e != hipErrorNotReady) return rank_fail(R, S2D_E_HIP, "hipEventQuery while %s: %s", what, hipGetErrorString(e));
+        if (!aborted && stopped(m, R)) aborted = true; // keep polling: with its collective aborted the stream drains
         const long long waited = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
         if (limit > 0 && waited > (aborted ? 2LL * limit : (long long)limit)) {
             if (aborted) return kStopped; // somebody else already reports; this stream is left as it is
-            const Progress& P = m->progress[(size_t)r];
-            const std::string table = phase_table(m);
-            m->timed_out.store(true);
-            stop_everybody(m, r);
-            return rank_fail(m, r, S2D_E_STATE, "rank %d (device %d): the device did not finish the work queued on its stream within %d ms "
-                                                "while %s (iteration %d) -- its own kernels, or a collective / peer wait for a rank that "
-                                                "stopped answering (%s)", r, m->devices[(size_t)r], limit, what, P.iteration.load(), table.c_str());
+            return wait_ran_out(m, R, "rank %d (device %d): the device did not finish the work queued on its stream within %d ms "
+                                      "while %s (iteration %d) -- its own kernels, or a collective / peer wait for a rank that "
+                                      "stopped answering (%s)", R.index, R.device, limit, what, R.progress.iteration.load(), phase_table(m).c_str());
         }
         if (spins < 2000) std::this_thread::yield();
         else std::this_thread::sleep_for(std::chrono::microseconds(spins < 20000 ? 20 : 200));
     }
 }
 
-// Three events per rank: [0], [1] mark every 64th iteration of a step (rank_step waits for the one before last, so a
-// wait never covers more than 128 iterations of device work and never leaves the device idle); [2] is for one-off drains.
-int drain(s2d_multi* m, int r, hipEvent_t ev, hipStream_t stream, const char* what)
+// A bounded wait for everything queued on the rank's stream so far.
+int drain_now(s2d_multi* m, Rank& R, const char* what)
 {
-    if (ev == nullptr) { // before the events exist (creation failed half-way): the plain wait
-        MHIP(m, r, hipStreamSynchronize(stream));
-        return S2D_OK;
-    }
-    MHIP(m, r, hipEventRecord(ev, stream));
-    return wait_event(m, r, ev, what);
+    MHIP(R, hipEventRecord(R.ev_prog[2], R.stream()));
+    return wait_event(m, R, R.ev_prog[2], what);
 }
-
-inline hipEvent_t prog_event(s2d_multi* m, int r, int which) { return m->ev_prog.empty() ? nullptr : m->ev_prog[(size_t)r * 3 + (size_t)which]; }
-inline int drain_now(s2d_multi* m, int r, const char* what) { return drain(m, r, prog_event(m, r, 2), (hipStream_t)s2d_stream(m->ctx[(size_t)r]), what); }
-
 
 // Device-to-device copy between two ranks' buffers, queued on `stream` (the receiver's): over xGMI between two GPUs,
 // an ordinary device copy when the ranks share one.
-hipError_t rank_copy(s2d_multi* m, void* dst, int dst_rank, const void* src, int src_rank, size_t bytes, hipStream_t stream)
+hipError_t rank_copy(void* dst, const Rank& to, const void* src, const Rank& from, size_t bytes, hipStream_t stream)
 {
     if (bytes == 0) return hipSuccess;
-    const int dd = m->devices[(size_t)dst_rank], sd = m->devices[(size_t)src_rank];
-    if (dd == sd) return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream);
-    return hipMemcpyPeerAsync(dst, dd, src, sd, bytes, stream);
+    if (to.device == from.device) return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream);
+    return hipMemcpyPeerAsync(dst, to.device, src, from.device, bytes, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // replicated state: the sum RCCL would form, through host memory (S2D_MULTI_SHARE_GPU): every rank copies its partial
 // gradients out, rank 0 adds them in rank order, every rank copies the sum back in.
 // ---------------------------------------------------------------------------------------------------------------------
-int staged_all_reduce(s2d_multi* m, int rank, float* grads, size_t count, hipStream_t stream)
+int staged_all_reduce(s2d_multi* m, Rank& R, float* grads, size_t count)
 {
-    MHIP(m, rank, hipMemcpyAsync(m->host_grads[(size_t)rank], grads, count * sizeof(float), hipMemcpyDeviceToHost, stream));
-    if (int rc = drain_now(m, rank, "copying its gradients out for the staged all-reduce")) return rc;
-    if (int rc = meet_rank(m, rank, "staged all-reduce (partials out)")) return rc;
-    if (rank == 0)
+    hipStream_t stream = R.stream();
+    float* sum = m->ranks[0].staging;
+    MHIP(R, hipMemcpyAsync(R.staging, grads, count * sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (int rc = drain_now(m, R, "copying its gradients out for the staged all-reduce")) return rc;
+    if (int rc = meet_rank(m, R, "staged all-reduce (partials out)")) return rc;
+    if (R.index == 0)
         for (int q = 1; q < m->world; q++) {
-            const float* src = m->host_grads[(size_t)q];
-            float* dst = m->host_grads[0];
-            for (size_t k = 0; k < count; k++) dst[k] += src[k];
+            const float* src = m->ranks[(size_t)q].staging;
+            for (size_t k = 0; k < count; k++) sum[k] += src[k];
         }
-    if (int rc = meet_rank(m, rank, "staged all-reduce (sum formed)")) return rc;
-    MHIP(m, rank, hipMemcpyAsync(grads, m->host_grads[0], count * sizeof(float), hipMemcpyHostToDevice, stream));
-    if (int rc = drain_now(m, rank, "copying the summed gradients in")) return rc;
-    return meet_rank(m, rank, "staged all-reduce (sum read)"); // nobody overwrites its host copy before everybody has read the sum
+    if (int rc = meet_rank(m, R, "staged all-reduce (sum formed)")) return rc;
+    MHIP(R, hipMemcpyAsync(grads, sum, count * sizeof(float), hipMemcpyHostToDevice, stream));
+    if (int rc = drain_now(m, R, "copying the summed gradients in")) return rc;
+    return meet_rank(m, R, "staged all-reduce (sum read)"); // nobody overwrites its host copy before everybody has read the sum
+}
+
+// The all-reduce of one iteration's gradients, between s2d_forward_backward and s2d_adam_step (a handle on one device
+// goes through RCCL too: same code whatever N).
+int all_reduce_grads(s2d_multi* m, Rank& R)
+{
+    float* grads = (float*)s2d_grads_device_ptr(R.ctx);
+    const size_t count = (size_t)m->n * 9;
+    if (m->share_gpu) return m->world > 1 ? staged_all_reduce(m, R, grads, count) : S2D_OK;
+    if (m->comms_aborted.load()) { // a stop was published (the barrier breaks a moment later): not this rank's failure
+        abort_collective(m, R);
+        return kStopped;
+    }
+    const ncclComm_t comm = R.comm.load();
+    if (!comm) return rank_fail(R, S2D_E_STATE, "no communicator");
+    if (m->rccl.AllReduce(grads, grads, count, ncclFloat, ncclSum, comm, R.stream()) != ncclSuccess) return rank_fail(R, S2D_E_HIP, "ncclAllReduce failed");
+    return S2D_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -456,134 +519,141 @@ int staged_all_reduce(s2d_multi* m, int rank, float* grads, size_t count, hipStr
 // Exchange lists for the rank's current hold set: which gradient rows go to which peer (ascending ids per peer -- the
 // peer derives the same list from its identical mask words), and for every shared row where each holder's partial sits
 // in the receive buffer (s2d_grads_combine's table).
-int plan(s2d_multi* m, int r)
+int plan(s2d_multi* m, Rank& R)
 {
-    HaloRank& H = m->halo[(size_t)r];
-    const int world = m->world;
-    const uint32_t me = 1u << r;
-    hipStream_t stream = (hipStream_t)s2d_stream(m->ctx[(size_t)r]);
-    std::vector<std::vector<int32_t>> peer((size_t)world);
+    HaloRank& H = R.halo;
+    const size_t world = (size_t)m->world, r = (size_t)R.index;
+    const uint32_t me = 1u << R.index;
+    hipStream_t stream = R.stream();
+    std::vector<std::vector<int32_t>> peer(world);
     std::vector<int32_t> rows, src;
     for (const int32_t i : H.held) {
         uint32_t others = H.mask[(size_t)i] & ~me;
         if (!others) continue;
         const size_t u = rows.size();
         rows.push_back(i);
-        src.resize((u + 1) * (size_t)world, -1);
-        src[u * (size_t)world + (size_t)r] = -2;
+        src.resize((u + 1) * world, -1);
+        src[u * world + r] = -2;
         while (others) {
-            const int p = __builtin_ctz(others);
+            const size_t p = (size_t)__builtin_ctz(others);
             others &= others - 1u;
-            src[u * (size_t)world + (size_t)p] = (int32_t)peer[(size_t)p].size(); // + the peer's offset, below
-            peer[(size_t)p].push_back(i);
+            src[u * world + p] = (int32_t)peer[p].size(); // + the peer's offset, below
+            peer[p].push_back(i);
         }
     }
-    H.splits.assign((size_t)world, 0);
-    H.offsets.assign((size_t)world, 0);
+    H.splits.assign(world, 0);
+    H.offsets.assign(world, 0);
     int total = 0;
-    for (int p = 0; p < world; p++) {
-        H.offsets[(size_t)p] = total;
-        H.splits[(size_t)p] = (int32_t)peer[(size_t)p].size();
-        total += H.splits[(size_t)p];
+    for (size_t p = 0; p < world; p++) {
+        H.offsets[p] = total;
+        H.splits[p] = (int32_t)peer[p].size();
+        total += H.splits[p];
     }
     for (size_t u = 0; u < rows.size(); u++)
-        for (int p = 0; p < world; p++)
-            if (src[u * (size_t)world + (size_t)p] >= 0) src[u * (size_t)world + (size_t)p] += H.offsets[(size_t)p];
+        for (size_t p = 0; p < world; p++)
+            if (src[u * world + p] >= 0) src[u * world + p] += H.offsets[p];
     std::vector<int32_t> send_ids;
     send_ids.reserve((size_t)total);
-    for (int p = 0; p < world; p++) send_ids.insert(send_ids.end(), peer[(size_t)p].begin(), peer[(size_t)p].end());
+    for (size_t p = 0; p < world; p++) send_ids.insert(send_ids.end(), peer[p].begin(), peer[p].end());
     H.total = total;
     H.n_rows = (int)rows.size();
     H.seq = 0;
-    m->sent_seq[(size_t)r].store(0u, std::memory_order_release); // every rank thread is behind a barrier here, none is waiting on it
-    MHIP(m, r, H.d_send_ids.reserve((size_t)total));
-    MHIP(m, r, H.d_send[0].reserve((size_t)total * 9));
-    MHIP(m, r, H.d_send[1].reserve((size_t)total * 9));
-    MHIP(m, r, H.d_recv.reserve((size_t)total * 9));
-    MHIP(m, r, H.d_rows.reserve(rows.size()));
-    MHIP(m, r, H.d_src.reserve(src.size()));
-    if (total) MHIP(m, r, hipMemcpyAsync(H.d_send_ids, send_ids.data(), (size_t)total * 4, hipMemcpyHostToDevice, stream));
+    R.sent_seq.store(0u, std::memory_order_release); // every rank thread is behind a barrier here, none is waiting on it
+    MHIP(R, H.d_send_ids.reserve((size_t)total));
+    MHIP(R, H.d_send[0].reserve((size_t)total * 9));
+    MHIP(R, H.d_send[1].reserve((size_t)total * 9));
+    MHIP(R, H.d_recv.reserve((size_t)total * 9));
+    MHIP(R, H.d_rows.reserve(rows.size()));
+    MHIP(R, H.d_src.reserve(src.size()));
+    if (total) MHIP(R, hipMemcpyAsync(H.d_send_ids, send_ids.data(), (size_t)total * 4, hipMemcpyHostToDevice, stream));
     if (!rows.empty()) {
-        MHIP(m, r, hipMemcpyAsync(H.d_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, stream));
-        MHIP(m, r, hipMemcpyAsync(H.d_src, src.data(), src.size() * 4, hipMemcpyHostToDevice, stream));
+        MHIP(R, hipMemcpyAsync(H.d_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, stream));
+        MHIP(R, hipMemcpyAsync(H.d_src, src.data(), src.size() * 4, hipMemcpyHostToDevice, stream));
     }
-    return drain_now(m, r, "uploading its exchange plan"); // the host vectors go away
+    return drain_now(m, R, "uploading its exchange plan"); // the host vectors go away
 }
 
 // After the plans of all ranks are in (behind a barrier): does anybody swap anything, and do the two sides of every
 // pair agree on how much?
-int settle_plans(s2d_multi* m, int r)
+int settle_plans(s2d_multi* m, Rank& R)
 {
-    HaloRank& H = m->halo[(size_t)r];
+    HaloRank& H = R.halo;
     H.any_exchange = false;
-    for (int p = 0; p < m->world; p++) {
-        const HaloRank& P = m->halo[(size_t)p];
-        H.any_exchange = H.any_exchange || P.total > 0;
-        if (p != r && P.splits[(size_t)r] != H.splits[(size_t)p])
-            return rank_fail(m, r, S2D_E_STATE, "slab ownership: ranks %d and %d disagree on the rows they share (%d vs %d)", r, p,
-                             H.splits[(size_t)p], P.splits[(size_t)r]);
+    for (const Rank& P : m->ranks) {
+        H.any_exchange = H.any_exchange || P.halo.total > 0;
+        const int mine = H.splits[(size_t)P.index], theirs = P.halo.splits[(size_t)R.index];
+        if (&P != &R && theirs != mine)
+            return rank_fail(R, S2D_E_STATE, "slab ownership: ranks %d and %d disagree on the rows they share (%d vs %d)", R.index, P.index, mine, theirs);
     }
     return S2D_OK;
 }
 
-// Hold sets from scratch; every context holds a complete, identical copy of the splats and the Adam state.
-int hold_fresh(s2d_multi* m, int r)
+// The end of hold_fresh and of refresh: the rank's new hold-set words (H.mask) go to its context -- `arrivals`: some
+// splat is new here, the tile lists are stale -- its exchange plan is made, and behind the rendezvous `where` the
+// plans of all ranks are checked against each other.
+int adopt_hold_set(s2d_multi* m, Rank& R, bool arrivals, const char* where)
 {
-    HaloRank& H = m->halo[(size_t)r];
-    s2d_ctx* c = m->ctx[(size_t)r];
-    hipStream_t stream = (hipStream_t)s2d_stream(c);
-    const size_t n = (size_t)m->n;
-    MHIP(m, r, hipSetDevice(m->devices[(size_t)r]));
+    HaloRank& H = R.halo;
+    MHIP(R, hipMemcpyAsync(H.d_mask, H.mask.data(), (size_t)m->n * 4, hipMemcpyHostToDevice, R.stream()));
+    if (int rc = s2d_halo_commit(R.ctx, H.d_mask, R.index, arrivals)) return rc;
+    if (int rc = plan(m, R)) return rc;
+    if (int rc = meet_rank(m, R, where)) return rc; // plans are in; after a refresh the outgoing buffers may be re-used
+    return settle_plans(m, R);
+}
+
+// Hold sets from scratch; every context holds a complete, identical copy of the splats and the Adam state.
+int hold_fresh(s2d_multi* m, Rank& R)
+{
+    HaloRank& H = R.halo;
+    const int r = R.index;
+    const size_t n = (size_t)m->n, world = (size_t)m->world;
+    MHIP(R, hipSetDevice(R.device));
     for (Event& e : H.ev_sent)
-        if (!e) MHIP(m, r, e.create(hipEventDisableTiming));
-    if (int rc = s2d_halo_commit(c, nullptr, r, 0)) return rc; // hold everything: the masks below cover every splat
-    MHIP(m, r, H.d_mask.reserve(n));
+        if (!e) MHIP(R, e.create(hipEventDisableTiming));
+    if (int rc = s2d_halo_commit(R.ctx, nullptr, r, 0)) return rc; // hold everything: the masks below cover every splat
+    MHIP(R, H.d_mask.reserve(n));
     H.fresh.resize(n);
     H.mask.assign(n, 0u);
     H.held.clear();
-    H.out_ids.assign((size_t)m->world, {});
-    H.out_mask.assign((size_t)m->world, {});
-    H.out_off.assign((size_t)m->world, 0);
-    if (int rc = s2d_halo_masks(c, m->world, m->bounds.data(), m->margin, H.d_mask)) return rc;
-    MHIP(m, r, hipMemcpyAsync(H.fresh.data(), H.d_mask, n * 4, hipMemcpyDeviceToHost, stream));
-    if (int rc = drain_now(m, r, "reading the hold-set words")) return rc;
+    H.out_ids.assign(world, {});
+    H.out_mask.assign(world, {});
+    H.out_off.assign(world, 0);
+    if (int rc = s2d_halo_masks(R.ctx, m->world, m->bounds.data(), m->margin, H.d_mask)) return rc;
+    MHIP(R, hipMemcpyAsync(H.fresh.data(), H.d_mask, n * 4, hipMemcpyDeviceToHost, R.stream()));
+    if (int rc = drain_now(m, R, "reading the hold-set words")) return rc;
     for (size_t i = 0; i < n; i++)
         if ((H.fresh[i] >> r) & 1u) {
             H.mask[i] = H.fresh[i];
             H.held.push_back((int32_t)i);
         }
-    MHIP(m, r, hipMemcpyAsync(H.d_mask, H.mask.data(), n * 4, hipMemcpyHostToDevice, stream));
-    if (int rc = s2d_halo_commit(c, H.d_mask, r, 1)) return rc;
-    if (int rc = plan(m, r)) return rc;
-    if (int rc = meet_rank(m, r, "hold sets")) return rc;
-    return settle_plans(m, r);
+    return adopt_hold_set(m, R, true, "hold sets");
 }
+
+inline bool lowest_holder(uint32_t mask, int r) { return mask != 0u && (mask & (0u - mask)) == (1u << r); }
 
 // Refresh the hold sets from the current parameters (every `interval` iterations).  A splat that has come within
 // reach + margin of a rank that does not hold it yet is handed over -- parameters and Adam moments, by its
 // lowest-ranked holder -- before it can touch that rank's rows; a holder it has left drops it.
-int refresh(s2d_multi* m, int r)
+int refresh(s2d_multi* m, Rank& R)
 {
-    HaloRank& H = m->halo[(size_t)r];
-    s2d_ctx* c = m->ctx[(size_t)r];
-    hipStream_t stream = (hipStream_t)s2d_stream(c);
-    const int world = m->world;
+    HaloRank& H = R.halo;
+    s2d_ctx* c = R.ctx;
+    hipStream_t stream = R.stream();
+    const int r = R.index;
     const size_t n = (size_t)m->n;
     const uint32_t me = 1u << r;
-    if (int rc = drain_now(m, r, "finishing the iterations before a hold-set refresh")) return rc; // up to `interval` iterations of device work
+    if (int rc = drain_now(m, R, "finishing the iterations before a hold-set refresh")) return rc; // up to `interval` iterations of device work
     if (int rc = s2d_synchronize(c)) return rc; // the finite guard; and every copy this rank queued has landed
-    if (int rc = s2d_halo_masks(c, world, m->bounds.data(), m->margin, H.d_mask)) return rc;
-    MHIP(m, r, hipMemcpyAsync(H.fresh.data(), H.d_mask, n * 4, hipMemcpyDeviceToHost, stream));
-    if (int rc = drain_now(m, r, "reading the hold-set words")) return rc;
-    for (int q = 0; q < world; q++) {
-        H.out_ids[(size_t)q].clear();
-        H.out_mask[(size_t)q].clear();
-    }
+    if (int rc = s2d_halo_masks(c, m->world, m->bounds.data(), m->margin, H.d_mask)) return rc;
+    MHIP(R, hipMemcpyAsync(H.fresh.data(), H.d_mask, n * 4, hipMemcpyDeviceToHost, stream));
+    if (int rc = drain_now(m, R, "reading the hold-set words")) return rc;
+    for (auto& ids : H.out_ids) ids.clear();
+    for (auto& words : H.out_mask) words.clear();
     std::vector<int32_t> keep;
     keep.reserve(H.held.size());
     for (const int32_t i : H.held) {
         const uint32_t old = H.mask[(size_t)i], now = H.fresh[(size_t)i];
-        if ((old & (0u - old)) == me) { // the lowest-ranked old holder hands the splat to its new holders
+        if (lowest_holder(old, r)) { // the lowest-ranked old holder hands the splat to its new holders
             uint32_t arriving = now & ~old;
             while (arriving) {
                 const int q = __builtin_ctz(arriving);
@@ -601,53 +671,52 @@ int refresh(s2d_multi* m, int r)
     }
     // outgoing state rows, one segment per destination
     std::vector<int32_t> pay_ids;
-    for (int q = 0; q < world; q++) {
-        H.out_off[(size_t)q] = (int32_t)pay_ids.size();
-        pay_ids.insert(pay_ids.end(), H.out_ids[(size_t)q].begin(), H.out_ids[(size_t)q].end());
+    for (const Rank& Q : m->ranks) {
+        const std::vector<int32_t>& ids = H.out_ids[(size_t)Q.index];
+        H.out_off[(size_t)Q.index] = (int32_t)pay_ids.size();
+        pay_ids.insert(pay_ids.end(), ids.begin(), ids.end());
     }
     const int k_out = (int)pay_ids.size();
     if (k_out) {
-        MHIP(m, r, H.d_pay_ids.reserve((size_t)k_out));
-        MHIP(m, r, H.d_pay_sp.reserve((size_t)k_out * 9));
-        MHIP(m, r, H.d_pay_ad.reserve((size_t)k_out * 18));
-        MHIP(m, r, hipMemcpyAsync(H.d_pay_ids, pay_ids.data(), (size_t)k_out * 4, hipMemcpyHostToDevice, stream));
+        MHIP(R, H.d_pay_ids.reserve((size_t)k_out));
+        MHIP(R, H.d_pay_sp.reserve((size_t)k_out * 9));
+        MHIP(R, H.d_pay_ad.reserve((size_t)k_out * 18));
+        MHIP(R, hipMemcpyAsync(H.d_pay_ids, pay_ids.data(), (size_t)k_out * 4, hipMemcpyHostToDevice, stream));
         if (int rc = s2d_rows_gather(c, S2D_ROWS_SPLATS, H.d_pay_ids, k_out, H.d_pay_sp)) return rc;
         if (int rc = s2d_rows_gather(c, S2D_ROWS_ADAM, H.d_pay_ids, k_out, H.d_pay_ad)) return rc;
-        if (int rc = drain_now(m, r, "gathering the state rows it hands over")) return rc;
+        if (int rc = drain_now(m, R, "gathering the state rows it hands over")) return rc;
     }
-    if (int rc = meet_rank(m, r, "hold-set refresh (state rows out)")) return rc; // every rank's outgoing rows are in place, every stream is idle
+    if (int rc = meet_rank(m, R, "hold-set refresh (state rows out)")) return rc; // every rank's outgoing rows are in place, every stream is idle
     // incoming state rows, in sender order
     std::vector<int32_t> in_ids;
     std::vector<uint32_t> in_mask;
-    for (int p = 0; p < world; p++)
-        if (p != r) {
-            const HaloRank& P = m->halo[(size_t)p];
-            in_ids.insert(in_ids.end(), P.out_ids[(size_t)r].begin(), P.out_ids[(size_t)r].end());
-            in_mask.insert(in_mask.end(), P.out_mask[(size_t)r].begin(), P.out_mask[(size_t)r].end());
+    for (const Rank& P : m->ranks)
+        if (&P != &R) {
+            in_ids.insert(in_ids.end(), P.halo.out_ids[(size_t)r].begin(), P.halo.out_ids[(size_t)r].end());
+            in_mask.insert(in_mask.end(), P.halo.out_mask[(size_t)r].begin(), P.halo.out_mask[(size_t)r].end());
         }
     const int k_in = (int)in_ids.size();
     int late = 0;
     if (k_in) {
-        MHIP(m, r, H.d_in_ids.reserve((size_t)k_in));
-        MHIP(m, r, H.d_in_sp.reserve((size_t)k_in * 9));
-        MHIP(m, r, H.d_in_ad.reserve((size_t)k_in * 18));
-        MHIP(m, r, hipMemcpyAsync(H.d_in_ids, in_ids.data(), (size_t)k_in * 4, hipMemcpyHostToDevice, stream));
+        MHIP(R, H.d_in_ids.reserve((size_t)k_in));
+        MHIP(R, H.d_in_sp.reserve((size_t)k_in * 9));
+        MHIP(R, H.d_in_ad.reserve((size_t)k_in * 18));
+        MHIP(R, hipMemcpyAsync(H.d_in_ids, in_ids.data(), (size_t)k_in * 4, hipMemcpyHostToDevice, stream));
         size_t off = 0;
-        for (int p = 0; p < world; p++)
-            if (p != r) {
-                const HaloRank& P = m->halo[(size_t)p];
-                const size_t cnt = P.out_ids[(size_t)r].size(), from = (size_t)P.out_off[(size_t)r];
+        for (const Rank& P : m->ranks)
+            if (&P != &R) {
+                const size_t cnt = P.halo.out_ids[(size_t)r].size(), from = (size_t)P.halo.out_off[(size_t)r];
                 if (!cnt) continue;
-                MHIP(m, r, rank_copy(m, H.d_in_sp + off * 9, r, P.d_pay_sp + from * 9, p, cnt * 9 * sizeof(float), stream));
-                MHIP(m, r, rank_copy(m, H.d_in_ad + off * 18, r, P.d_pay_ad + from * 18, p, cnt * 18 * sizeof(float), stream));
+                MHIP(R, rank_copy(H.d_in_sp + off * 9, R, P.halo.d_pay_sp + from * 9, P, cnt * 9 * sizeof(float), stream));
+                MHIP(R, rank_copy(H.d_in_ad + off * 18, R, P.halo.d_pay_ad + from * 18, P, cnt * 18 * sizeof(float), stream));
                 off += cnt;
             }
         std::vector<float> sp((size_t)k_in * 9);
-        MHIP(m, r, hipMemcpyAsync(sp.data(), H.d_in_sp, sp.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
-        if (int rc = drain_now(m, r, "fetching the state rows handed to it")) return rc;
+        MHIP(R, hipMemcpyAsync(sp.data(), H.d_in_sp, sp.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
+        if (int rc = drain_now(m, R, "fetching the state rows handed to it")) return rc;
         // a splat that arrives already touching this rank's rows was rasterised here without being listed: the margin
         // did not outlast the interval
-        const float r0 = (float)m->bounds[(size_t)r], r1 = (float)m->bounds[(size_t)r + 1];
+        const float r0 = (float)R.row_begin, r1 = (float)R.row_end;
         for (int j = 0; j < k_in; j++) {
             const float* q = sp.data() + (size_t)j * 9;
             const float reach = 3.0f * std::max(q[2], q[3]) + 2.0f;
@@ -655,10 +724,10 @@ int refresh(s2d_multi* m, int r)
         }
     }
     if (late) m->late.fetch_add(late);
-    if (int rc = meet_rank(m, r, "hold-set refresh (state rows in)")) return rc; // everybody has fetched its rows and reported late arrivals
+    if (int rc = meet_rank(m, R, "hold-set refresh (state rows in)")) return rc; // everybody has fetched its rows and reported late arrivals
     if (m->late.load() > 0)        // fatal on every rank alike
-        return rank_fail(m, r, S2D_E_STATE, "slab ownership: %d splat(s) reached the rows of a rank before their state was handed "
-                                            "over (%d on rank %d): the margin of %.1f rows did not outlast %d iterations",
+        return rank_fail(R, S2D_E_STATE, "slab ownership: %d splat(s) reached the rows of a rank before their state was handed "
+                                         "over (%d on rank %d): the margin of %.1f rows did not outlast %d iterations",
                          m->late.load(), late, r, (double)m->margin, m->interval);
     if (k_in) {
         if (int rc = s2d_rows_scatter(c, S2D_ROWS_SPLATS, H.d_in_ids, k_in, H.d_in_sp)) return rc;
@@ -669,25 +738,20 @@ int refresh(s2d_multi* m, int r)
     }
     H.held.swap(keep);
     H.handed += k_out + k_in;
-    MHIP(m, r, hipMemcpyAsync(H.d_mask, H.mask.data(), n * 4, hipMemcpyHostToDevice, stream));
-    if (int rc = s2d_halo_commit(c, H.d_mask, r, k_in > 0)) return rc; // departures alone leave the tile lists valid
-    if (int rc = plan(m, r)) return rc;
-    if (int rc = meet_rank(m, r, "hold-set refresh (plans)")) return rc; // plans are in; the outgoing buffers may be re-used
-    return settle_plans(m, r);
+    return adopt_hold_set(m, R, k_in > 0, "hold-set refresh (plans)"); // departures alone leave the tile lists valid
 }
 
-// Has rank p's thread issued (gathered + recorded the event of) exchange number `seq`?  Spins without sleeping at first:
+// Has rank P's thread issued (gathered + recorded the event of) exchange number `seq`?  Spins without sleeping at first:
 // the threads queue an iteration in tens of microseconds and run at the same pace, so the wait is short.  A failed rank
 // ends it (kStopped); a rank that does not answer within the stall limit ends it too, with a report that names it
 // (S2D_E_STATE): the reference's only failure policy is abort() (main.cpp:752-785), the boundary turns "a rank stopped
 // answering" into a status like the rest.
-int wait_issued(s2d_multi* m, int r, int p, unsigned seq)
+int wait_issued(s2d_multi* m, Rank& R, const Rank& P, unsigned seq)
 {
-    const std::atomic<unsigned>& a = m->sent_seq[(size_t)p];
     const int limit = m->stall_ms.load();
     std::chrono::steady_clock::time_point t0;
-    for (unsigned spins = 0; a.load(std::memory_order_acquire) < seq; spins++) {
-        if (stopped(m, r)) return kStopped;
+    for (unsigned spins = 0; P.sent_seq.load(std::memory_order_acquire) < seq; spins++) {
+        if (stopped(m, R)) return kStopped;
         if (spins <= 64) continue;
         if (spins == 65) t0 = std::chrono::steady_clock::now();
         if (spins < 4096) {
@@ -695,15 +759,10 @@ int wait_issued(s2d_multi* m, int r, int p, unsigned seq)
             continue;
         }
         std::this_thread::sleep_for(std::chrono::microseconds(50));
-        if (limit > 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(limit)) {
-            const Progress& P = m->progress[(size_t)p];
-            const int it = m->progress[(size_t)r].iteration.load();
-            m->timed_out.store(true);
-            stop_everybody(m, r);
-            return rank_fail(m, r, S2D_E_STATE, "rank %d (device %d) stopped answering: it has not issued gradient exchange %u (iteration %d) "
-                                                "%d ms after rank %d asked for it; it was last seen at '%s', iteration %d", p,
-                             m->devices[(size_t)p], seq, it, limit, r, phase_name(P.phase.load()), P.iteration.load());
-        }
+        if (limit > 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(limit))
+            return wait_ran_out(m, R, "rank %d (device %d) stopped answering: it has not issued gradient exchange %u (iteration %d) "
+                                      "%d ms after rank %d asked for it; it was last seen at '%s', iteration %d", P.index, P.device, seq,
+                                R.progress.iteration.load(), limit, R.index, phase_name(P.progress.phase.load()), P.progress.iteration.load());
     }
     return S2D_OK;
 }
@@ -717,117 +776,100 @@ int wait_issued(s2d_multi* m, int r, int p, unsigned seq)
 // this rank's stream has waited for every neighbour's event k + 1, which that neighbour recorded behind its copy of k
 // (exchanges are symmetric: who receives from a rank also sends to it), and the neighbour's thread called
 // hipStreamWaitEvent for k before it recorded k + 1, so re-recording the event at k + 2 cannot overtake that call.
-int exchange_grads(s2d_multi* m, int r)
+int exchange_grads(s2d_multi* m, Rank& R)
 {
-    HaloRank& H = m->halo[(size_t)r];
+    HaloRank& H = R.halo;
     if (!H.any_exchange) return S2D_OK;
-    s2d_ctx* c = m->ctx[(size_t)r];
-    hipStream_t stream = (hipStream_t)s2d_stream(c);
+    s2d_ctx* c = R.ctx;
+    hipStream_t stream = R.stream();
     const unsigned seq = ++H.seq;
     const int b = (int)((seq - 1u) & 1u);
     if (H.total) {
         if (int rc = s2d_rows_gather(c, S2D_ROWS_GRADS, H.d_send_ids, H.total, H.d_send[b])) return rc;
-        MHIP(m, r, hipEventRecord(H.ev_sent[b], stream));
+        MHIP(R, hipEventRecord(H.ev_sent[b], stream));
     }
-    m->sent_seq[(size_t)r].store(seq, std::memory_order_release);
-    for (int p = 0; p < m->world; p++) {
-        const int cnt = H.splits[(size_t)p];
-        if (p == r || cnt == 0) continue;
-        if (int rc = wait_issued(m, r, p, seq)) return rc;
-        const HaloRank& P = m->halo[(size_t)p];
-        MHIP(m, r, hipStreamWaitEvent(stream, P.ev_sent[b], 0));
-        MHIP(m, r, rank_copy(m, H.d_recv + (size_t)H.offsets[(size_t)p] * 9, r, P.d_send[b] + (size_t)P.offsets[(size_t)r] * 9, p,
-                             (size_t)cnt * 9 * sizeof(float), stream));
+    R.sent_seq.store(seq, std::memory_order_release);
+    for (const Rank& P : m->ranks) {
+        const int cnt = H.splits[(size_t)P.index];
+        if (&P == &R || cnt == 0) continue;
+        if (int rc = wait_issued(m, R, P, seq)) return rc;
+        MHIP(R, hipStreamWaitEvent(stream, P.halo.ev_sent[b], 0));
+        MHIP(R, rank_copy(H.d_recv + (size_t)H.offsets[(size_t)P.index] * 9, R, P.halo.d_send[b] + (size_t)P.halo.offsets[(size_t)R.index] * 9, P,
+                          (size_t)cnt * 9 * sizeof(float), stream));
     }
     if (H.n_rows)
         if (int rc = s2d_grads_combine(c, H.d_rows, H.n_rows, H.d_src, m->world, H.d_recv)) return rc;
     return S2D_OK;
 }
 
-// One rank's share of s2d_multi_step: `iters` frames of main.cpp:334 on its rows.
-//
-// Replicated state over RCCL: a rank that fails before it has queued its share of a collective leaves the others waiting
-// inside theirs for good.  The failing rank publishes the stop and aborts ITS communicator (stop_everybody); every other
-// rank aborts its own as soon as one of its bounded waits sees the stop (RCCL then ends the kernels that wait for the
-// missing rank), and no rank submits a collective once comms_aborted is set.  The handle is dead afterwards --
-// s2d_multi_destroy and a new s2d_multi_create bring it back.
-int rank_step(s2d_multi* m, int rank)
+// Test hook (s2d_test_multi_stall): the chosen rank's thread stops answering before its exchange of the chosen iteration.
+void stall_if_asked(s2d_multi* m, const Rank& R, int iteration)
 {
-    s2d_ctx* c = m->ctx[(size_t)rank];
+    if (R.index != m->stall_rank || iteration != m->stall_iter) return;
+    const auto t0 = std::chrono::steady_clock::now();
+    while (!m->barrier.broken && (m->stall_for_ms < 0 || std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(m->stall_for_ms)))
+        std::this_thread::sleep_for(std::chrono::milliseconds(1));
+}
+
+// One rank's share of s2d_multi_step: `iters` frames of main.cpp:334 on its rows.  A rank that fails before it has
+// queued its share of a collective would leave the others waiting inside theirs for good: it stops everybody.
+int rank_step(s2d_multi* m, Rank& R)
+{
+    s2d_ctx* c = R.ctx;
     const uint32_t bwd_flags = (m->step_flags & S2D_STEP_OPTIMIZE_OPACITY) ? 0u : S2D_BWD_SKIP_OPACITY_GRAD; // main.cpp:735
-    float* grads = (float*)s2d_grads_device_ptr(c);
-    hipStream_t stream = (hipStream_t)s2d_stream(c);
-    const size_t count = (size_t)m->n * 9;
     int rc = S2D_OK;
     int marks = 0; // progress marks recorded so far in this call
     for (int k = 0; k < m->step_iters && rc == S2D_OK && !m->barrier.broken; k++) {
         const bool last = k + 1 == m->step_iters;
         const int it = m->step_first_iter + k;
-        at_phase(m, rank, PH_RASTER, it);
+        at_phase(R, PH_RASTER, it);
         rc = s2d_forward_backward(c, bwd_flags | (last ? 0u : S2D_FB_SKIP_IMAGE));
         if (rc != S2D_OK) break;
-        if (rank == m->stall_rank && it == m->stall_iter) { // test hook: this rank's thread stops answering here
-            const auto t0 = std::chrono::steady_clock::now();
-            while (!m->barrier.broken && (m->stall_for_ms < 0 || std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(m->stall_for_ms)))
-                std::this_thread::sleep_for(std::chrono::milliseconds(1));
-        }
+        stall_if_asked(m, R, it);
         // the only exchange of the iteration
         if (m->scheme == SCHEME_OWNERSHIP) {
-            at_phase(m, rank, PH_EXCHANGE, it);
-            rc = exchange_grads(m, rank);
-        } else if (m->scheme == SCHEME_REPLICATED) { // (a handle on one device goes through RCCL too: same code whatever N)
-            at_phase(m, rank, PH_ALLREDUCE, it);
-            if (m->share_gpu) {
-                if (m->world > 1) rc = staged_all_reduce(m, rank, grads, count, stream);
-            } else {
-                // this rank's own slot: nobody frees what it holds while comms_aborted is clear, and once it is set no
-                // collective is started any more
-                const ncclComm_t comm = m->comms_aborted.load() ? nullptr : m->comms[(size_t)rank].load();
-                if (m->comms_aborted.load()) { // a stop was published (the barrier breaks a moment later): not this rank's failure
-                    abort_own_collective(m, rank);
-                    rc = kStopped;
-                } else if (!comm) {
-                    rc = rank_fail(m, rank, S2D_E_STATE, "no communicator");
-                } else if (m->rccl.AllReduce(grads, grads, count, ncclFloat, ncclSum, comm, stream) != ncclSuccess)
-                    rc = rank_fail(m, rank, S2D_E_HIP, "ncclAllReduce failed");
-            }
+            at_phase(R, PH_EXCHANGE, it);
+            rc = exchange_grads(m, R);
+        } else if (m->scheme == SCHEME_REPLICATED) {
+            at_phase(R, PH_ALLREDUCE, it);
+            rc = all_reduce_grads(m, R);
         }
         if (rc == S2D_OK) {
-            at_phase(m, rank, PH_ADAM, it);
+            at_phase(R, PH_ADAM, it);
             rc = s2d_adam_step(c, m->step_flags);
         }
         if (rc == S2D_OK && m->scheme == SCHEME_OWNERSHIP && (m->hold_age + k + 1) % m->interval == 0) {
-            at_phase(m, rank, PH_REFRESH, it);
-            rc = refresh(m, rank);
-        } else if (rc == S2D_OK && m->scheme != SCHEME_OWNERSHIP && (k + 1) % 64 == 0 && !last && prog_event(m, rank, 0)) {
+            at_phase(R, PH_REFRESH, it);
+            rc = refresh(m, R);
+        } else if (rc == S2D_OK && m->scheme != SCHEME_OWNERSHIP && (k + 1) % 64 == 0 && !last) {
             // no refresh paces these schemes: mark every 64th iteration on the stream and wait for the mark BEFORE the one
             // just recorded, so the host never runs more than 128 iterations ahead of the device, the device never waits
             // for the host, and a device that stopped is noticed within the stall limit
-            MHIP(m, rank, hipEventRecord(prog_event(m, rank, marks & 1), stream));
+            MHIP(R, hipEventRecord(R.ev_prog[marks & 1], R.stream()));
             marks++;
             if (marks >= 2) {
-                at_phase(m, rank, PH_DRAIN, it);
-                rc = wait_event(m, rank, prog_event(m, rank, marks & 1), "running a batch of 64 iterations");
+                at_phase(R, PH_DRAIN, it);
+                rc = wait_event(m, R, R.ev_prog[marks & 1], "running a batch of 64 iterations");
             }
         }
     }
-    std::vector<double>& mine = m->sqerr[(size_t)rank];
-    mine.assign((size_t)m->step_iters, 0.0);
+    R.sqerr.assign((size_t)m->step_iters, 0.0);
     // A rank that failed on the way (not the finite guard below, which every replica sees alike and which leaves every
     // collective queued): the others may already sit in an all-reduce that will never get this rank's share
-    if (rc != S2D_OK && rc != kStopped) stop_everybody(m, rank);
+    if (rc != S2D_OK && rc != kStopped) stop_everybody(m, R);
     if (rc == S2D_OK) {
-        at_phase(m, rank, PH_DRAIN, m->step_first_iter + m->step_iters);
-        rc = drain_now(m, rank, "finishing the iterations of this call");
+        at_phase(R, PH_DRAIN, m->step_first_iter + m->step_iters);
+        rc = drain_now(m, R, "finishing the iterations of this call");
     }
-    if (rc == S2D_OK && m->step_iters > 0) rc = s2d_get_sqerr_trace(c, m->step_first_iter, m->step_iters, mine.data());
+    if (rc == S2D_OK && m->step_iters > 0) rc = s2d_get_sqerr_trace(c, m->step_first_iter, m->step_iters, R.sqerr.data());
     if (rc == S2D_OK) rc = s2d_synchronize(c); // the finite guard, main.cpp:752-785
     if (rc != S2D_OK) m->barrier.abort();      // the other ranks stop at their next wait instead of sitting in it
     return rc;
 }
 
-void worker_main(s2d_multi* m, int rank)
+void worker_main(s2d_multi* m, Rank* rank)
 {
+    Rank& R = *rank;
     int seen = 0;
     for (;;) {
         int cmd;
@@ -838,28 +880,27 @@ void worker_main(s2d_multi* m, int rank)
             cmd = m->cmd;
         }
         if (cmd == CMD_QUIT) {
-            (void)hipSetDevice(m->devices[(size_t)rank]);
-            m->halo[(size_t)rank] = HaloRank(); // its device buffers and events go here, on their device, not with the handle
+            R.let_go(); // here, on its device, not with the handle
             return;
         }
         int rc = S2D_OK;
-        if (cmd == CMD_STEP) rc = rank_step(m, rank);
+        if (cmd == CMD_STEP) rc = rank_step(m, R);
         if (cmd == CMD_HOLD) {
-            at_phase(m, rank, PH_HOLD, 0);
-            rc = hold_fresh(m, rank);
+            at_phase(R, PH_HOLD, 0);
+            rc = hold_fresh(m, R);
             if (rc != S2D_OK) m->barrier.abort();
         }
         if (cmd == CMD_FORWARD) { // the rank's rows of image0 from the current parameters (it holds every splat that reaches them)
-            at_phase(m, rank, PH_FORWARD, 0);
-            rc = s2d_forward(m->ctx[(size_t)rank]);
-            if (rc == S2D_OK) rc = drain_now(m, rank, "rendering its rows");
-            if (rc == S2D_OK) rc = s2d_synchronize(m->ctx[(size_t)rank]);
+            at_phase(R, PH_FORWARD, 0);
+            rc = s2d_forward(R.ctx);
+            if (rc == S2D_OK) rc = drain_now(m, R, "rendering its rows");
+            if (rc == S2D_OK) rc = s2d_synchronize(R.ctx);
         }
-        at_phase(m, rank, PH_DONE, 0);
+        at_phase(R, PH_DONE, 0);
         {
             std::lock_guard<std::mutex> lk(m->m);
-            m->rank_rc[(size_t)rank] = rc;
-            m->rank_done[(size_t)rank] = 1;
+            R.rc = rc;
+            R.done = true;
             m->done_count++;
         }
         m->cv_done.notify_one();
@@ -870,11 +911,10 @@ void worker_main(s2d_multi* m, int rank)
 // wait_event, the barrier), but a rank can also sit inside a runtime call this file cannot bound (a synchronous copy in
 // a context's list rebuild behind a kernel that never ends, a collective's submission).  When NO rank has changed phase
 // for twice the stall limit the caller stops everybody, gives the ranks one more limit to come back, and otherwise
-// returns without them: the handle is then `stuck` -- its abandoned threads and contexts are never freed (a thread
-// inside a runtime call cannot be cancelled) -- and every later call is refused.
+// returns without them: the handle is then Abandoned -- its threads and contexts are never freed (a thread inside a
+// runtime call cannot be cancelled) -- and every later call is refused.
 void run_command(s2d_multi* m, int cmd)
 {
-    for (std::string& s : m->rank_msg) s.clear();
     m->late = 0;
     m->comms_aborted.store(false); // (a dead handle never gets here)
     m->barrier.reset();
@@ -884,7 +924,10 @@ void run_command(s2d_multi* m, int cmd)
         m->cmd = cmd;
         m->cmd_seq++;
         m->done_count = 0;
-        std::fill(m->rank_done.begin(), m->rank_done.end(), 0);
+        for (Rank& R : m->ranks) {
+            R.msg.clear();
+            R.done = false;
+        }
     }
     m->cv_cmd.notify_all();
     std::unique_lock<std::mutex> lk(m->m);
@@ -900,7 +943,7 @@ void run_command(s2d_multi* m, int cmd)
         }
         if (m->cv_done.wait_for(lk, std::chrono::milliseconds(std::max(10, std::min(250, limit / 4))), all_done)) return;
         uint64_t ticks = (uint64_t)m->done_count;
-        for (int r = 0; r < m->world; r++) ticks += m->progress[(size_t)r].ticks.load(std::memory_order_acquire);
+        for (const Rank& R : m->ranks) ticks += R.progress.ticks.load(std::memory_order_acquire);
         const auto now = std::chrono::steady_clock::now();
         if (ticks != seen) {
             seen = ticks;
@@ -914,28 +957,20 @@ void run_command(s2d_multi* m, int cmd)
             m->timed_out.store(true);
             m->comms_aborted.store(true);
             m->barrier.abort();
-            // last resort for a rank that sits inside a collective's submission or behind its kernel and cannot look up:
-            // take its communicator out of its slot and abort it from here
-            if (m->scheme == SCHEME_REPLICATED && !m->share_gpu)
-                for (int r = 0; r < m->n_comms; r++)
-                    if (!m->rank_done[(size_t)r]) {
-                        const ncclComm_t c = m->comms[(size_t)r].exchange(nullptr);
-                        if (c) m->collective_lost.store(true);
-                        if (c && m->rccl.CommAbort) (void)m->rccl.CommAbort(c);
-                    }
+            // last resort for a rank that sits inside a collective's submission or behind its kernel and cannot look up
+            for (Rank& R : m->ranks)
+                if (!R.done) abort_collective(m, R);
         } else if (stopping && quiet > (long long)limit + 1000) {
             std::string who;
-            for (int r = 0; r < m->world; r++)
-                if (!m->rank_done[(size_t)r]) {
-                    const Progress& P = m->progress[(size_t)r];
+            for (Rank& R : m->ranks)
+                if (!R.done) {
                     char one[128];
-                    snprintf(one, sizeof(one), "%srank %d (device %d) at '%s', iteration %d", who.empty() ? "" : "; ", r, m->devices[(size_t)r],
-                             phase_name(P.phase.load()), P.iteration.load());
+                    snprintf(one, sizeof(one), "%srank %d (device %d) at '%s', iteration %d", who.empty() ? "" : "; ", R.index, R.device,
+                             phase_name(R.progress.phase.load()), R.progress.iteration.load());
                     who += one;
-                    m->rank_rc[(size_t)r] = S2D_E_STATE; // (under m->m, like the workers' own writes; their message strings are theirs)
+                    R.rc = S2D_E_STATE; // (under m->m, like the workers' own writes; their message strings are theirs)
                 }
-            m->stuck = true;
-            m->dead = true;
+            worsen(m, Health::Abandoned);
             snprintf(m->err, sizeof(m->err), "no rank made progress for %d ms and the stop was not answered: %s; the handle is abandoned "
                                              "(its threads and device memory are not freed)", 3 * limit + 2000, who.c_str());
             return;
@@ -945,15 +980,12 @@ void run_command(s2d_multi* m, int cmd)
 
 int first_failure(s2d_multi* m, const char* what)
 {
-    if (m->stuck) return S2D_E_STATE; // run_command wrote the report
-    for (int r = 0; r < m->world; r++) {
-        const int rc = m->rank_rc[(size_t)r];
-        if (rc != S2D_OK && rc != kStopped)
-            return mfail(m, rc, "%s on rank %d (device %d): %s", what, r, m->devices[(size_t)r],
-                         m->rank_msg[(size_t)r].empty() ? s2d_last_error(m->ctx[(size_t)r]) : m->rank_msg[(size_t)r].c_str());
-    }
-    for (int r = 0; r < m->world; r++)
-        if (m->rank_rc[(size_t)r] != S2D_OK) return mfail(m, S2D_E_STATE, "%s: rank %d stopped without a failing rank", what, r);
+    if (m->health == Health::Abandoned) return S2D_E_STATE; // run_command wrote the report
+    for (const Rank& R : m->ranks)
+        if (R.rc != S2D_OK && R.rc != kStopped)
+            return mfail(m, R.rc, "%s on rank %d (device %d): %s", what, R.index, R.device, R.msg.empty() ? s2d_last_error(R.ctx) : R.msg.c_str());
+    for (const Rank& R : m->ranks)
+        if (R.rc != S2D_OK) return mfail(m, S2D_E_STATE, "%s: rank %d stopped without a failing rank", what, R.index);
     return S2D_OK;
 }
 
@@ -976,27 +1008,25 @@ struct DeviceGuard {
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
-int refuse_dead(s2d_multi* m)
-{
-    if (m->stuck) return S2D_E_STATE; // keeps the watchdog's report
-    return mfail(m, S2D_E_STATE, "%s; s2d_multi_destroy this handle and create a new one",
-                 m->collective_lost.load() ? "a collective of this handle was aborted after a rank failed: its communicators are gone"
-                                           : "a rank of this handle stopped answering and the ranks no longer agree on where the run stands");
-}
-
-inline bool lowest_holder(uint32_t mask, int r) { return mask != 0u && (mask & (0u - mask)) == (1u << r); }
-
 // Slab ownership: the complete parameter or Adam array, every row from its lowest-ranked holder.
 template <typename Row, typename Get>
 int assemble(s2d_multi* m, Row* out, Get get)
 {
     std::vector<Row> tmp((size_t)m->n);
-    for (int r = 0; r < m->world; r++) {
-        if (int rc = get(m->ctx[(size_t)r], tmp.data())) return mfail(m, rc, "reading rank %d: %s", r, s2d_last_error(m->ctx[(size_t)r]));
-        const HaloRank& H = m->halo[(size_t)r];
-        for (const int32_t i : H.held)
-            if (lowest_holder(H.mask[(size_t)i], r)) out[(size_t)i] = tmp[(size_t)i];
+    for (const Rank& R : m->ranks) {
+        if (int rc = get(R.ctx, tmp.data())) return mfail(m, rc, "reading rank %d: %s", R.index, s2d_last_error(R.ctx));
+        for (const int32_t i : R.halo.held)
+            if (lowest_holder(R.halo.mask[(size_t)i], R.index)) out[(size_t)i] = tmp[(size_t)i];
     }
+    return S2D_OK;
+}
+
+// `call` on every replica in turn, from the caller's thread (the workers are idle between commands).
+template <typename Call>
+int each_ctx(s2d_multi* m, const char* what, Call call)
+{
+    for (const Rank& R : m->ranks)
+        if (int rc = call(R.ctx)) return mfail(m, rc, "%s on rank %d (device %d): %s", what, R.index, R.device, s2d_last_error(R.ctx));
     return S2D_OK;
 }
 
@@ -1017,39 +1047,31 @@ int s2d_multi_create(const s2d_config* cfg, const int32_t* devices, int32_t n_de
     m->W = cfg->width;
     m->H = cfg->height;
     m->n = cfg->n_splats;
+    m->mse_norm = (double)((long long)m->H * m->W * 3);
     m->share_gpu = (flags & S2D_MULTI_SHARE_GPU) != 0;
     m->scheme = (flags & S2D_MULTI_REPLICATED) ? SCHEME_REPLICATED : (n_devices > 1 ? SCHEME_OWNERSHIP : SCHEME_NONE);
-    m->devices.assign(devices, devices + n_devices);
-    if (m->share_gpu)
-        for (int& d : m->devices) d = devices[0];
-    if ((m->H + 15) / 16 < m->world) return mfail(m, S2D_E_INVALID, "%d devices for %d tile rows", m->world, (m->H + 15) / 16);
-    m->ctx.assign((size_t)m->world, nullptr);
-    m->row_begin.resize((size_t)m->world);
-    m->row_end.resize((size_t)m->world);
-    m->rank_rc.assign((size_t)m->world, S2D_OK);
-    m->rank_msg.resize((size_t)m->world);
-    m->sqerr.resize((size_t)m->world);
-    m->halo.resize((size_t)m->world);
+    m->ranks = std::vector<Rank>((size_t)m->world);
+    m->bounds.assign((size_t)m->world + 1, m->H);
     m->barrier.n = m->world;
-    m->sent_seq.reset(new std::atomic<unsigned>[(size_t)m->world]);
-    for (int r = 0; r < m->world; r++) m->sent_seq[(size_t)r].store(0u);
-    m->progress.reset(new Progress[(size_t)m->world]);
-    m->rank_done.assign((size_t)m->world, 0);
     if (const char* e = getenv("S2D_MULTI_STALL_TIMEOUT_MS")) m->stall_ms = std::max(0, atoi(e));
-    m->bounds.resize((size_t)m->world + 1);
+    if ((m->H + 15) / 16 < m->world) return mfail(m, S2D_E_INVALID, "%d devices for %d tile rows", m->world, (m->H + 15) / 16);
     for (int r = 0; r < m->world; r++) {
+        Rank& R = m->ranks[(size_t)r];
+        R.index = r;
+        R.device = devices[m->share_gpu ? 0 : r];
         s2d_config c = *cfg;
-        c.device = m->devices[(size_t)r];
+        c.device = R.device;
         slab_rows(m->H, r, m->world, &c.row_begin, &c.row_end);
-        m->row_begin[(size_t)r] = c.row_begin;
-        m->row_end[(size_t)r] = c.row_end;
-        m->bounds[(size_t)r] = c.row_begin;
-        const int rc = s2d_create(&c, &m->ctx[(size_t)r]);
+        m->bounds[(size_t)r] = R.row_begin = c.row_begin;
+        R.row_end = c.row_end;
+        const int rc = s2d_create(&c, &R.ctx);
         if (rc != S2D_OK)
             return mfail(m, rc, "s2d_create for device %d, rows %d..%d: %s", c.device, c.row_begin, c.row_end,
-                         m->ctx[(size_t)r] ? s2d_last_error(m->ctx[(size_t)r]) : "rejected configuration");
+                         R.ctx ? s2d_last_error(R.ctx) : "rejected configuration");
+        if (hipSetDevice(R.device) != hipSuccess) return mfail(m, S2D_E_HIP, "hipSetDevice(%d)", R.device);
+        for (Event& e : R.ev_prog)
+            if (e.create(hipEventDisableTiming) != hipSuccess) return mfail(m, S2D_E_HIP, "hipEventCreate on device %d", R.device);
     }
-    m->bounds[(size_t)m->world] = m->H;
     // Adam moves a parameter by at most lr * |m^| / sqrt(v^) <= 2.35 * lr per step for beta = (0.9, 0.99); pos.y moves by
     // that and reach = 3 * max(sx, sy) + 2 by three times that: the margin must outlast one refresh interval
     const float lr = cfg->training_rate > 0.0f ? cfg->training_rate : 0.05f;
@@ -1057,48 +1079,37 @@ int s2d_multi_create(const s2d_config* cfg, const int32_t* devices, int32_t n_de
     if (m->scheme == SCHEME_REPLICATED && !m->share_gpu) {
         std::string why;
         if (!load_rccl(&m->rccl, &why)) return mfail(m, S2D_E_HIP, "%s", why.c_str());
+        std::vector<int> devs;
+        for (const Rank& R : m->ranks) devs.push_back(R.device);
         std::vector<ncclComm_t> made((size_t)m->world, nullptr);
-        const ncclResult_t nrc = m->rccl.CommInitAll(made.data(), m->world, m->devices.data());
-        if (nrc == ncclSuccess) {
-            m->comms.reset(new std::atomic<ncclComm_t>[(size_t)m->world]);
-            for (int r = 0; r < m->world; r++) m->comms[(size_t)r].store(made[(size_t)r]);
-            m->n_comms = m->world;
-        } else {
+        const ncclResult_t nrc = m->rccl.CommInitAll(made.data(), m->world, devs.data());
+        if (nrc != ncclSuccess)
             return mfail(m, S2D_E_HIP, "ncclCommInitAll over %d devices: %s (RCCL takes one rank per GPU; S2D_MULTI_SHARE_GPU rehearses "
                                        "on fewer)", m->world, m->rccl.GetErrorString(nrc));
-        }
+        for (Rank& R : m->ranks) R.comm.store(made[(size_t)R.index]);
     } else if (m->scheme == SCHEME_REPLICATED && m->world > 1) {
-        m->host_grads.assign((size_t)m->world, nullptr);
-        if (hipSetDevice(m->devices[0]) != hipSuccess) return mfail(m, S2D_E_HIP, "hipSetDevice(%d)", m->devices[0]);
-        for (int r = 0; r < m->world; r++)
-            if (hipHostMalloc((void**)&m->host_grads[(size_t)r], (size_t)m->n * 9 * sizeof(float) + 16, hipHostMallocDefault) != hipSuccess)
+        if (hipSetDevice(m->ranks[0].device) != hipSuccess) return mfail(m, S2D_E_HIP, "hipSetDevice(%d)", m->ranks[0].device);
+        for (Rank& R : m->ranks)
+            if (R.staging.alloc((size_t)m->n * 9 + 4, hipHostMallocDefault) != hipSuccess)
                 return mfail(m, S2D_E_NOMEM, "host staging buffers for %d ranks", m->world);
     } else if (m->scheme == SCHEME_OWNERSHIP) {
         // one rank per GPU, and direct peer-to-peer copies where the fabric allows them (the copies work without, staged)
-        for (int a = 0; a < m->world; a++)
-            for (int b = 0; b < m->world; b++) {
-                const int da = m->devices[(size_t)a], db = m->devices[(size_t)b];
-                if (a == b || da == db) {
-                    if (a != b && !m->share_gpu) return mfail(m, S2D_E_INVALID, "device %d listed twice (S2D_MULTI_SHARE_GPU rehearses several ranks on one GPU)", da);
+        for (const Rank& A : m->ranks)
+            for (const Rank& B : m->ranks) {
+                if (&A == &B) continue;
+                if (A.device == B.device) {
+                    if (!m->share_gpu) return mfail(m, S2D_E_INVALID, "device %d listed twice (S2D_MULTI_SHARE_GPU rehearses several ranks on one GPU)", A.device);
                     continue;
                 }
                 int can = 0;
-                if (hipSetDevice(da) != hipSuccess) return mfail(m, S2D_E_HIP, "hipSetDevice(%d)", da);
-                if (hipDeviceCanAccessPeer(&can, da, db) == hipSuccess && can) {
-                    const hipError_t e = hipDeviceEnablePeerAccess(db, 0);
+                if (hipSetDevice(A.device) != hipSuccess) return mfail(m, S2D_E_HIP, "hipSetDevice(%d)", A.device);
+                if (hipDeviceCanAccessPeer(&can, A.device, B.device) == hipSuccess && can) {
+                    const hipError_t e = hipDeviceEnablePeerAccess(B.device, 0);
                     if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError(); // copies are staged then
                 }
             }
     }
-    // the events of the bounded stream waits (three per rank, prog_event())
-    m->ev_prog.assign((size_t)m->world * 3, nullptr);
-    for (int r = 0; r < m->world; r++) {
-        if (hipSetDevice(m->devices[(size_t)r]) != hipSuccess) return mfail(m, S2D_E_HIP, "hipSetDevice(%d)", m->devices[(size_t)r]);
-        for (int k = 0; k < 3; k++)
-            if (hipEventCreateWithFlags(&m->ev_prog[(size_t)r * 3 + (size_t)k], hipEventDisableTiming) != hipSuccess)
-                return mfail(m, S2D_E_HIP, "hipEventCreate on device %d", m->devices[(size_t)r]);
-    }
-    for (int r = 0; r < m->world; r++) m->workers.emplace_back(worker_main, m, r);
+    for (Rank& R : m->ranks) m->workers.emplace_back(worker_main, m, &R);
     return S2D_OK;
 }
 
@@ -1106,7 +1117,7 @@ void s2d_multi_destroy(s2d_multi* m)
 {
     if (!m) return;
     DeviceGuard guard;
-    if (m->stuck) {
+    if (m->health == Health::Abandoned) {
         // some worker sits inside a runtime call that never returned: it cannot be joined, and what it may still touch
         // -- the handle, its context, its device memory -- cannot be freed under it.  Abandon all of it.
         for (auto& t : m->workers) t.detach();
@@ -1118,17 +1129,15 @@ void s2d_multi_destroy(s2d_multi* m)
             m->cmd = CMD_QUIT;
             m->cmd_seq++;
         }
-        m->cv_cmd.notify_all();
+        m->cv_cmd.notify_all(); // every worker lets its rank's resources go (Rank::let_go)
         for (auto& t : m->workers) t.join();
     }
-    for (int r = 0; r < m->n_comms; r++)
-        if (const ncclComm_t c = m->comms[(size_t)r].exchange(nullptr)) m->rccl.CommDestroy(c);
-    for (size_t k = 0; k < m->ev_prog.size(); k++)
-        if (m->ev_prog[k] && hipSetDevice(m->devices[k / 3]) == hipSuccess) (void)hipEventDestroy(m->ev_prog[k]);
-    for (float* p : m->host_grads)
-        if (p) (void)hipHostFree(p);
-    for (s2d_ctx* c : m->ctx)
-        if (c) s2d_destroy(c);
+    for (Rank& R : m->ranks) {
+        if (m->workers.empty()) R.let_go(); // creation failed before any worker was started
+        if (const ncclComm_t c = R.comm.exchange(nullptr)) m->rccl.CommDestroy(c);
+    }
+    for (Rank& R : m->ranks)
+        if (R.ctx) s2d_destroy(R.ctx);
     delete m;
 }
 
@@ -1147,13 +1156,13 @@ int s2d_multi_device_info(s2d_multi* m, int32_t rank, int32_t* device, int32_t* 
                           int32_t pci_capacity, char* name, int32_t name_capacity)
 {
     if (!m || rank < 0 || rank >= m->world) return S2D_E_INVALID;
-    const int dev = m->devices[(size_t)rank];
-    if (device) *device = dev;
-    if (row_begin) *row_begin = m->row_begin[(size_t)rank];
-    if (row_end) *row_end = m->row_end[(size_t)rank];
+    const Rank& R = m->ranks[(size_t)rank];
+    if (device) *device = R.device;
+    if (row_begin) *row_begin = R.row_begin;
+    if (row_end) *row_end = R.row_end;
     if (pci_bus_id && pci_capacity > 0) {
         pci_bus_id[0] = 0;
-        if (hipDeviceGetPCIBusId(pci_bus_id, pci_capacity, dev) != hipSuccess) {
+        if (hipDeviceGetPCIBusId(pci_bus_id, pci_capacity, R.device) != hipSuccess) {
             (void)hipGetLastError();
             pci_bus_id[0] = 0;
         }
@@ -1161,7 +1170,7 @@ int s2d_multi_device_info(s2d_multi* m, int32_t rank, int32_t* device, int32_t* 
     if (name && name_capacity > 0) {
         hipDeviceProp_t prop;
         name[0] = 0;
-        if (hipGetDeviceProperties(&prop, dev) == hipSuccess) snprintf(name, (size_t)name_capacity, "%s", prop.name);
+        if (hipGetDeviceProperties(&prop, R.device) == hipSuccess) snprintf(name, (size_t)name_capacity, "%s", prop.name);
         else (void)hipGetLastError();
     }
     return S2D_OK;
@@ -1182,50 +1191,37 @@ int s2d_multi_exchange_info(s2d_multi* m, int64_t* out4)
     out4[0] = m->scheme;
     out4[1] = out4[2] = out4[3] = 0;
     if (m->scheme == SCHEME_OWNERSHIP && m->hold_valid)
-        for (const HaloRank& H : m->halo) {
-            out4[1] += H.total;
-            out4[2] += H.handed;
-            out4[3] += (int64_t)H.held.size();
+        for (const Rank& R : m->ranks) {
+            out4[1] += R.halo.total;
+            out4[2] += R.halo.handed;
+            out4[3] += (int64_t)R.halo.held.size();
         }
     else
         out4[3] = (int64_t)m->n * m->world;
     return S2D_OK;
 }
 
-// The calls below address every replica in turn from the caller's thread (the workers are idle between commands).
-#define S2D_EACH(m, what, call)                                                                                      \
-    do {                                                                                                             \
-        for (int r_ = 0; r_ < (m)->world; r_++) {                                                                    \
-            s2d_ctx* c = (m)->ctx[(size_t)r_];                                                                       \
-            const int rc_ = (call);                                                                                  \
-            if (rc_ != S2D_OK)                                                                                       \
-                return mfail((m), rc_, "%s on rank %d (device %d): %s", what, r_, (m)->devices[(size_t)r_], s2d_last_error(c)); \
-        }                                                                                                            \
-    } while (0)
-
 int s2d_multi_set_target(s2d_multi* m, const float* rgba32f)
 {
     if (!m || !rgba32f) return S2D_E_INVALID;
     DeviceGuard guard;
-    S2D_EACH(m, "s2d_set_target", s2d_set_target(c, rgba32f));
-    return S2D_OK;
+    return each_ctx(m, "s2d_set_target", [&](s2d_ctx* c) { return s2d_set_target(c, rgba32f); });
 }
 
 int s2d_multi_set_target_synthetic(s2d_multi* m)
 {
     if (!m) return S2D_E_INVALID;
     DeviceGuard guard;
-    S2D_EACH(m, "s2d_set_target_synthetic", s2d_set_target_synthetic(c));
-    return S2D_OK;
+    return each_ctx(m, "s2d_set_target_synthetic", s2d_set_target_synthetic);
 }
 
 int s2d_multi_init_splats(s2d_multi* m)
 {
     if (!m) return S2D_E_INVALID;
     DeviceGuard guard;
-    S2D_EACH(m, "s2d_init_splats", s2d_init_splats(c)); // every replica: the same deterministic init(), main.cpp:280-305
+    if (int rc = each_ctx(m, "s2d_init_splats", s2d_init_splats)) return rc; // every replica: the same deterministic init(), main.cpp:280-305
     m->iterations = 0;
-    m->failed_step = false;
+    state_set_afresh(m);
     m->hold_valid = false; // every replica is complete again: new hold sets at the next step
     return S2D_OK;
 }
@@ -1234,11 +1230,12 @@ int s2d_multi_get_adam(s2d_multi* m, s2d_splat_adam* adams, float* beta1t, float
 {
     if (!m) return S2D_E_INVALID;
     DeviceGuard guard;
+    s2d_ctx* first = m->ranks[0].ctx;
     if (m->scheme == SCHEME_OWNERSHIP && m->hold_valid && adams) {
         if (int rc = assemble(m, adams, [](s2d_ctx* c, s2d_splat_adam* p) { return s2d_get_adam(c, p, nullptr, nullptr, nullptr); })) return rc;
         adams = nullptr;
     }
-    if (int rc = s2d_get_adam(m->ctx[0], adams, beta1t, beta2t, iterations)) return mfail(m, rc, "s2d_get_adam: %s", s2d_last_error(m->ctx[0]));
+    if (int rc = s2d_get_adam(first, adams, beta1t, beta2t, iterations)) return mfail(m, rc, "s2d_get_adam: %s", s2d_last_error(first));
     return S2D_OK;
 }
 
@@ -1253,9 +1250,9 @@ int s2d_multi_set_splats(s2d_multi* m, const s2d_splat* splats)
         float b1 = 0.f, b2 = 0.f;
         int32_t it = 0;
         if (int rc = s2d_multi_get_adam(m, full.data(), &b1, &b2, &it)) return rc;
-        S2D_EACH(m, "s2d_set_adam", s2d_set_adam(c, full.data(), b1, b2, it));
+        if (int rc = each_ctx(m, "s2d_set_adam", [&](s2d_ctx* c) { return s2d_set_adam(c, full.data(), b1, b2, it); })) return rc;
     }
-    S2D_EACH(m, "s2d_set_splats", s2d_set_splats(c, splats));
+    if (int rc = each_ctx(m, "s2d_set_splats", [&](s2d_ctx* c) { return s2d_set_splats(c, splats); })) return rc;
     m->hold_valid = false;
     return S2D_OK;
 }
@@ -1266,7 +1263,8 @@ int s2d_multi_get_splats(s2d_multi* m, s2d_splat* splats)
     DeviceGuard guard;
     if (m->scheme == SCHEME_OWNERSHIP && m->hold_valid)
         return assemble(m, splats, [](s2d_ctx* c, s2d_splat* p) { return s2d_get_splats(c, p); });
-    if (int rc = s2d_get_splats(m->ctx[0], splats)) return mfail(m, rc, "s2d_get_splats: %s", s2d_last_error(m->ctx[0]));
+    s2d_ctx* first = m->ranks[0].ctx;
+    if (int rc = s2d_get_splats(first, splats)) return mfail(m, rc, "s2d_get_splats: %s", s2d_last_error(first));
     return S2D_OK; // the replicas are bit-identical: any one of them
 }
 
@@ -1274,19 +1272,17 @@ int s2d_multi_set_adam(s2d_multi* m, const s2d_splat_adam* adams, float beta1t, 
 {
     if (!m || (!adams && m->n) || iterations < 0) return S2D_E_INVALID;
     DeviceGuard guard;
-    S2D_EACH(m, "s2d_set_adam", s2d_set_adam(c, adams, beta1t, beta2t, iterations)); // complete on every rank; hold sets unaffected
+    // complete on every rank; hold sets unaffected
+    if (int rc = each_ctx(m, "s2d_set_adam", [&](s2d_ctx* c) { return s2d_set_adam(c, adams, beta1t, beta2t, iterations); })) return rc;
     m->iterations = iterations;
-    m->failed_step = false; // every rank's counters are alike again (the caller sets the splats as well: include/splat2d.h)
+    state_set_afresh(m); // every rank's counters are alike again (the caller sets the splats as well: include/splat2d.h)
     return S2D_OK;
 }
 
 int s2d_multi_step(s2d_multi* m, int32_t iters, uint32_t flags, double* mse_out)
 {
     if (!m || iters < 0 || iters > (1 << 16)) return S2D_E_INVALID;
-    if (m->dead) return refuse_dead(m);
-    if (m->failed_step)
-        return mfail(m, S2D_E_STATE, "the last s2d_multi_step failed and left the ranks at different iterations: s2d_multi_init_splats, or "
-                                     "s2d_multi_set_splats + s2d_multi_set_adam, first");
+    if (int rc = refuse(m, Health::Usable)) return rc;
     DeviceGuard guard;
     if (int rc = ensure_hold(m)) return rc;
     m->step_iters = iters;
@@ -1299,32 +1295,29 @@ int s2d_multi_step(s2d_multi* m, int32_t iters, uint32_t flags, double* mse_out)
         // The earliest count is the iteration at which the reference abort()ed; the state is for inspection only, and
         // s2d_multi_set_adam (which sets every rank's counters alike) comes before any further step.
         int32_t earliest = INT32_MAX;
-        for (s2d_ctx* c : m->ctx) {
+        for (const Rank& R : m->ranks) {
             int32_t it = 0;
-            if (s2d_get_adam(c, nullptr, nullptr, nullptr, &it) == S2D_OK) earliest = std::min(earliest, it);
+            if (s2d_get_adam(R.ctx, nullptr, nullptr, nullptr, &it) == S2D_OK) earliest = std::min(earliest, it);
         }
         if (earliest != INT32_MAX) m->iterations = earliest;
-        if (m->collective_lost.load() || m->timed_out.load()) m->dead = true;
-        m->failed_step = true;
+        worsen(m, m->collective_lost.load() || m->timed_out.load() ? Health::Dead : Health::NeedsState);
         return rc;
     }
     m->iterations += iters;
     m->hold_age += iters;
-    if (mse_out) {
-        const double norm = (double)((long long)m->H * m->W * 3);
+    if (mse_out)
         for (int k = 0; k < iters; k++) {
             double sum = 0.0;
-            for (int r = 0; r < m->world; r++) sum += m->sqerr[(size_t)r][(size_t)k]; // slab order: a fixed order
-            mse_out[k] = sum / norm; // main.cpp:805
+            for (const Rank& R : m->ranks) sum += R.sqerr[(size_t)k]; // slab order: a fixed order
+            mse_out[k] = sum / m->mse_norm; // main.cpp:805
         }
-    }
     return S2D_OK;
 }
 
 int s2d_multi_forward(s2d_multi* m)
 {
     if (!m) return S2D_E_INVALID;
-    if (m->dead) return refuse_dead(m);
+    if (int rc = refuse(m, Health::NeedsState)) return rc;
     DeviceGuard guard;
     // slab ownership: after set_splats / init_splats the hold sets (and with them each context's list of the splats it
     // projects and rasterises) are stale until they are made afresh -- a splat that now reaches a rank's rows but was not
@@ -1340,9 +1333,9 @@ int s2d_multi_get_image(s2d_multi* m, float* rgba32f)
     DeviceGuard guard;
     // every context holds (and returns) its own rows; together they tile the image
     const size_t row = (size_t)m->W * 4;
-    for (int r = 0; r < m->world; r++)
-        if (int rc = s2d_get_image_rows(m->ctx[(size_t)r], rgba32f + row * (size_t)m->row_begin[(size_t)r]))
-            return mfail(m, rc, "s2d_get_image_rows on rank %d: %s", r, s2d_last_error(m->ctx[(size_t)r]));
+    for (const Rank& R : m->ranks)
+        if (int rc = s2d_get_image_rows(R.ctx, rgba32f + row * (size_t)R.row_begin))
+            return mfail(m, rc, "s2d_get_image_rows on rank %d: %s", R.index, s2d_last_error(R.ctx));
     return S2D_OK;
 }
 

@@ -50,17 +50,22 @@ private:
     size_t cap_ = 0;
 };
 
-// Pinned host memory (hipHostMalloc with the caller's flags), allocated once and kept for its owner's lifetime.
+// Pinned host memory (hipHostMalloc with the caller's flags), allocated once and kept until its owner lets it go.
 template <typename T>
 class S2D_LOCAL HostBuf {
 public:
     HostBuf() = default;
     HostBuf(const HostBuf&) = delete;
     HostBuf& operator=(const HostBuf&) = delete;
-    ~HostBuf() { if (p_) (void)hipHostFree(p_); }
+    ~HostBuf() { release(); }
     operator T*() const { return p_; }
     T* operator->() const { return p_; }
     hipError_t alloc(size_t count, unsigned flags) { return p_ ? hipSuccess : hipHostMalloc((void**)&p_, count * sizeof(T), flags); }
+    void release()
+    {
+        if (p_) (void)hipHostFree(p_);
+        p_ = nullptr;
+    }
 
 private:
     T* p_ = nullptr;
