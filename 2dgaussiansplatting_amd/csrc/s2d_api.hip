@@ -5,7 +5,7 @@
 //   -> adam (+ the sum of the tile errors, + projection of the updated splats and the containment check for the next
 //      iteration)
 // s2d_forward / s2d_backward / s2d_adam_step queue the passes one by one (raster_forward, raster_backward, sqerr_finalize).
-// When the tile lists have to be (re)built:  project -> count scan -> emit -> radix sort -> tile offsets.
+// When the tile lists have to be (re)built:  project -> TileLists (s2d_lists.h): count scan -> emit -> sort -> tile offsets.
 // The host never makes the GPU wait: it reads the 4-byte containment flag after launching the raster kernel
 // optimistically, and the 4-byte pair count only when lists are rebuilt.
 #include "../../include/splat2d.h"
@@ -23,6 +23,7 @@
 #include <new>
 
 #include "s2d_device.h"
+#include "s2d_lists.h"
 #include "s2d_owned.h"
 
 using namespace s2d;
@@ -47,11 +48,9 @@ struct s2d_ctx {
     DevBuf<TileRect> d_rects;
     DevBuf<uint32_t> d_counts;
     DevBuf<uint32_t> d_offsets;
-    DevBuf<uint32_t> d_scan_temp;
-    DevBuf<uint32_t> d_total;
-    DevBuf<uint32_t> d_keys[2];
-    DevBuf<uint32_t> d_vals[2];
-    DevBuf<uint32_t> d_sort_temp;
+    DevBuf<uint32_t> d_scan_temp;               // lent to the list builds and to s2d_halo_commit
+    TileLists lists;                            // the per-tile lists and everything only their builds use
+    // the raster's per-pair hand-over, sized by lists.capacity() (ensure_pair_capacity)
     DevBuf<unsigned long long> d_wave_masks;    // 4 x u64 per listed pair (capacity; written per executed pair): forward -> backward lane masks
     DevBuf<uint32_t> d_exec_list;               // per listed pair (capacity): splat indices of a tile's executed entries, compacted
     DevBuf<uint32_t> d_tile_exec;               // [tiles]: how many entries the tile's last forward walk handed over
@@ -62,17 +61,6 @@ struct s2d_ctx {
     DevBuf<uint32_t> d_det_stamp;               // [pair capacity]
     DevBuf<uint32_t> d_det_touched;             // [n]: which of a splat's slots the current pass wrote (zero between passes)
     uint32_t det_epoch = 0;                     // stamps written so far (monotone; 0 = never)
-    uint64_t pair_capacity = 0;
-    DevBuf<uint32_t> d_tile_off;
-    DevBuf<uint32_t> d_tile_first;    // per tile id (padded to a power of two): position of its first pair (last radix pass)
-    // tile lists in two levels (s2d_tilelists.hip): (splat, tile row) entries sorted by row, then per-row counting sort by column
-    bool two_level = false;            // tiles_x <= kTlMaxColumns and not S2D_CFG_GENERIC_BINNING
-    DevBuf<uint32_t> d_row_counts;     // per splat: tile rows its rectangle covers
-    DevBuf<uint32_t> d_row_offsets;    // ... scanned
-    DevBuf<uint32_t> d_row_off;        // [tiles_y + 1]: where each tile row's entries begin
-    DevBuf<uint32_t> d_chunk_base;     // [tiles_y + 1]
-    DevBuf<uint32_t> d_tl_hist;        // per (row, column, chunk) counts + scan workspace
-    uint32_t* d_list = nullptr; // == one of d_vals after the sort
     // Index-range ("chunked") rendering: when the (tile, splat) pairs of a scene exceed chunk_pairs -- at the latest 2^32 - 65536,
     // what 32-bit list positions can address -- the splats are cut into consecutive index ranges of at most that many
     // pairs, and the lists of one range at a time are built and walked front to back (chunked_forward / chunked_backward)
@@ -82,11 +70,9 @@ struct s2d_ctx {
     int chunk_built = -1;                // the range whose lists are in the buffers now
     DevBuf<float4> d_state;              // per pixel of the slab: (r, g, b, T) carried from range to range
     DevBuf<uint32_t> d_chunk_alive;      // != 0: some pixel is still above the throughput cut-off after this range
-    uint64_t pairs = 0;
-    uint64_t rebins = 0;
+    HostBuf<uint32_t> h_chunk_alive;     // ... read back between two ranges
     bool lists_valid = false;
     bool proj_fresh = false; // d_proj and d_status->rebin_needed describe the CURRENT parameters
-    Event ev_total;                // recorded behind the copy of the pair count to the host (rebuild_lists)
     Event ev_flag;                 // recorded behind the kernel that ran the latest containment check
     int check_seq = 1;             // its sequence number (both stamp words start at 0: nothing matches before a check): the stamp that kernel writes if a splat left its rectangle
     HostBuf<int> h_rebin_stamp;    // host-mapped copy of that stamp (written by the kernel, read after ev_flag)
@@ -121,7 +107,6 @@ struct s2d_ctx {
     DevBuf<DeviceStatus> d_status;
     DevBuf<PairCounters> d_counters;
     // pinned host mirrors
-    HostBuf<uint32_t> h_total;
     HostBuf<DeviceStatus> h_status;
     HostBuf<double> h_trace;            // kHostTrace squared errors: s2d_step reads its trace and the status word in ONE round trip
 
@@ -174,133 +159,51 @@ int use_device(s2d_ctx* c)
     return S2D_OK;
 }
 
-int key_bits_for(int num_tiles)
-{
-    int bits = 0;
-    while ((1 << bits) < num_tiles) bits++;
-    return bits;
-}
-
+// The single place where pair capacity grows: the pair buffers of the lists and the raster's hand-over have one size.
+// Every one of them is released, with the stream idle, before the first is allocated again.
 int ensure_pair_capacity(s2d_ctx* c, uint64_t need)
 {
-    if (need <= c->pair_capacity) return S2D_OK;
+    if (need <= c->lists.capacity()) return S2D_OK;
     if (need >= 0xFFFF0000ull) return fail(c, S2D_E_NOMEM, "tile lists need %llu pairs (> 2^32)", (unsigned long long)need);
     uint64_t cap = std::max<uint64_t>(need + need / 4 + 4096, 1 << 16);
     if (cap > 0xFFFF0000ull) cap = 0xFFFF0000ull;
     S2D_HIP(c, hipStreamSynchronize(c->stream));
-    for (int k = 0; k < 2; k++) c->d_keys[k].release(), c->d_vals[k].release(); // all six go before the first comes back
-    c->d_sort_temp.release(), c->d_wave_masks.release(), c->d_exec_list.release(), c->d_det_data.release(), c->d_det_stamp.release();
-    c->pair_capacity = 0; // (what is left if an allocation below fails)
-    for (int k = 0; k < 2; k++) {
-        S2D_HIP(c, c->d_keys[k].alloc(cap));
-        S2D_HIP(c, c->d_vals[k].alloc(cap));
-    }
-    S2D_HIP(c, c->d_sort_temp.alloc(sort_temp_words((int64_t)cap)));
-    S2D_HIP(c, c->d_wave_masks.alloc((size_t)cap * 4));
-    S2D_HIP(c, c->d_exec_list.alloc((size_t)cap));
-    if (c->deterministic) {
-        S2D_HIP(c, c->d_det_data.alloc((size_t)cap * kDetStride));
-        S2D_HIP(c, c->d_det_stamp.alloc((size_t)cap));
-        S2D_HIP(c, hipMemsetAsync(c->d_det_stamp, 0, (size_t)cap * sizeof(uint32_t), c->stream));
-    }
-    c->pair_capacity = cap;
-    return S2D_OK;
-}
-
-// The workspace of the two-level builder grows with the number of (splat, tile row) entries.
-int ensure_tl_hist(s2d_ctx* c, uint64_t entries)
-{
-    const size_t need = tl_workspace_words(entries, c->g.tiles_x, c->g.tiles_y);
-    if (need <= c->d_tl_hist.capacity()) return S2D_OK;
-    S2D_HIP(c, hipStreamSynchronize(c->stream));
-    S2D_HIP(c, c->d_tl_hist.alloc(need + need / 4 + 4096));
-    return S2D_OK;
+    c->lists.release_pairs();
+    c->d_wave_masks.release(), c->d_exec_list.release(), c->d_det_data.release(), c->d_det_stamp.release();
+    S2D_HIP(c, c->lists.alloc_pairs(cap));
+    const auto hand_over = [&]() -> int {
+        S2D_HIP(c, c->d_wave_masks.alloc((size_t)cap * 4));
+        S2D_HIP(c, c->d_exec_list.alloc((size_t)cap));
+        if (c->deterministic) {
+            S2D_HIP(c, c->d_det_data.alloc((size_t)cap * kDetStride));
+            S2D_HIP(c, c->d_det_stamp.alloc((size_t)cap));
+            S2D_HIP(c, hipMemsetAsync(c->d_det_stamp, 0, (size_t)cap * sizeof(uint32_t), c->stream));
+        }
+        return S2D_OK;
+    };
+    const int rc = hand_over();
+    if (rc != S2D_OK) c->lists.release_pairs(); // (capacity 0 is what is left if an allocation fails)
+    return rc;
 }
 
 // (Re)build the per-tile lists from the current parameters.  The projection has already been queued with mode 0.
-// Two builders with the same result (every tile's list ascending in splat index): the two-level one of s2d_tilelists.hip
-// (images of up to kTlMaxColumns tile columns), and the generic one -- all (tile, splat) pairs emitted in splat order and
-// radix-sorted by tile -- for wider images and on request (S2D_CFG_GENERIC_BINNING).
 // first / count: the index range of the splats to list (count < 0: all of them).  A range's lists hold indices RELATIVE to
 // its first splat -- every per-splat array is handed over from that splat on -- and so do the scanned offsets.
-// Returns kNeedChunks (and builds nothing) when all splats were asked for and their pairs exceed chunk_pairs.
-constexpr int kNeedChunks = -100;
-int rebuild_lists(s2d_ctx* c, int first = 0, int count = -1)
+// *need_ranges (all splats only): their pairs exceed chunk_pairs, nothing was built.
+int rebuild_lists(s2d_ctx* c, int first = 0, int count = -1, bool* need_ranges = nullptr)
 {
-    const bool whole = count < 0;
-    const int n = whole ? c->n : count;
-    const TileRect* const rects = c->d_rects + first;
-    const uint32_t *const counts = c->d_counts + first, *const row_counts = c->d_row_counts ? c->d_row_counts + first : nullptr;
-    uint32_t *const offsets = c->d_offsets + first, *const row_offsets = c->d_row_offsets ? c->d_row_offsets + first : nullptr;
-    // the scans' last kernels store their totals into host-mapped memory themselves (no copy engine between two kernels)
-    S2D_HIP(c, exclusive_scan_u32(counts, offsets, n, c->d_scan_temp, c->d_total, c->stream, c->h_total));
-    if (c->two_level)
-        S2D_HIP(c, exclusive_scan_u32(row_counts, row_offsets, n, c->d_scan_temp, c->d_total + 1, c->stream, c->h_total + 1));
-    S2D_HIP(c, hipEventRecord(c->ev_total, c->stream));
-    // The emission needs the offsets, not the totals (it never writes past the buffers' capacity): queue it behind the
-    // scans and wait for the SCANS only, so the host reads the totals and queues the rest while the emission runs instead
-    // of the device idling through the host's round trip (~30 us per rebuild).  Only when the pairs outgrow the buffers
-    // (rare: they are sized with a quarter to spare) is the emission queued again.
-    auto emit = [&]() -> hipError_t {
-        if (c->two_level) // (there are never more entries than pairs: the pair buffers hold them)
-            return launch_emit_row_entries(rects, row_offsets, row_counts, n, c->d_keys[0], c->d_vals[0],
-                                           (uint32_t)c->pair_capacity, c->stream);
-        return launch_emit_pairs(rects, offsets, counts, n, c->g, c->d_keys[0], c->d_vals[0], (uint32_t)c->pair_capacity,
-                                 c->stream);
-    };
-    S2D_HIP(c, emit());
-    S2D_HIP(c, hipEventSynchronize(c->ev_total));
-    const uint64_t total = *(volatile uint32_t*)c->h_total; // saturates at 0xFFFFFFFF instead of wrapping (scan_top_kernel)
-    if (whole && total > c->chunk_pairs) return kNeedChunks; // (the emission queued above wrote within the buffers' capacity: harmless)
+    const int n = count < 0 ? c->n : count;
+    uint64_t total = 0;
+    c->lists_valid = false; // (count() already writes into the buffers the lists lie in)
+    S2D_HIP(c, c->lists.count(ListInput{c->d_rects + first, c->d_counts + first, c->d_offsets + first, first, n, c->d_scan_temp},
+                              c->stream, &total));
+    if (need_ranges) *need_ranges = total > c->chunk_pairs;
+    if (need_ranges && *need_ranges) return S2D_OK;
     if (total >= 0xFFFF0000ull)
         return fail(c, S2D_E_NOMEM, "the tile lists of splats %d..%d need more than 2^32 - 65536 (tile, splat) pairs", first, first + n - 1);
-    if (total > c->pair_capacity) {
-        int rc = ensure_pair_capacity(c, total);
-        if (rc != S2D_OK) return rc;
-        S2D_HIP(c, emit());
-    }
-    uint32_t *k_out = nullptr, *v_out = nullptr;
-    if (c->two_level) {
-        const uint64_t entries = *(volatile uint32_t*)(c->h_total + 1);
-        if (int rc = ensure_tl_hist(c, entries)) return rc;
-        const int row_bits = key_bits_for(c->g.tiles_y);
-        if (row_bits > 0) { // level 1: the entries by tile row, and where every row begins
-            // (sorted keys written out and compared: with only tiles_y distinct keys the last pass's atomicMin per (block,
-            // key) would pile thousands of atomics on each of a few hundred words)
-            S2D_HIP(c, sort_pairs_u32(c->d_keys[0], c->d_vals[0], c->d_keys[1], c->d_vals[1], (int64_t)entries, row_bits,
-                                      c->d_sort_temp, &k_out, &v_out, nullptr, c->stream));
-            S2D_HIP(c, launch_tile_offsets(k_out, (uint32_t)entries, c->g.tiles_y, c->d_row_off, c->stream, (1u << kTlRowBits) - 1u));
-        } else { // one tile row: the emission order is the row's order
-            const uint32_t two[2] = {0u, (uint32_t)entries};
-            S2D_HIP(c, hipMemcpyAsync(c->d_row_off, two, sizeof(two), hipMemcpyHostToDevice, c->stream));
-            S2D_HIP(c, hipStreamSynchronize(c->stream)); // (`two` lives on this stack frame)
-            v_out = c->d_vals[0];
-            k_out = c->d_keys[0];
-        }
-        // level 2: every row's entries by column, straight into the lists (the value buffer the sort finished with is free)
-        uint32_t* list = v_out == c->d_vals[0] ? c->d_vals[1] : c->d_vals[0];
-        S2D_HIP(c, launch_tile_lists_from_rows(v_out, k_out, entries, c->d_row_off, c->g, c->d_chunk_base, c->d_tl_hist,
-                                               c->d_tile_off, list, c->stream));
-        c->d_list = list;
-    } else {
-        const int key_bits = key_bits_for(c->g.num_tiles);
-        if (key_bits > 0) {
-            // the last radix pass records where each tile's pairs begin instead of writing the sorted keys out
-            S2D_HIP(c, hipMemsetAsync(c->d_tile_first, 0xFF, ((size_t)1 << key_bits) * sizeof(uint32_t), c->stream));
-            S2D_HIP(c, sort_pairs_u32(c->d_keys[0], c->d_vals[0], c->d_keys[1], c->d_vals[1], (int64_t)total, key_bits,
-                                      c->d_sort_temp, &k_out, &v_out, c->d_tile_first, c->stream));
-            S2D_HIP(c, launch_tile_offsets_from_first(c->d_tile_first, c->g.num_tiles, (uint32_t)total,
-                                                      c->d_tile_first + ((size_t)1 << key_bits), c->d_tile_off, c->stream));
-        } else { // a single tile: nothing to sort
-            S2D_HIP(c, sort_pairs_u32(c->d_keys[0], c->d_vals[0], c->d_keys[1], c->d_vals[1], (int64_t)total, key_bits,
-                                      c->d_sort_temp, &k_out, &v_out, nullptr, c->stream));
-            S2D_HIP(c, launch_tile_offsets(k_out, (uint32_t)total, c->g.num_tiles, c->d_tile_off, c->stream));
-        }
-        c->d_list = v_out;
-    }
-    c->pairs = total;
-    c->rebins++;
-    c->lists_valid = whole; // a range's lists are walked once and replaced by the next range's
+    if (int rc = ensure_pair_capacity(c, total)) return rc;
+    S2D_HIP(c, c->lists.finish(c->stream));
+    c->lists_valid = count < 0; // a range's lists are walked once and replaced by the next range's
     c->since_rebin = 0;
     return S2D_OK;
 }
@@ -310,7 +213,7 @@ int rebuild_lists(s2d_ctx* c, int first = 0, int count = -1)
 RasterArgs raster_args(const s2d_ctx* c, int first = 0, int count = -1)
 {
     RasterArgs a;
-    a.tile_off = c->d_tile_off; a.list = c->d_list; a.wave_masks = c->d_wave_masks;
+    a.tile_off = c->lists.tile_off(); a.list = c->lists.list(); a.wave_masks = c->d_wave_masks;
     a.exec_list = c->d_exec_list; a.tile_exec = c->d_tile_exec; a.retire_hint = c->d_retire_hint;
     a.proj = c->d_proj + first; a.grads = c->d_grads + (size_t)first * 9;
     a.image0 = c->d_image0; a.image_ref = c->d_ref; a.tile_sqerr = c->d_tile_sqerr;
@@ -363,6 +266,7 @@ int plan_chunks(s2d_ctx* c)
     c->chunks.push_back(c->n);
     if (!c->d_state) S2D_HIP(c, c->d_state.alloc((size_t)c->g.W * (size_t)(c->g.row_end - c->g.row_begin)));
     if (!c->d_chunk_alive) S2D_HIP(c, c->d_chunk_alive.alloc(1));
+    S2D_HIP(c, c->h_chunk_alive.alloc(1, hipHostMallocDefault));
     return S2D_OK;
 }
 
@@ -393,9 +297,9 @@ int chunked_forward(s2d_ctx* c)
         S2D_HIP(c, launch_raster(RasterPass::ForwardRange, a, c->stream));
         c->chunks_used = k + 1;
         if (k + 1 < K) {
-            S2D_HIP(c, hipMemcpyAsync(c->h_total + 2, c->d_chunk_alive, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            S2D_HIP(c, hipMemcpyAsync(c->h_chunk_alive, c->d_chunk_alive, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
             S2D_HIP(c, hipStreamSynchronize(c->stream));
-            if (*(volatile uint32_t*)(c->h_total + 2) == 0u) break;
+            if (*(volatile uint32_t*)c->h_chunk_alive == 0u) break;
         }
     }
     return S2D_OK;
@@ -554,18 +458,18 @@ int queue_raster(s2d_ctx* c, const RasterJob& job)
     if (rebuild) {
         if (int rc = compact_flush(c)) return rc;
         S2D_HIP(c, launch_project(c->d_splats, c->d_held, c->n, c->g, c->margin, 0, c->d_proj, c->d_rects, c->d_counts,
-                                  c->two_level ? c->d_row_counts : nullptr, c->d_status, 0, nullptr, c->stream));
+                                  c->lists.row_counts(), c->d_status, 0, nullptr, c->stream));
         c->chunks.clear();
-        int rc = rebuild_lists(c);
-        if (rc != S2D_OK && rc != kNeedChunks) return rc;
-        if (rc == kNeedChunks && (c->cfg.flags & S2D_CFG_COUNT_PAIRS))
+        bool need_ranges = false;
+        int rc = rebuild_lists(c, 0, -1, &need_ranges);
+        if (rc != S2D_OK) return rc;
+        if (need_ranges && (c->cfg.flags & S2D_CFG_COUNT_PAIRS))
             return fail(c, S2D_E_NOMEM, "pair counting (S2D_CFG_COUNT_PAIRS) is not available for scenes beyond %llu (tile, splat) pairs",
                         (unsigned long long)c->chunk_pairs);
         c->proj_fresh = true;
         c->check_seq++; // the new lists cover the current parameters: a stamp that asked for them matches nothing now
-        if (rc == kNeedChunks) {
+        if (need_ranges) {
             // more pairs than one set of lists may hold: render by index ranges (every pass rebuilds: lists_valid stays false)
-            c->lists_valid = false;
             if ((rc = plan_chunks(c)) != S2D_OK) return rc;
             if ((rc = chunked_forward(c)) != S2D_OK) return rc;
             if (job.fused && (rc = chunked_backward(c, job.need_opacity_grad)) != S2D_OK) return rc;
@@ -777,20 +681,11 @@ int s2d_create(const s2d_config* cfg, s2d_ctx** out)
     S2D_HIP(c, c->d_counts.alloc(n));
     S2D_HIP(c, c->d_offsets.alloc(n));
     S2D_HIP(c, c->d_scan_temp.alloc(scan_temp_words((int64_t)n)));
-    S2D_HIP(c, c->d_total.alloc(4)); // [0] pairs, [1] (splat, tile row) entries
-    S2D_HIP(c, c->d_tile_off.alloc((size_t)g.num_tiles + 1));
-    S2D_HIP(c, c->d_tile_first.alloc(((size_t)1 << key_bits_for(g.num_tiles)) + tile_first_temp_words(g.num_tiles))); // + chunk minima
-    c->two_level = g.tiles_x <= kTlMaxColumns && !(cfg->flags & S2D_CFG_GENERIC_BINNING);
+    S2D_HIP(c, c->lists.create(g, n, (cfg->flags & S2D_CFG_GENERIC_BINNING) != 0));
     if (const char* e = getenv("S2D_COMPACT_HELD")) c->compact_enabled = atoi(e) != 0;
     if (const char* e = getenv("S2D_CHUNK_PAIRS")) { // pairs per index range (tests; default 2^30, never beyond 32-bit positions)
         const unsigned long long v = strtoull(e, nullptr, 10);
         if (v > 0) c->chunk_pairs = std::min<unsigned long long>(v, 0xFFFF0000ull - 1);
-    }
-    if (c->two_level) {
-        S2D_HIP(c, c->d_row_counts.alloc(n));
-        S2D_HIP(c, c->d_row_offsets.alloc(n));
-        S2D_HIP(c, c->d_row_off.alloc((size_t)g.tiles_y + 1));
-        S2D_HIP(c, c->d_chunk_base.alloc((size_t)g.tiles_y + 1));
     }
     c->deterministic = (cfg->flags & S2D_CFG_DETERMINISTIC) != 0;
     if (c->deterministic) {
@@ -810,8 +705,6 @@ int s2d_create(const s2d_config* cfg, s2d_ctx** out)
     S2D_HIP(c, c->d_status.alloc(1));
     S2D_HIP(c, c->d_counters.alloc(1));
     S2D_HIP(c, c->ev_flag.create(hipEventDisableTiming));
-    S2D_HIP(c, c->ev_total.create(hipEventDisableTiming));
-    S2D_HIP(c, c->h_total.alloc(16, hipHostMallocMapped)); // 64 bytes each for the two words kernels write through
     S2D_HIP(c, c->h_status.alloc(1, hipHostMallocDefault));
     S2D_HIP(c, c->h_trace.alloc(kHostTrace, hipHostMallocDefault));
     S2D_HIP(c, c->h_rebin_stamp.alloc(16, hipHostMallocMapped));
@@ -1202,9 +1095,9 @@ int s2d_get_stats(s2d_ctx* c, s2d_stats* out)
     out = &full;
     std::memset(out, 0, sizeof(*out));
     out->struct_size = caller_size;
-    out->pairs_binned = c->pairs;
-    out->pairs_capacity = c->pair_capacity;
-    out->rebins = c->rebins;
+    out->pairs_binned = c->lists.pairs();
+    out->pairs_capacity = c->lists.capacity();
+    out->rebins = c->lists.builds();
     out->fwd_visited = pc.fwd_visited; out->fwd_active = pc.fwd_active;
     out->bwd_visited = pc.bwd_visited; out->bwd_active = pc.bwd_active;
     out->fwd_staged = pc.fwd_staged; out->bwd_staged = pc.bwd_staged;
@@ -1222,7 +1115,7 @@ int s2d_get_stats(s2d_ctx* c, s2d_stats* out)
 int s2d_get_rebuild_count(const s2d_ctx* c, uint64_t* rebuilds)
 {
     if (!c || !rebuilds) return S2D_E_INVALID;
-    *rebuilds = c->rebins;
+    *rebuilds = c->lists.builds();
     return S2D_OK;
 }
 
@@ -1236,12 +1129,12 @@ int s2d_debug_get_tile_lists(s2d_ctx* c, int32_t* tiles_x, int32_t* tiles_y, uin
     if (tiles_y) *tiles_y = c->g.tiles_y;
     if (offsets) {
         if (offsets_capacity < c->g.num_tiles + 1) return S2D_E_INVALID;
-        S2D_HIP(c, hipMemcpyAsync(offsets, c->d_tile_off, (size_t)(c->g.num_tiles + 1) * sizeof(uint32_t),
+        S2D_HIP(c, hipMemcpyAsync(offsets, c->lists.tile_off(), (size_t)(c->g.num_tiles + 1) * sizeof(uint32_t),
                                   hipMemcpyDeviceToHost, c->stream));
     }
     if (list) {
-        if (list_capacity < (int64_t)c->pairs) return S2D_E_INVALID;
-        S2D_HIP(c, hipMemcpyAsync(list, c->d_list, (size_t)c->pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (list_capacity < (int64_t)c->lists.pairs()) return S2D_E_INVALID;
+        S2D_HIP(c, hipMemcpyAsync(list, c->lists.list(), (size_t)c->lists.pairs() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     }
     S2D_HIP(c, hipStreamSynchronize(c->stream));
     return S2D_OK;

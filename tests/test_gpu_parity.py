@@ -23,6 +23,7 @@ Bars (north_star: "within 1e-4 rel fp32"):
     (floor 1.0) of the oracle's;
   * MSE (double): 1e-9 relative for the same framebuffer.
 """
+import functools
 import hashlib
 import importlib
 import os
@@ -729,6 +730,91 @@ def test_image_covering_splats_grow_the_pair_buffers():
     st = _run_pair(W, H, s, check_grads=False)
     assert st["pairs_binned"] == n * 40 * 30
     assert st["pairs_capacity"] >= st["pairs_binned"]
+
+
+@functools.lru_cache(maxsize=None)
+def _covering_scene():
+    """120 splats that each cover all 1200 tiles of 640x480: 144 000 pairs, more than a new context has room for.
+    Opacity 0.02 keeps every pixel above 1/256 through all of them (0.98^120 = 0.09): no tile retires."""
+    W, H, n = 640, 480, 120
+    rng = np.random.default_rng(22)
+    s = np.zeros(n, dtype=O.SPLAT_DTYPE)
+    s["pos"][:, 0] = rng.uniform(0, W - 1, n)
+    s["pos"][:, 1] = rng.uniform(0, H - 1, n)
+    s["sx"] = rng.uniform(250, 400, n)
+    s["sy"] = rng.uniform(250, 400, n)
+    s["rot"] = rng.uniform(0, np.pi, n)
+    s["color"] = rng.uniform(0, 1, (n, 3))
+    s["opacity"] = 0.02
+    tgt = O.synthetic_target(W, H)
+    o = O.OracleTrainer(tgt, n)
+    o.splats[:] = s
+    return W, H, s, tgt, o.forward().tobytes()
+
+
+@functools.lru_cache(maxsize=None)
+def _covering_run(generic, deterministic, chunk_pairs=None):
+    """forward + backward on a new context (the first build grows the pair buffers), then -- one set of lists only -- the
+    same splats set again, forward (a build that does not grow) and, deterministic, a second backward."""
+    W, H, s, tgt, _ = _covering_scene()
+    r = {}
+    with S2D.Trainer(W, H, len(s), generic_binning=generic, deterministic=deterministic, chunk_pairs=chunk_pairs) as t:
+        t.set_target(tgt)
+        t.set_splats(s)
+        t.forward()
+        r["image"], r["stats"] = t.get_image().tobytes(), t.stats()
+        if chunk_pairs is None:
+            r["lists"] = t.tile_lists()
+        t.backward()
+        r["g1"] = t.get_grads().view(np.float32).copy()
+        if chunk_pairs is None:
+            t.set_splats(s)
+            t.forward()
+            r["image2"], r["stats2"], r["lists2"] = t.get_image().tobytes(), t.stats(), t.tile_lists()
+            if deterministic:
+                t.backward()
+                r["g2"] = t.get_grads().view(np.float32).copy()
+    return r
+
+
+@pytest.mark.parametrize("deterministic", [False, True])
+@pytest.mark.parametrize("generic", [False, True])
+def test_backward_and_rebuild_after_the_pair_buffers_grew(generic, deterministic):
+    """A build that had to grow the pair buffers leaves what one that did not grow leaves, for both builders: same
+    lists, same framebuffer (the oracle's), and -- deterministic sums -- the same gradients from the backward pass
+    behind either (nothing zeroes the gradient buffer between the two passes, and the gather adds: exactly 2 * g1)."""
+    r = _covering_run(generic, deterministic)
+    print("pairs", r["stats"]["pairs_binned"], "capacity", r["stats"]["pairs_capacity"], "->", r["stats2"]["pairs_capacity"],
+          "rebins", r["stats"]["rebins"], r["stats2"]["rebins"])
+    assert r["image"] == _covering_scene()[4]
+    assert r["stats"]["pairs_binned"] == 144000
+    assert r["stats"]["pairs_capacity"] >= r["stats"]["pairs_binned"]
+    assert r["stats"]["rebins"] == 1
+    assert r["stats2"]["rebins"] == 2
+    assert r["stats2"]["pairs_capacity"] == r["stats"]["pairs_capacity"]
+    (tx, ty, off, lst), (tx2, ty2, off2, lst2) = r["lists"], r["lists2"]
+    assert (tx, ty) == (tx2, ty2) == (40, 30)
+    assert off.tobytes() == off2.tobytes() and lst.tobytes() == lst2.tobytes()
+    assert np.array_equal(np.diff(off.astype(np.int64)), np.full(1200, 120))  # every splat in every tile
+    assert r["image2"] == r["image"]
+    assert np.any(r["g1"] != 0)
+    if deterministic:
+        assert r["g2"].tobytes() == (2.0 * r["g1"]).astype(np.float32).tobytes()
+
+
+# 80 000: ranges of 66 and 54 splats (66 * 1200 = 79 200 <= 80 000 < 67 * 1200).  100 000: ranges of 83 and 37 splats, and
+# the first range (99 600 pairs) is more than a new context of 120 splats has room for (65 536 and a quarter: 86 016), so
+# it is a RANGE build that grows the pair buffers.
+@pytest.mark.parametrize("budget,first_range", [(80000, 79200), (100000, 99600)])
+@pytest.mark.parametrize("generic", [False, True])
+def test_index_range_builds_on_image_covering_splats(generic, budget, first_range):
+    """The same scene by index ranges, deterministic: framebuffer and gradients bit for bit those of one set of lists."""
+    whole, r = _covering_run(generic, True), _covering_run(generic, True, budget)
+    print("capacity", r["stats"]["pairs_capacity"], "rebins", r["stats"]["rebins"])
+    assert r["image"] == whole["image"]
+    assert r["g1"].tobytes() == whole["g1"].tobytes()
+    assert r["stats"]["pairs_capacity"] >= first_range
+    assert r["stats"]["rebins"] >= 2
 
 
 @pytest.mark.parametrize("budget,kw", [(3000, {}), (700, {}), (3000, {"fp16_images": True}), (2500, {"generic_binning": True}),

@@ -3,7 +3,7 @@
 different gpurun calls do not compare).  Every build runs the same s2d_step(iters) on the same workloads, alternating,
 and the best of `reps` wall-clock timings per build is reported.
 
-  python tools/gpu_ab.py lib/libsplat2d_hip_base.so lib/libsplat2d_hip.so [--reps 3] [--small]
+  python tools/gpu_ab.py lib/libsplat2d_hip_base.so lib/libsplat2d_hip.so [--reps 3] [--only K] [--rebin-interval 1]
 """
 import argparse
 import importlib
@@ -50,11 +50,14 @@ def main():
     ap.add_argument("--only", type=int, default=-1, help="index into the workload list")
     ap.add_argument("--deterministic", action="store_true", help="contexts with S2D_CFG_DETERMINISTIC")
     ap.add_argument("--fp16-images", action="store_true")
+    ap.add_argument("--rebin-interval", type=int, default=0, help="1: the tile lists are rebuilt in every iteration")
     args = ap.parse_args()
     if args.deterministic:
         MODE["deterministic"] = True
     if args.fp16_images:
         MODE["fp16_images"] = True
+    if args.rebin_interval:
+        MODE["rebin_interval"] = args.rebin_interval
     libs = [os.path.abspath(p) for p in args.libs]
     for k, (name, W, H, n, iters, rows) in enumerate(WORKLOADS):
         if args.only >= 0 and k != args.only:
