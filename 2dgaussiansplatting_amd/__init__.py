@@ -70,7 +70,7 @@ ABI_VERSION = 2  # S2D_ABI_VERSION of include/splat2d.h as this binding was writ
 ABI_SYMBOLS = [
     "s2d_abi_version", "s2d_create", "s2d_destroy", "s2d_set_target", "s2d_set_target_synthetic",
     "s2d_init_splats", "s2d_set_splats", "s2d_get_splats", "s2d_set_adam", "s2d_get_adam", "s2d_forward",
-    "s2d_get_image", "s2d_get_image_rows", "s2d_backward", "s2d_forward_backward", "s2d_get_grads", "s2d_adam_step", "s2d_step", "s2d_get_mse",
+    "s2d_get_image", "s2d_get_image_rows", "s2d_backward", "s2d_backward_image_grads", "s2d_set_splats_device", "s2d_get_image_rows_device", "s2d_forward_backward", "s2d_get_grads", "s2d_adam_step", "s2d_step", "s2d_get_mse",
     "s2d_bind_grads_device", "s2d_grads_device_ptr", "s2d_stream", "s2d_get_sqerr_trace", "s2d_synchronize", "s2d_get_stats",
     "s2d_get_rebuild_count",
     "s2d_last_error", "s2d_test_sincos", "s2d_test_sort_pairs", "s2d_test_exclusive_scan",
@@ -225,6 +225,9 @@ def load_library(path=None):
     sig("s2d_get_image_rows", [vp, vp])
     sig("s2d_backward", [vp, u32])
     sig("s2d_forward_backward", [vp, u32])
+    sig("s2d_backward_image_grads", [vp, vp, u32])
+    sig("s2d_set_splats_device", [vp, vp])
+    sig("s2d_get_image_rows_device", [vp, vp])
     sig("s2d_get_grads", [vp, vp])
     sig("s2d_adam_step", [vp, u32])
     sig("s2d_step", [vp, i32, u32, vp])
@@ -417,6 +420,24 @@ class Trainer:
         a = np.zeros(self.n, dtype=SPLAT_DTYPE)
         self._ck(self.L.s2d_get_grads(self._h, _p(a)))
         return a
+
+    # -- the rasteriser as a building block: raw DEVICE pointers, work queued on the context's stream, no host
+    # synchronisation (torch_op.SplatRenderer wraps these around torch tensors)
+    def set_splats_device(self, ptr):
+        """The n x 9 float parameters from device memory (s2d_set_splats_device)."""
+        self._ck(self.L.s2d_set_splats_device(self._h, C.c_void_p(ptr) if ptr else None))
+
+    def get_image_rows_device(self, ptr):
+        """The slab's rows of image0 into device memory, always RGBA32F (s2d_get_image_rows_device)."""
+        self._ck(self.L.s2d_get_image_rows_device(self._h, C.c_void_p(ptr) if ptr else None))
+
+    def backward_image_grads(self, ptr, skip_opacity_grad=None):
+        """Backward pass from the caller's dL/d(image0) (device pointer, the slab's rows, RGBA32F, .w ignored) instead of
+        image0 - imageRef; skip_opacity_grad as backward()."""
+        if skip_opacity_grad is None:
+            skip_opacity_grad = self.lean_backward and not self.optimize_opacity
+        self._ck(self.L.s2d_backward_image_grads(self._h, C.c_void_p(ptr) if ptr else None,
+                                                 S2D_BWD_SKIP_OPACITY_GRAD if skip_opacity_grad else 0))
 
     def adam_step(self):
         self._ck(self.L.s2d_adam_step(self._h, self._flags()))

@@ -306,11 +306,13 @@ int chunked_forward(s2d_ctx* c)
 }
 
 // Backward pass over the same ranges (main.cpp:548-712), from a fresh per-pixel state; image0 holds the final colours.
-int chunked_backward(s2d_ctx* c, bool need_opacity_grad)
+// upstream: as in queue_backward.
+int chunked_backward(s2d_ctx* c, bool need_opacity_grad, const float4* upstream = nullptr)
 {
     for (int k = 0; k < c->chunks_used; k++) {
         RasterArgs a;
         if (int rc = build_chunk(c, k, &a)) return rc;
+        a.upstream = upstream;
         with_backward_walk(c, a, need_opacity_grad);
         S2D_HIP(c, launch_raster(RasterPass::BackwardRange, a, c->stream));
     }
@@ -351,6 +353,10 @@ int launch_job(s2d_ctx* c, bool optimistic, const RasterJob& job)
 //     record, moments included, is new.
 //   some splat rows replaced (s2d_rows_scatter): Projection; state_written().  Not Lists: a row moves a splat a little,
 //     and the containment check of the projection that follows asks for new lists if it left its rectangle.
+//   all splats replaced from device memory (s2d_set_splats_device): as some rows, over all of them -- Projection;
+//     state_written().  Not Lists, and no fresh status word: this is the call of an optimisation loop outside the
+//     library, which moves every splat a little per call; a splat that left its rectangle gets its new lists from the
+//     same containment check.
 //   moments replaced (s2d_set_adam, s2d_rows_scatter): nothing, what is drawn depends on the parameters only; state_written().
 //   held set changed (s2d_halo_commit): Lists if splats arrived, on the first commit and on the return to holding
 //     everything (the lists hold the held splats only); departures alone leave lists that still cover every held splat.
@@ -505,16 +511,24 @@ int queue_sqerr(s2d_ctx* c, bool defer = false)
     return defer && (c->n + 255) / 256 >= kSqerrChunks ? S2D_OK : flush_sqerr(c);
 }
 
-int queue_backward(s2d_ctx* c, bool need_opacity_grad)
+// upstream != nullptr (s2d_backward_image_grads): the walk starts from the caller's dL/d(image0) instead of
+// image0 - imageRef.  The loss is the caller's, so no squared error is formed or queued: the trace ring, last_sqerr_slot
+// and a reduction still deferred to the next Adam launch stay as the last s2d_backward left them.
+int queue_backward(s2d_ctx* c, bool need_opacity_grad, const float4* upstream = nullptr)
 {
-    if (!c->have_forward) return fail(c, S2D_E_STATE, "s2d_backward needs s2d_forward on the current parameters");
+    if (!c->have_forward) return fail(c, S2D_E_STATE, "the backward pass needs s2d_forward on the current parameters");
     if (!c->chunks.empty()) { // the forward pass went over index ranges: so does this one
-        if (int rc = chunked_backward(c, need_opacity_grad)) return rc;
-        return queue_sqerr(c);
+        if (int rc = chunked_backward(c, need_opacity_grad, upstream)) return rc;
+    } else {
+        RasterArgs a = raster_args(c);
+        a.upstream = upstream;
+        with_backward_walk(c, a, need_opacity_grad);
+        S2D_HIP(c, launch_raster(RasterPass::Backward, a, c->stream));
     }
-    RasterArgs a = raster_args(c);
-    with_backward_walk(c, a, need_opacity_grad);
-    S2D_HIP(c, launch_raster(RasterPass::Backward, a, c->stream));
+    if (upstream) {
+        c->have_backward = true;
+        return S2D_OK;
+    }
     return queue_sqerr(c);
 }
 
@@ -886,6 +900,41 @@ int s2d_backward(s2d_ctx* c, uint32_t flags)
     if (!c) return S2D_E_INVALID;
     if (int rc = use_device(c)) return rc;
     return queue_backward(c, !(flags & S2D_BWD_SKIP_OPACITY_GRAD));
+}
+
+int s2d_backward_image_grads(s2d_ctx* c, const float* dimage_rows_device, uint32_t flags)
+{
+    if (!c || !dimage_rows_device) return S2D_E_INVALID;
+    if ((uintptr_t)dimage_rows_device & 15u) return fail(c, S2D_E_INVALID, "the image gradient must be 16-byte aligned");
+    if (c->cfg.flags & S2D_CFG_COUNT_PAIRS)
+        return fail(c, S2D_E_INVALID, "pair counting (S2D_CFG_COUNT_PAIRS) has no backward pass from a caller's image gradient");
+    if (int rc = use_device(c)) return rc;
+    return queue_backward(c, !(flags & S2D_BWD_SKIP_OPACITY_GRAD), reinterpret_cast<const float4*>(dimage_rows_device));
+}
+
+int s2d_set_splats_device(s2d_ctx* c, const float* splats_device)
+{
+    if (!c || (!splats_device && c->n)) return S2D_E_INVALID;
+    if (int rc = use_device(c)) return rc;
+    if (int rc = compact_flush(c)) return rc; // the moments of the held splats must not be lost with the compact copy
+    if (c->n > 0)
+        S2D_HIP(c, hipMemcpyAsync(c->d_splats, splats_device, (size_t)c->n * sizeof(s2d_splat), hipMemcpyDeviceToDevice, c->stream));
+    if (int rc = state_written(c, true)) return rc;
+    invalidate(c, Stale::Projection); // (not Lists: see the table above invalidate())
+    return S2D_OK;
+}
+
+int s2d_get_image_rows_device(s2d_ctx* c, float* rgba32f_rows_device)
+{
+    if (!c || !rgba32f_rows_device) return S2D_E_INVALID;
+    if ((uintptr_t)rgba32f_rows_device & 15u) return fail(c, S2D_E_INVALID, "the image buffer must be 16-byte aligned");
+    if (int rc = use_device(c)) return rc;
+    const size_t px = slab_pixels(c);
+    if (c->half_images)
+        S2D_HIP(c, launch_convert_f16_to_f32(c->d_image0, reinterpret_cast<float4*>(rgba32f_rows_device), px, c->stream));
+    else
+        S2D_HIP(c, hipMemcpyAsync(rgba32f_rows_device, c->d_image0, px * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    return S2D_OK;
 }
 
 int s2d_get_grads(s2d_ctx* c, s2d_splat* dsplats)

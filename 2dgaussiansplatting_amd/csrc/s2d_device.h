@@ -211,6 +211,9 @@ struct RasterArgs {
     const ProjRec* proj = nullptr;  // proj / grads / the arrays of `det` start at the first splat of the lists
     void* image0 = nullptr;
     const void* image_ref = nullptr;
+    // Backward, BackwardRange (not with `count`): the caller's dL/d(image0) for the rows of the slab, RGBA32F whatever the
+    // image format, .w ignored -- the walk starts from it instead of image0 - image_ref and forms no squared error
+    const float4* upstream = nullptr;
     // forward -> backward walk: lane masks and splat indices of the entries the forward walk executed, compacted to the
     // front of each tile's list range, and their number per tile (s2d_raster.hip forward_tile)
     unsigned long long* wave_masks = nullptr;

@@ -95,6 +95,23 @@ __device__ __forceinline__ void store_pixel(void* base, size_t i, float4 c)
     }
 }
 
+// What the backward walk starts from, per pixel: the reference's own dL/dC = finalColor - imageRef (main.cpp:616), or --
+// UPSTREAM -- the caller's dL/d(image0) of some other loss.  The backward kernels' image_ref is then that gradient image:
+// RGBA32F whatever the image format, one 16-byte load per pixel, .w not used, 0 for lanes outside the image.
+template <bool HALF, bool UPSTREAM>
+__device__ __forceinline__ float4 load_ref_or_upstream(const void* src, size_t i)
+{
+    return UPSTREAM ? reinterpret_cast<const float4*>(src)[i] : load_pixel<HALF>(src, i);
+}
+// (By value on purpose: handed over as whole 16-byte values, the way backward_tile took `ref` before, the kernels without
+// UPSTREAM compile to the instructions they had when the subtraction stood inside backward_tile -- DESIGN.md section 10;
+// by reference the compiler narrows their image loads and renumbers registers.)
+template <bool UPSTREAM>
+__device__ __forceinline__ float4 loss_grad(const float4 fin, const float4 src)
+{
+    return UPSTREAM ? src : make_float4(fin.x - src.x, fin.y - src.y, fin.z - src.z, 0.0f);
+}
+
 // A pair of fp32 values -- (vx,vy), (mx,my), the (r,g) colour channels, the two covariance dot products.  The blend
 // and gradient arithmetic below is written on such pairs with every product and sum in the reference's order.
 // A plain struct whose operators are two scalar VALU instructions each: on gfx950 a v_pk_{mul,add,fma}_f32 occupies a
@@ -575,14 +592,17 @@ struct BwdShared {
     __attribute__((aligned(16))) float xpose[4][kRedDwords]; // wave-private transpose scratch
 };
 
-// One tile's backward walk (main.cpp:552-711 for its pixels) from the pixel's final colour `fin` and target `ref`:
+// One tile's backward walk (main.cpp:552-711 for its pixels) from the pixel's final colour `fin` and the loss gradient
+// `dL` = dL/dC of that pixel (.w unused; the reference's own loss: fin - ref, main.cpp:616, formed by the caller):
 // adds the tile's partial gradients into grads (or its deterministic slots) and stores the tile's squared error.
+// UPSTREAM: dL is a caller's gradient of some other loss, so there is no squared error to form -- no reduction, no
+// tile_sqerr store, no ticket (tile_sqerr and sq are not looked at).
 // It walks the n_handed entries the forward walk handed over (exec_list, wave_masks: see forward_tile), every one of which
 // has a body to run in some wave; a counting walk (COUNT) goes through the tile's whole list and ignores both.
 // CHUNK: as in forward_tile -- the list is one index range of the splats, *state_io (running colour r, g, b and T of
 // main.cpp:601-625, :707) is the pixel's state after the ranges before it on entry and after this range on return.
-template <bool COUNT, bool NEED_OP, bool DET, bool EXACT, bool CHUNK = false>
-__device__ __forceinline__ void backward_tile(BwdShared<DET>& s, const TileCtx& c, const float4 fin, const float4 ref,
+template <bool COUNT, bool NEED_OP, bool DET, bool EXACT, bool CHUNK = false, bool UPSTREAM = false>
+__device__ __forceinline__ void backward_tile(BwdShared<DET>& s, const TileCtx& c, const float4 fin, const float4 dL,
                                               const uint32_t* __restrict__ tile_off, const uint32_t* __restrict__ list,
                                               const ProjRec* __restrict__ proj,
                                               const unsigned long long* __restrict__ wave_masks,
@@ -599,11 +619,11 @@ __device__ __forceinline__ void backward_tile(BwdShared<DET>& s, const TileCtx& 
     const bool op_lane = NEED_OP && !DET && lane == 63;
     const int part_slot = op_lane ? 8 : lane >> 3;
     const bool adds = (lane & 7) == 0 || op_lane;
-    const float dLr = fin.x - ref.x, dLg = fin.y - ref.y, dLb = fin.z - ref.z; // dL_dC, main.cpp:616
+    const float dLr = dL.x, dLg = dL.y, dLb = dL.z; // dL_dC, main.cpp:616
     const f2 dLrg = mk2(dLr, dLg), fin_rg = mk2(fin.x, fin.y);
 
     // squared error of this tile (main.cpp:801-802): float per pixel, double across pixels
-    {
+    if constexpr (!UPSTREAM) {
         const float ex = dLr * 255.0f, ey = dLg * 255.0f, ez = dLb * 255.0f;
         double e2 = inside ? (double)(ex * ex + ey * ey + ez * ez) : 0.0;
 #pragma unroll
@@ -613,7 +633,9 @@ __device__ __forceinline__ void backward_tile(BwdShared<DET>& s, const TileCtx& 
     if (!DET)
         for (int i = tid; i < BB * 3; i += 256) reinterpret_cast<float4*>(s.part)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     __syncthreads();
-    if (sq.out == nullptr) {
+    if constexpr (UPSTREAM) {
+        // (no squared error: the loss is the caller's)
+    } else if (sq.out == nullptr) {
         if (tid == 0) tile_sqerr[c.tile] = ((s.red[0] + s.red[1]) + s.red[2]) + s.red[3];
     } else {
         // Small images: the iteration's squared error (main.cpp:796-805) is summed here, by the workgroup whose tile
@@ -824,7 +846,8 @@ __device__ __forceinline__ void backward_tile(BwdShared<DET>& s, const TileCtx& 
     }
 }
 
-template <bool COUNT, bool NEED_OP, bool HALF, bool DET, bool EXACT>
+// UPSTREAM (both backward kernels): image_ref is not the target but the caller's dL/d(image0), see load_ref_or_upstream.
+template <bool COUNT, bool NEED_OP, bool HALF, bool DET, bool EXACT, bool UPSTREAM = false>
 __global__ __launch_bounds__(256) void raster_backward_kernel(const uint32_t* __restrict__ tile_off,
                                                               const uint32_t* __restrict__ list,
                                                               const ProjRec* __restrict__ proj,
@@ -846,10 +869,10 @@ __global__ __launch_bounds__(256) void raster_backward_kernel(const uint32_t* __
     float4 fin = make_float4(0.f, 0.f, 0.f, 0.f), ref = make_float4(0.f, 0.f, 0.f, 0.f);
     if (c.inside) {
         fin = load_pixel<HALF>(image0, pixel_index(c, g));    // finalColor, main.cpp:613
-        ref = load_pixel<HALF>(image_ref, pixel_index(c, g));
+        ref = load_ref_or_upstream<HALF, UPSTREAM>(image_ref, pixel_index(c, g));
     }
     const uint32_t n_exec = COUNT ? 0u : tile_exec[tile];
-    backward_tile<COUNT, NEED_OP, DET, EXACT>(s, c, fin, ref, tile_off, list, proj, wave_masks, exec_list, n_exec, grads, tile_sqerr,
+    backward_tile<COUNT, NEED_OP, DET, EXACT, false, UPSTREAM>(s, c, fin, loss_grad<UPSTREAM>(fin, ref), tile_off, list, proj, wave_masks, exec_list, n_exec, grads, tile_sqerr,
                                               g, det, counters, SqerrJob{nullptr, 0, nullptr, nullptr});
 }
 
@@ -901,8 +924,8 @@ __global__ __launch_bounds__(256, 8) void raster_fused_kernel(const uint32_t* __
     // the backward walk re-uses the LDS the forward walk's hand-over may still be reading, and reads what other threads
     // of the workgroup handed over through global memory
     __syncthreads();
-    backward_tile<false, NEED_OP, DET, EXACT>(*reinterpret_cast<BwdShared<DET>*>(smem), c, fin, ref, tile_off, list, proj,
-                                              wave_masks, exec_list, n_exec, grads, tile_sqerr, g, det, nullptr, sq);
+    backward_tile<false, NEED_OP, DET, EXACT>(*reinterpret_cast<BwdShared<DET>*>(smem), c, fin, loss_grad<false>(fin, ref), tile_off,
+                                              list, proj, wave_masks, exec_list, n_exec, grads, tile_sqerr, g, det, nullptr, sq);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -944,7 +967,7 @@ __global__ __launch_bounds__(256) void raster_forward_chunk_kernel(const uint32_
     if (__ballot(c.inside && !(T < kMinThroughput)) != 0ull && c.lane == 0) atomicOr(any_alive, 1u);
 }
 
-template <bool NEED_OP, bool HALF, bool DET, bool EXACT>
+template <bool NEED_OP, bool HALF, bool DET, bool EXACT, bool UPSTREAM = false>
 __global__ __launch_bounds__(256) void raster_backward_chunk_kernel(const uint32_t* __restrict__ tile_off,
                                                                     const uint32_t* __restrict__ list,
                                                                     const ProjRec* __restrict__ proj,
@@ -968,7 +991,7 @@ __global__ __launch_bounds__(256) void raster_backward_chunk_kernel(const uint32
     if (c.inside) {
         if (!first) st = state[pixel_index(c, g)];
         fin = load_pixel<HALF>(image0, pixel_index(c, g));    // finalColor, main.cpp:613: of ALL ranges
-        ref = load_pixel<HALF>(image_ref, pixel_index(c, g));
+        ref = load_ref_or_upstream<HALF, UPSTREAM>(image_ref, pixel_index(c, g));
     }
     uint32_t n_exec;
     {   // the executed entries of this range, from the state the backward walk starts from (colours discarded)
@@ -978,7 +1001,7 @@ __global__ __launch_bounds__(256) void raster_backward_chunk_kernel(const uint32
                                                   nullptr, crg, cb, &T);
     }
     __syncthreads(); // as in the fused kernel: LDS re-use, and the hand-over through global memory
-    backward_tile<false, NEED_OP, DET, EXACT, true>(*reinterpret_cast<BwdShared<DET>*>(smem), c, fin, ref, tile_off, list, proj,
+    backward_tile<false, NEED_OP, DET, EXACT, true, UPSTREAM>(*reinterpret_cast<BwdShared<DET>*>(smem), c, fin, loss_grad<UPSTREAM>(fin, ref), tile_off, list, proj,
                                                     wave_masks, exec_list, n_exec, grads, tile_sqerr, g, det, nullptr,
                                                     SqerrJob{nullptr, 0, nullptr, nullptr}, &st);
     if (c.inside) state[pixel_index(c, g)] = st;
@@ -1095,8 +1118,9 @@ hipError_t launch_raster(RasterPass pass, const RasterArgs& a, hipStream_t strea
     const DetSlots det{dg.rects, dg.offsets, dg.data, dg.stamp, dg.touched, dg.now};
     const int first = a.first ? 1 : 0, wi = a.write_image ? 1 : 0;
     const std::false_type no; // a flag the pass has no variants of
+    const std::true_type yes;
     hipError_t e = hipErrorInvalidValue;
-    switch (pass) {
+    if (a.upstream == nullptr) switch (pass) {
     case RasterPass::Forward:
         e = with_variant([&](auto exact, auto count, auto half) {
             hipLaunchKernelGGL((raster_forward_kernel<count, half, exact>), grid, block, 0, stream, a.tile_off, a.list, a.proj,
@@ -1132,6 +1156,23 @@ hipError_t launch_raster(RasterPass pass, const RasterArgs& a, hipStream_t strea
         }, a.exact_exp, no, a.half_images, a.need_opacity_grad, gather);
         break;
     }
+    // The walks from a caller's loss gradient (a.upstream, in the place of image_ref): the two backward kernels only --
+    // a fused launch has no image yet to have a gradient of -- and without pair counting.  Behind everything else on
+    // purpose: these instantiations come last, and the kernels above come out of the compiler as they did without them
+    // (DESIGN.md section 10).
+    else if (a.count) e = hipErrorInvalidValue;
+    else if (pass == RasterPass::Backward)
+        e = with_variant([&](auto exact, auto, auto half, auto op, auto d, auto up) {
+            hipLaunchKernelGGL((raster_backward_kernel<false, op, half, d, exact, up>), grid, block, 0, stream, a.tile_off, a.list,
+                               a.proj, a.image0, a.upstream, a.wave_masks, a.exec_list, a.tile_exec, a.grads, nullptr, a.g, det,
+                               a.status, a.iteration, nullptr);
+        }, a.exact_exp, no, a.half_images, a.need_opacity_grad, gather, yes);
+    else if (pass == RasterPass::BackwardRange)
+        e = with_variant([&](auto exact, auto, auto half, auto op, auto d, auto up) {
+            hipLaunchKernelGGL((raster_backward_chunk_kernel<op, half, d, exact, up>), grid, block, 0, stream, a.tile_off, a.list,
+                               a.proj, a.image0, a.upstream, a.state, first, a.wave_masks, a.exec_list, a.grads, nullptr, a.g, det,
+                               a.status, a.iteration);
+        }, a.exact_exp, no, a.half_images, a.need_opacity_grad, gather, yes);
     if (e != hipSuccess) return e;
     if (gather && dg.n > 0)
         hipLaunchKernelGGL(gather_grads_kernel, dim3((dg.n + 255) / 256), dim3(256), 0, stream, dg.offsets, dg.counts, dg.n,

@@ -1,0 +1,108 @@
+"""The rasteriser as a differentiable PyTorch operator: any loss written in torch on the rendered image.
+
+    pkg = importlib.import_module("2dgaussiansplatting_amd")
+    torch_op = importlib.import_module("2dgaussiansplatting_amd.torch_op")
+    with torch.cuda.stream(torch.cuda.Stream()):
+        r = torch_op.SplatRenderer(W, H, n)
+        splats = torch.nn.Parameter(...)          # (n, 9) float32: pos.xy, sx, sy, rot, color.rgb, opacity (main.cpp:85-93)
+        img = r.render(splats)                    # (rows, W, 4) float32, .w = 1
+        loss = (img[..., :3] - target).abs().sum()
+        loss.backward()                           # splats.grad: the hand-derived backward walk, from dL/d(img)
+
+Both directions are the library's HIP kernels (s2d_forward, s2d_backward_image_grads) on device pointers of torch's
+tensors: nothing crosses the host and nothing synchronises.  The library and torch touch the same buffers, so they work
+on ONE stream -- the one that is current when the renderer is created (as distributed.HipHaloOps documents); a call
+with another stream current raises.  What the library itself applies to the parameters inside its Adam step (clamps of
+the scales, colours and opacity, main.cpp:736-750) is NOT part of render(): a caller's optimiser keeps its parameters in
+range itself.
+
+This module imports torch; the package itself does not.
+"""
+import torch
+
+from . import Trainer
+
+__all__ = ["SplatRenderer"]
+
+
+class SplatRenderer:
+    """A `Trainer` (one GPU, or one row slab: row_begin / row_end in trainer_kw) used as a renderer with a backward pass.
+
+    The context needs a target to run (s2d_forward requires one, and s2d_backward on `trainer` still means the
+    reference's loss): the synthetic one is set here; `set_target` replaces it."""
+
+    def __init__(self, width, height, n_splats, **trainer_kw):
+        if "stream" in trainer_kw:
+            raise ValueError("SplatRenderer works on torch's current stream: make the stream current instead of passing it")
+        self.device = torch.device("cuda", int(trainer_kw.get("device", torch.cuda.current_device())))
+        self.stream = torch.cuda.current_stream(self.device).cuda_stream
+        if not self.stream:
+            # (a null stream handle in s2d_config means "create one", which torch's work would not be ordered with)
+            raise RuntimeError("SplatRenderer cannot share torch's default stream with the library: create it, and call it, "
+                               "under `with torch.cuda.stream(torch.cuda.Stream()):`")
+        trainer_kw.setdefault("device", self.device.index)
+        self.trainer = Trainer(width, height, n_splats, stream=self.stream, **trainer_kw)
+        self.n = self.trainer.n
+        self.rows, self.W = self.trainer.row_end - self.trainer.row_begin, self.trainer.W
+        # the gradient buffer the backward walk accumulates into: torch's memory, zero when bound
+        self.grads = torch.zeros((max(self.n, 1), 9), dtype=torch.float32, device=self.device)
+        self.trainer.bind_grads(self.grads.data_ptr())
+        self.trainer.set_target_synthetic()
+        self.generation = 0  # frames drawn so far: image0 and the forward walk's hand-over belong to the last one
+
+    def close(self):
+        self.trainer.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def set_target(self, rgba32f):
+        self.trainer.set_target(rgba32f)
+
+    def _check_stream(self):
+        if torch.cuda.current_stream(self.device).cuda_stream != self.stream:
+            raise RuntimeError("SplatRenderer was created on stream %#x and is called with another stream current: its "
+                               "kernels would not be ordered with torch's" % self.stream)
+
+    def _draw(self, splats):
+        """Forward pass of `splats`: afterwards image0 and the hand-over to the backward walk are theirs."""
+        self.trainer.set_splats_device(splats.data_ptr())
+        self.trainer.forward()
+        self.generation += 1
+
+    def render(self, splats):
+        """(n, 9) float32 contiguous tensor on the renderer's device -> the slab's rows of the image, (rows, W, 4), .w = 1;
+        differentiable with respect to `splats`."""
+        if not (isinstance(splats, torch.Tensor) and splats.dtype == torch.float32 and splats.device == self.device and
+                tuple(splats.shape) == (self.n, 9) and splats.is_contiguous()):
+            raise ValueError("render() takes a contiguous float32 tensor of shape (%d, 9) on %s" % (self.n, self.device))
+        return _Render.apply(splats, self)
+
+
+class _Render(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, splats, r):
+        r._check_stream()
+        r._draw(splats)
+        img = torch.empty((r.rows, r.W, 4), dtype=torch.float32, device=r.device)
+        r.trainer.get_image_rows_device(img.data_ptr())
+        ctx.renderer, ctx.generation = r, r.generation
+        ctx.save_for_backward(splats)
+        return img
+
+    @staticmethod
+    def backward(ctx, grad_image):
+        r = ctx.renderer
+        (splats,) = ctx.saved_tensors  # (torch raises here if they were modified in place since render())
+        r._check_stream()
+        if ctx.generation != r.generation:
+            # a later render() (or backward) drew another frame: the backward walk needs THIS call's framebuffer and
+            # executed entries, so draw its parameters again rather than differentiate the newer frame
+            r._draw(splats)
+        g = grad_image.to(torch.float32).contiguous()
+        r.grads.zero_()
+        r.trainer.backward_image_grads(g.data_ptr(), skip_opacity_grad=False)
+        return r.grads[:r.n].clone(), None

@@ -196,6 +196,22 @@ int s2d_backward(s2d_ctx* ctx, uint32_t flags);
 int s2d_forward_backward(s2d_ctx* ctx, uint32_t flags);
 int s2d_get_grads(s2d_ctx* ctx, s2d_splat* dsplats);
 
+/* ---- the rasteriser as a building block: any loss on image0, formed by the caller on the device (INTEGRATION.md
+ * section 5; torch_op.py wraps these three into a torch.autograd.Function) ---- */
+/* Backward pass (main.cpp:548-712) with dL/d(image0) supplied by the caller instead of image0 - imageRef (main.cpp:616):
+ * DEVICE pointer, (row_end - row_begin) * width RGBA32F, first row = row_begin, .w ignored, 16-byte aligned.
+ * Accumulates into the gradient buffer like s2d_backward; needs s2d_forward on the current parameters (S2D_E_STATE
+ * otherwise, also after a fused launch with S2D_FB_SKIP_IMAGE); S2D_E_INVALID for a S2D_CFG_COUNT_PAIRS context.
+ * flags: S2D_BWD_SKIP_OPACITY_GRAD.  Forms no squared error: the trace ring and s2d_get_mse keep what they had.
+ * The values are not checked: a non-finite one reaches the gradients, and the finite guard of the next s2d_adam_step
+ * judges the parameters as always. */
+int s2d_backward_image_grads(s2d_ctx* ctx, const float* dimage_rows_device, uint32_t flags);
+/* s2d_set_splats / s2d_get_image_rows with DEVICE pointers, queued on the context's stream, no host synchronisation.
+ * s2d_set_splats_device keeps the tile lists (the containment check rebuilds them when a splat left its binned
+ * rectangle) and the status word; the image buffer must be 16-byte aligned. */
+int s2d_set_splats_device(s2d_ctx* ctx, const float* splats_device);     /* n_splats * 9 floats */
+int s2d_get_image_rows_device(s2d_ctx* ctx, float* rgba32f_rows_device); /* always RGBA32F */
+
 /* Adam + constraints + finite guard, main.cpp:714-785, on the current gradient buffer; then iterations++ (809). */
 int s2d_adam_step(s2d_ctx* ctx, uint32_t flags);
 

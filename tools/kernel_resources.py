@@ -1,0 +1,121 @@
+"""Register / LDS / occupancy report of the raster kernels from the gfx950 cross-compile, and its comparison between two trees.
+
+    python tools/kernel_resources.py report [csrc_dir] > new.json     (no GPU needed: hipcc -Rpass-analysis=kernel-resource-usage)
+    python tools/kernel_resources.py compare old.json new.json
+    python tools/kernel_resources.py asm old_csrc_dir [new_csrc_dir]
+
+compare: every kernel instantiation of `old` must be in `new` with the same SGPRs, VGPRs, AGPRs, scratch, LDS and occupancy
+(exit status 1 otherwise); instantiations only `new` has are listed.  A kernel that gained a trailing template flag is
+matched with its `false` instantiation (`k<a, b>` of old == `k<a, b, false>` of new): adding a defaulted flag renames the
+symbol and must change nothing else.  The order in which variants are instantiated has moved the register allocation of
+unrelated kernels before (s2d_raster.hip, with_variant), which is what this is run for.
+asm: the device assembly (--offload-device-only -S) of every kernel of the old tree against the same kernel of the new one,
+comments dropped and local labels unnumbered: which are instruction for instruction the same (exit status 1 if one is not).
+"""
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FIELDS = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch",
+          "Occupancy [waves/SIMD]": "occupancy", "LDS Size [bytes/block]": "lds"}
+
+
+def _build_flags():
+    sys.path.insert(0, ROOT)
+    import importlib
+    build = importlib.import_module("2dgaussiansplatting_amd._build")
+    return build, [f for f in build.HIPCC_FLAGS if f not in ("-shared", "-pthread", "-ldl")]
+
+
+def _plain(names):
+    out = subprocess.run(["c++filt"], input="\n".join(names), check=True, stdout=subprocess.PIPE, universal_newlines=True).stdout
+    return [re.sub(r"\(.*$", "", p).replace("void ", "") for p in out.splitlines()]
+
+
+def assembly(csrc, source="s2d_raster.hip"):
+    """{kernel: its instructions as text} of one translation unit."""
+    build, flags = _build_flags()
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "out.s")
+        subprocess.run([build.hipcc()] + [f for f in flags if f != "-fPIC"] + ["-I", os.path.join(ROOT, "include"), "--offload-device-only",
+                        "-S", os.path.join(csrc, source), "-o", out], check=True, stderr=subprocess.DEVNULL)
+        text = open(out).read()
+    bodies = {}
+    for m in re.finditer(r"^(_ZN3s2d\w+):[^\n]*\n(.*?)^\.Lfunc_end\d+:", text, flags=re.S | re.M):
+        body = re.sub(r"\.L\w+", "L", re.sub(r";.*", "", m.group(2)))
+        bodies[m.group(1)] = body.replace(m.group(1), "SELF")
+    names = sorted(bodies)
+    return {p: bodies[n] for n, p in zip(names, _plain(names))}
+
+
+def compare_assembly(old, new):
+    same, changed = 0, []
+    for name, want in sorted(old.items()):
+        got = new.get(name, new.get(name[:-1] + ", false>") if name.endswith(">") else None)
+        if got == want:
+            same += 1
+        else:
+            changed.append(name)
+    print("%d of %d kernels of the old tree instruction for instruction the same (%d kernels in the new tree)" % (same, len(old), len(new)))
+    for n in changed:
+        print("  CHANGED: " + n)
+    return not changed
+
+
+def report(csrc, source="s2d_raster.hip"):
+    build, flags = _build_flags()
+    with tempfile.TemporaryDirectory() as tmp:
+        cmd = [build.hipcc()] + flags + ["-I", os.path.join(ROOT, "include"), "-c", os.path.join(csrc, source), "-o",
+                                         os.path.join(tmp, "out.o"), "-Rpass-analysis=kernel-resource-usage"]
+        text = subprocess.run(cmd, check=True, stderr=subprocess.PIPE, universal_newlines=True).stderr
+    kernels, cur = {}, None
+    for line in text.splitlines():
+        m = re.search(r"remark:\s+(.*?):\s+(\S+) \[-Rpass-analysis", line)
+        if not m:
+            continue
+        key, val = m.group(1).strip(), m.group(2)
+        if key == "Function Name":
+            cur = kernels.setdefault(val, {})
+        elif cur is not None and key in FIELDS:
+            cur[FIELDS[key]] = int(val)
+    names = sorted(kernels)
+    return {p: kernels[n] for n, p in zip(names, _plain(names))}
+
+
+def compare(old, new):
+    bad, matched = [], 0
+    for name, want in sorted(old.items()):
+        got = new.get(name)
+        if got is None and name.endswith(">"):
+            got = new.get(name[:-1] + ", false>")
+        if got is None:
+            bad.append("%s: gone" % name)
+        elif got != want:
+            bad.append("%s: %s -> %s" % (name, want, got))
+        else:
+            matched += 1
+    known = set(old) | {n[:-1] + ", false>" for n in old if n.endswith(">")}
+    added = sorted(n for n in new if n not in known)
+    print("%d of %d kernels of the old tree unchanged, %d new" % (matched, len(old), len(added)))
+    for n in added:
+        print("  new: %s %s" % (n, new[n]))
+    for b in bad:
+        print("  CHANGED: " + b)
+    return not bad
+
+
+if __name__ == "__main__":
+    if len(sys.argv) >= 2 and sys.argv[1] == "report":
+        csrc = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "2dgaussiansplatting_amd", "csrc")
+        json.dump(report(csrc), sys.stdout, indent=1, sort_keys=True)
+    elif len(sys.argv) == 4 and sys.argv[1] == "compare":
+        sys.exit(0 if compare(json.load(open(sys.argv[2])), json.load(open(sys.argv[3]))) else 1)
+    elif len(sys.argv) in (3, 4) and sys.argv[1] == "asm":
+        new = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "2dgaussiansplatting_amd", "csrc")
+        sys.exit(0 if compare_assembly(assembly(sys.argv[2]), assembly(new)) else 1)
+    else:
+        sys.exit(__doc__)
