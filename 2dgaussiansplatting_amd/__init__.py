@@ -32,6 +32,7 @@ S2D_CFG_DETERMINISTIC = 0x4
 S2D_CFG_EXACT_EXP = 0x8
 S2D_CFG_ADAM_FP32 = 0x10
 S2D_CFG_GENERIC_BINNING = 0x20
+S2D_CFG_REFERENCE_ORDER = 0x40
 S2D_BWD_SKIP_OPACITY_GRAD = 0x1
 S2D_FB_SKIP_IMAGE = 0x2
 STATUS_NAMES = {0: "S2D_OK", 1: "S2D_E_INVALID", 2: "S2D_E_HIP", 3: "S2D_E_NONFINITE", 4: "S2D_E_NOMEM",
@@ -287,7 +288,7 @@ class Trainer:
 
     def __init__(self, width, height, n_splats, device=0, row_begin=0, row_end=0, training_rate=0.0,
                  rebin_interval=0, rebin_margin=0.0, count_pairs=False, fp16_images=False, deterministic=False, exact_exp=False,
-                 adam_fp32=False, generic_binning=False, stream=None, chunk_pairs=None):
+                 adam_fp32=False, generic_binning=False, stream=None, chunk_pairs=None, reference_order=False):
         self.L = load_library()
         self.W, self.H, self.n = int(width), int(height), int(n_splats)
         cfg = _Config()
@@ -298,11 +299,14 @@ class Trainer:
         cfg.training_rate = float(training_rate)
         cfg.flags = ((S2D_CFG_COUNT_PAIRS if count_pairs else 0) | (S2D_CFG_FP16_IMAGES if fp16_images else 0) |
                      (S2D_CFG_DETERMINISTIC if deterministic else 0) | (S2D_CFG_EXACT_EXP if exact_exp else 0) |
-                     (S2D_CFG_ADAM_FP32 if adam_fp32 else 0) | (S2D_CFG_GENERIC_BINNING if generic_binning else 0))
+                     (S2D_CFG_ADAM_FP32 if adam_fp32 else 0) | (S2D_CFG_GENERIC_BINNING if generic_binning else 0) |
+                     (S2D_CFG_REFERENCE_ORDER if reference_order else 0))
         cfg.rebin_interval = int(rebin_interval)
         cfg.rebin_margin = float(rebin_margin)
         cfg.stream = stream
         self.stream = stream  # HIP stream handle the context works on; None: a stream the library owns
+        # reference_order: validation mode, gradients / optimiser state / MSE bytes-equal to the reference's
+        # (S2D_CFG_REFERENCE_ORDER, include/splat2d.h); slower and memory-hungry, results otherwise those of the reference
         h = C.c_void_p()
         # chunk_pairs (tests): the (tile, splat) pair budget beyond which a scene is rendered by index ranges of the splats;
         # the library reads S2D_CHUNK_PAIRS when the context is created (default 2^30)
@@ -522,7 +526,7 @@ class MultiTrainer:
     SCHEMES = {0: "none", 1: "ownership", 2: "replicated"}
 
     def __init__(self, width, height, n_splats, devices, share_gpu=False, training_rate=0.0, rebin_interval=0,
-                 fp16_images=False, deterministic=False, replicated=False):
+                 fp16_images=False, deterministic=False, replicated=False, reference_order=False):
         self.L = load_library()
         self.W, self.H, self.n = int(width), int(height), int(n_splats)
         cfg = _Config()
@@ -530,7 +534,8 @@ class MultiTrainer:
         cfg.width, cfg.height, cfg.n_splats = self.W, self.H, self.n
         cfg.training_rate = float(training_rate)
         cfg.rebin_interval = int(rebin_interval)
-        cfg.flags = (S2D_CFG_FP16_IMAGES if fp16_images else 0) | (S2D_CFG_DETERMINISTIC if deterministic else 0)
+        cfg.flags = ((S2D_CFG_FP16_IMAGES if fp16_images else 0) | (S2D_CFG_DETERMINISTIC if deterministic else 0) |
+                     (S2D_CFG_REFERENCE_ORDER if reference_order else 0))  # (refused: a single-context mode)
         devs = (C.c_int32 * len(devices))(*devices)
         h = C.c_void_p()
         rc = self.L.s2d_multi_create(C.byref(cfg), devs, len(devices), (1 if share_gpu else 0) | (2 if replicated else 0), C.byref(h))

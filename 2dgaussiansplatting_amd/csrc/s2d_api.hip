@@ -61,6 +61,13 @@ struct s2d_ctx {
     DevBuf<uint32_t> d_det_stamp;               // [pair capacity]
     DevBuf<uint32_t> d_det_touched;             // [n]: which of a splat's slots the current pass wrote (zero between passes)
     uint32_t det_epoch = 0;                     // stamps written so far (monotone; 0 = never)
+    // S2D_CFG_REFERENCE_ORDER: every backward pass stores its per-pixel terms and adds them in the reference's order
+    // (s2d_raster.hip, reference_*_kernel).  Slots and stamps are deterministic mode's (d_det_stamp, det_epoch), which this
+    // mode replaces: `deterministic` is false in such a context.
+    bool ref_order = false;
+    uint64_t ref_max_bytes = 32ull << 30;       // S2D_REFERENCE_ORDER_MAX_BYTES overrides: bound on d_ref_terms
+    DevBuf<float> d_ref_terms;                  // [pair capacity][kRefTermsStride]
+    DevBuf<float> d_pixel_sqerr;                // [pixels of the slab]
     // Index-range ("chunked") rendering: when the (tile, splat) pairs of a scene exceed chunk_pairs -- at the latest 2^32 - 65536,
     // what 32-bit list positions can address -- the splats are cut into consecutive index ranges of at most that many
     // pairs, and the lists of one range at a time are built and walked front to back (chunked_forward / chunked_backward)
@@ -167,15 +174,29 @@ int ensure_pair_capacity(s2d_ctx* c, uint64_t need)
     if (need >= 0xFFFF0000ull) return fail(c, S2D_E_NOMEM, "tile lists need %llu pairs (> 2^32)", (unsigned long long)need);
     uint64_t cap = std::max<uint64_t>(need + need / 4 + 4096, 1 << 16);
     if (cap > 0xFFFF0000ull) cap = 0xFFFF0000ull;
+    if (c->ref_order) { // refused before anything is released or launched
+        const uint64_t per_slot = (uint64_t)kRefTermsStride * sizeof(float);
+        if (cap * per_slot > c->ref_max_bytes) cap = std::max<uint64_t>(need, 1 << 16); // no headroom rather than no context
+        if (cap * per_slot > c->ref_max_bytes)
+            return fail(c, S2D_E_NOMEM, "the term scratch of S2D_CFG_REFERENCE_ORDER needs %llu bytes for %llu (tile, splat) pairs, "
+                        "S2D_REFERENCE_ORDER_MAX_BYTES allows %llu", (unsigned long long)(cap * per_slot), (unsigned long long)cap,
+                        (unsigned long long)c->ref_max_bytes);
+    }
     S2D_HIP(c, hipStreamSynchronize(c->stream));
     c->lists.release_pairs();
     c->d_wave_masks.release(), c->d_exec_list.release(), c->d_det_data.release(), c->d_det_stamp.release();
+    c->d_ref_terms.release();
     S2D_HIP(c, c->lists.alloc_pairs(cap));
     const auto hand_over = [&]() -> int {
         S2D_HIP(c, c->d_wave_masks.alloc((size_t)cap * 4));
         S2D_HIP(c, c->d_exec_list.alloc((size_t)cap));
         if (c->deterministic) {
             S2D_HIP(c, c->d_det_data.alloc((size_t)cap * kDetStride));
+            S2D_HIP(c, c->d_det_stamp.alloc((size_t)cap));
+            S2D_HIP(c, hipMemsetAsync(c->d_det_stamp, 0, (size_t)cap * sizeof(uint32_t), c->stream));
+        }
+        if (c->ref_order) {
+            S2D_HIP(c, c->d_ref_terms.alloc((size_t)cap * kRefTermsStride));
             S2D_HIP(c, c->d_det_stamp.alloc((size_t)cap));
             S2D_HIP(c, hipMemsetAsync(c->d_det_stamp, 0, (size_t)cap * sizeof(uint32_t), c->stream));
         }
@@ -337,7 +358,10 @@ int launch_job(s2d_ctx* c, bool optimistic, const RasterJob& job)
         a.write_image = job.write_image;
         a.sq = sqerr_job(c, job.sum_sqerr ? c->iterations % c->trace_cap : -1);
     }
-    S2D_HIP(c, launch_raster(job.fused ? RasterPass::Fused : RasterPass::Forward, a, c->stream));
+    if (c->ref_order && a.exact_exp) // (never fused: queue_forward_backward)
+        S2D_HIP(c, launch_reference_forward_exact(a, c->stream));
+    else
+        S2D_HIP(c, launch_raster(job.fused ? RasterPass::Fused : RasterPass::Forward, a, c->stream));
     return S2D_OK;
 }
 
@@ -472,6 +496,9 @@ int queue_raster(s2d_ctx* c, const RasterJob& job)
         if (need_ranges && (c->cfg.flags & S2D_CFG_COUNT_PAIRS))
             return fail(c, S2D_E_NOMEM, "pair counting (S2D_CFG_COUNT_PAIRS) is not available for scenes beyond %llu (tile, splat) pairs",
                         (unsigned long long)c->chunk_pairs);
+        if (need_ranges && c->ref_order)
+            return fail(c, S2D_E_NOMEM, "reference order (S2D_CFG_REFERENCE_ORDER) is not available for scenes beyond %llu (tile, splat) pairs",
+                        (unsigned long long)c->chunk_pairs);
         c->proj_fresh = true;
         c->check_seq++; // the new lists cover the current parameters: a stamp that asked for them matches nothing now
         if (need_ranges) {
@@ -511,12 +538,35 @@ int queue_sqerr(s2d_ctx* c, bool defer = false)
     return defer && (c->n + 255) / 256 >= kSqerrChunks ? S2D_OK : flush_sqerr(c);
 }
 
+// S2D_CFG_REFERENCE_ORDER: terms into their slots, the ordered sums into the gradient buffer, and the squared error as one
+// ordered chain straight into the ring slot -- nothing is deferred to the Adam launch.  (Such a context never renders by
+// index ranges: queue_raster refuses the scene.)
+int queue_backward_reference(s2d_ctx* c, bool need_opacity_grad, const float4* upstream)
+{
+    RasterArgs a = raster_args(c);
+    a.upstream = upstream;
+    a.need_opacity_grad = need_opacity_grad;
+    RefOrder ro;
+    ro.splats = c->d_splats; ro.rects = c->d_rects; ro.offsets = c->d_offsets; ro.counts = c->d_counts; ro.n = c->n;
+    ro.terms = c->d_ref_terms; ro.stamp = c->d_det_stamp; ro.capacity = (uint32_t)c->lists.capacity(); ro.now = ++c->det_epoch;
+    ro.pixel_sqerr = c->d_pixel_sqerr;
+    S2D_HIP(c, launch_reference_backward(a, ro, c->stream));
+    c->have_backward = true;
+    if (upstream) return S2D_OK;
+    c->last_sqerr_slot = c->iterations % c->trace_cap;
+    c->sqerr_deferred = false;
+    S2D_HIP(c, launch_reference_sqerr(c->d_pixel_sqerr, (size_t)c->g.W * (size_t)(c->g.row_end - c->g.row_begin), c->d_sqerr_trace + c->last_sqerr_slot, c->d_status,
+                                      c->iterations, c->stream));
+    return S2D_OK;
+}
+
 // upstream != nullptr (s2d_backward_image_grads): the walk starts from the caller's dL/d(image0) instead of
 // image0 - imageRef.  The loss is the caller's, so no squared error is formed or queued: the trace ring, last_sqerr_slot
 // and a reduction still deferred to the next Adam launch stay as the last s2d_backward left them.
 int queue_backward(s2d_ctx* c, bool need_opacity_grad, const float4* upstream = nullptr)
 {
     if (!c->have_forward) return fail(c, S2D_E_STATE, "the backward pass needs s2d_forward on the current parameters");
+    if (c->ref_order) return queue_backward_reference(c, need_opacity_grad, upstream);
     if (!c->chunks.empty()) { // the forward pass went over index ranges: so does this one
         if (int rc = chunked_backward(c, need_opacity_grad, upstream)) return rc;
     } else {
@@ -536,7 +586,7 @@ int queue_backward(s2d_ctx* c, bool need_opacity_grad, const float4* upstream = 
 // property of the separate kernels only, so a counting context takes those.
 int queue_forward_backward(s2d_ctx* c, bool need_opacity_grad, bool write_image, bool defer_sqerr = true)
 {
-    if (c->cfg.flags & S2D_CFG_COUNT_PAIRS) {
+    if ((c->cfg.flags & S2D_CFG_COUNT_PAIRS) || c->ref_order) { // (reference order: its backward pass is a launch of its own)
         if (int rc = queue_forward(c)) return rc;
         return queue_backward(c, need_opacity_grad);
     }
@@ -650,7 +700,8 @@ int s2d_create(const s2d_config* cfg, s2d_ctx** out)
     int rb = cfg->row_begin, re = cfg->row_end;
     if (rb == 0 && re == 0) re = cfg->height;
     if (rb < 0 || re > cfg->height || rb >= re || (rb % kTile) != 0) return S2D_E_INVALID;
-    if ((cfg->flags & S2D_CFG_EXACT_EXP) && (cfg->flags & (S2D_CFG_COUNT_PAIRS | S2D_CFG_FP16_IMAGES))) return S2D_E_INVALID;
+    if ((cfg->flags & (S2D_CFG_EXACT_EXP | S2D_CFG_REFERENCE_ORDER)) && (cfg->flags & (S2D_CFG_COUNT_PAIRS | S2D_CFG_FP16_IMAGES)))
+        return S2D_E_INVALID;
 
     s2d_ctx* c = new (std::nothrow) s2d_ctx();
     if (!c) return S2D_E_NOMEM;
@@ -701,7 +752,15 @@ int s2d_create(const s2d_config* cfg, s2d_ctx** out)
         const unsigned long long v = strtoull(e, nullptr, 10);
         if (v > 0) c->chunk_pairs = std::min<unsigned long long>(v, 0xFFFF0000ull - 1);
     }
-    c->deterministic = (cfg->flags & S2D_CFG_DETERMINISTIC) != 0;
+    c->ref_order = (cfg->flags & S2D_CFG_REFERENCE_ORDER) != 0;
+    if (c->ref_order) {
+        if (const char* e = getenv("S2D_REFERENCE_ORDER_MAX_BYTES")) {
+            const unsigned long long v = strtoull(e, nullptr, 10);
+            if (v > 0) c->ref_max_bytes = v;
+        }
+        S2D_HIP(c, c->d_pixel_sqerr.alloc(px));
+    }
+    c->deterministic = (cfg->flags & S2D_CFG_DETERMINISTIC) != 0 && !c->ref_order; // (reference order alone decides the result)
     if (c->deterministic) {
         S2D_HIP(c, c->d_det_touched.alloc(n));
         S2D_HIP(c, hipMemset(c->d_det_touched, 0, n * sizeof(uint32_t)));
@@ -1037,6 +1096,8 @@ int s2d_halo_masks(s2d_ctx* c, int32_t world, const int32_t* row_bounds, float m
 int s2d_halo_commit(s2d_ctx* c, const uint32_t* masks_device, int32_t rank, int32_t added)
 {
     if (!c || rank < 0 || rank > 31) return S2D_E_INVALID;
+    if (masks_device && c->ref_order)
+        return fail(c, S2D_E_INVALID, "reference order (S2D_CFG_REFERENCE_ORDER) has no slab ownership: the chains run over all splats");
     if (int rc = use_device(c)) return rc;
     if (int rc = compact_off(c)) return rc;
     if (!masks_device) { // back to holding every splat (the caller has made this context's copy complete again)

@@ -246,6 +246,32 @@ struct RasterArgs {
     bool need_opacity_grad = false;
 };
 hipError_t launch_raster(RasterPass pass, const RasterArgs& a, hipStream_t stream);
+// Reference-order backward pass (S2D_CFG_REFERENCE_ORDER; s2d_raster.hip, behind everything else).  The walk stores the
+// nine addends of every (executed pair, pixel of its tile) into the pair's slot -- the slot numbering of deterministic
+// mode: offsets[splat] + position of the tile in the splat's binned rectangle, stamped with `now` -- and, unless the loss
+// is the caller's (a.upstream), the pixel's squared error; the sum kernel then adds each splat's terms to a.grads in
+// the order of main.cpp:576-598.
+constexpr int kRefTermsStride = 9 * kTile * kTile; // floats per slot: [component][pixel row of the tile][column]
+struct RefOrder {
+    const float* splats = nullptr;    // n x 9: the raw scales are not in ProjRec
+    const TileRect* rects = nullptr;
+    const uint32_t* offsets = nullptr;
+    const uint32_t* counts = nullptr;
+    int n = 0;
+    float* terms = nullptr;           // [pair capacity][kRefTermsStride]
+    uint32_t* stamp = nullptr;        // [pair capacity]: `now` of the last pass that wrote the slot
+    uint32_t capacity = 0;            // slots allocated (no kernel touches a slot beyond)
+    uint32_t now = 0;                 // never 0 (0 marks a slot that was never written)
+    float* pixel_sqerr = nullptr;     // [pixels of the slab]: lengthSquared(d * 255) of main.cpp:801-802, as float
+};
+// uses of `a`: tile_off, exec_list, wave_masks, tile_exec, proj, image0, image_ref / upstream, grads, g, status, iteration,
+// exact_exp, need_opacity_grad (false: the opacity component of a.grads is left as it is)
+hipError_t launch_reference_backward(const RasterArgs& a, const RefOrder& ro, hipStream_t stream);
+// RasterPass::Forward for such a context with exact_exp: expf with the bits of the oracle's libm (s2d_math.h expf_ref)
+hipError_t launch_reference_forward_exact(const RasterArgs& a, hipStream_t stream);
+// *out = the slab's squared error as main.cpp:796-805 adds it: one double chain over pixel_sqerr[0 .. pixels), in order
+hipError_t launch_reference_sqerr(const float* pixel_sqerr, size_t pixels, double* out, const DeviceStatus* status, int iteration,
+                                  hipStream_t stream);
 // slab ownership (s2d_halo.hip): `held` == nullptr means every splat is held (single rank, or replicated state)
 hipError_t launch_halo_masks(const float* splats, const uint8_t* held, int n, int world, const int* row_bounds, float margin,
                              uint32_t* masks, hipStream_t stream);

@@ -155,6 +155,42 @@ S2D_HD float gauss_pow8(float d2, bool* nonzero)
     return x;
 }
 
+// expf as the oracle's libm evaluates it (main.cpp:51 with the switch on; glibc 2.35 on x86-64: the "expf" of the ARM
+// optimized routines -- x*32/ln2 = k + r, 2^(k/32) from a 32-entry table, a cubic in r, all in double, rounded to float
+// once -- compiled with FMA contraction).  A restatement of that published algorithm with the contractions written out,
+// like sincos_f32 above; it returns the same bits as this container's libm for 2.6e8 arguments spread over [-104.5, 89.5]
+// (every 7th / 11th float), 0 mismatches.  S2D_CFG_REFERENCE_ORDER with S2D_CFG_EXACT_EXP uses it in both walks: the
+// device library's own expf is accurate to 1 ulp, not equal to libm's.
+S2D_HD float expf_ref(float x)
+{
+    const uint64_t tab[32] = {
+        0x3ff0000000000000ull, 0x3fefd9b0d3158574ull, 0x3fefb5586cf9890full, 0x3fef9301d0125b51ull, 0x3fef72b83c7d517bull,
+        0x3fef54873168b9aaull, 0x3fef387a6e756238ull, 0x3fef1e9df51fdee1ull, 0x3fef06fe0a31b715ull, 0x3feef1a7373aa9cbull,
+        0x3feedea64c123422ull, 0x3feece086061892dull, 0x3feebfdad5362a27ull, 0x3feeb42b569d4f82ull, 0x3feeab07dd485429ull,
+        0x3feea47eb03a5585ull, 0x3feea09e667f3bcdull, 0x3fee9f75e8ec5f74ull, 0x3feea11473eb0187ull, 0x3feea589994cce13ull,
+        0x3feeace5422aa0dbull, 0x3feeb737b0cdc5e5ull, 0x3feec49182a3f090ull, 0x3feed503b23e255dull, 0x3feee89f995ad3adull,
+        0x3feeff76f2fb5e47ull, 0x3fef199bdd85529cull, 0x3fef3720dcef9069ull, 0x3fef5818dcfba487ull, 0x3fef7c97337b9b5full,
+        0x3fefa4afa2a490daull, 0x3fefd0765b6e4540ull};
+    const double inv_ln2_n = 0x1.71547652b82fep+0 * 32, shift = 0x1.8p+52;
+    const double c0 = 0x1.c6af84b912394p-5 / 32 / 32 / 32, c1 = 0x1.ebfce50fac4f3p-3 / 32 / 32, c2 = 0x1.62e42ff0c52d6p-1 / 32;
+    const uint32_t top = abstop12(x);
+    if (top >= abstop12(88.0f)) {
+        if (f32_bits(x) == 0xff800000u) return 0.0f;      // -inf
+        if (top >= abstop12(INFINITY)) return x + x;      // +inf, NaN
+        if (x > 0x1.62e42ep6f) return INFINITY;           // overflow
+        if (x < -0x1.9fe368p6f) return 0.0f;              // underflow
+    }
+    union { double f; uint64_t u; } kd, s;
+    const double z = inv_ln2_n * (double)x;
+    kd.f = z + shift;                                     // round to nearest integer: k in the low bits
+    const uint64_t ki = kd.u;
+    const double r = z - (kd.f - shift);
+    s.u = tab[ki % 32] + (ki << (52 - 5));                // 2^(k/32)
+    const double p = ::fma(c0, r, c1);
+    const double y = ::fma(p, r * r, ::fma(c2, r, 1.0));
+    return (float)(y * s.f);
+}
+
 // C float -> int conversion as the reference's x86-64 build performs it (cvttss2si): truncation
 // toward zero, and the "integer indefinite" value INT_MIN for NaN / out-of-range inputs.
 S2D_HD int cvt_trunc(float f)
@@ -269,6 +305,72 @@ S2D_HD float gauss_at(float px, float py, float pos_x, float pos_y, float a, flo
     *vx_out = vx;
     *vy_out = vy;
     return gauss_from_d2(d2);
+}
+
+// ----------------------------------------------------------------------------------------------
+// The backward loop body of one (splat, pixel), main.cpp:601-709, with the reference's own expressions and association
+// (S2D_CFG_REFERENCE_ORDER; the fast path regroups some of them, s2d_raster.hip backward_tile).  Every `/` is one IEEE
+// division; glm::dot(vec3, vec3) is (x + y) + z.
+// ----------------------------------------------------------------------------------------------
+struct RefSplat { // what the body reads of the splat: inv_cov (main.cpp:561-565; b = [1][0], c = [0][1]), cov_of's trig, raw scales
+    float a, b, c, d;
+    float cosT, sinT, sx, sy;
+    float col_r, col_g, col_b, opacity;
+};
+
+struct RefPixel { // image1(x, y), main.cpp:601: running colour and throughput
+    float r, g, b, T;
+};
+
+// d2 = dot(v, inv_cov * v), main.cpp:607-609, as gauss_at forms it
+S2D_HD float quad_form_at(float px, float py, float pos_x, float pos_y, const RefSplat& s, float* vx_out, float* vy_out)
+{
+    float vx = px - pos_x;
+    float vy = py - pos_y;
+    float mx = s.a * vx + s.b * vy;
+    float my = s.c * vx + s.d * vy;
+    *vx_out = vx;
+    *vy_out = vy;
+    return vx * mx + vy * my;
+}
+
+// main.cpp:611-707 for a pixel that passed the throughput test (:604), from G (:610) and v (:608): advances `px` and writes
+// the nine addends of dSplats[i] in record order (pos.x, pos.y, sx, sy, rot, color.rgb, opacity).  fin = image0(x, y);
+// dL = dL_dC (:616).
+S2D_HD void reference_terms(const RefSplat& s, float G, float vx, float vy, RefPixel& px, float fin_r, float fin_g,
+                            float fin_b, float dL_r, float dL_g, float dL_b, float* t)
+{
+    float T = px.T;
+    float alpha = G * s.opacity;                          // :611
+    float dC_dc = alpha * T;                              // :618
+    t[5] = dL_r * dC_dc;                                  // :619
+    t[6] = dL_g * dC_dc;
+    t[7] = dL_b * dC_dc;
+    px.r += T * s.col_r * alpha;                          // :623-625
+    px.g += T * s.col_g * alpha;
+    px.b += T * s.col_b * alpha;
+    float Sx = fin_r - px.r, Sy = fin_g - px.g, Sz = fin_b - px.b; // :627
+    float den = 1.0f - alpha + 1.0e-15f;
+    float dL_dalpha_x = dL_r * (s.col_r * T - Sx / den);  // :628-629
+    float dL_dalpha_y = dL_g * (s.col_g * T - Sy / den);
+    float dL_dalpha_z = dL_b * (s.col_b * T - Sz / den);
+    float dL_dalpha_rgb = dL_dalpha_x + dL_dalpha_y + dL_dalpha_z; // :630
+    float dalpha_dx = 0.5f * alpha * (2.0f * s.a * vx + (s.b + s.c) * vy); // :639
+    float dalpha_dy = 0.5f * alpha * (2.0f * s.d * vy + (s.b + s.c) * vx); // :640
+    t[0] = dL_dalpha_rgb * dalpha_dx;                     // :654-655
+    t[1] = dL_dalpha_rgb * dalpha_dy;
+    float vxx = vx * vx, vxy = vx * vy, vyy = vy * vy;
+    float dalpha_dsx = alpha / (s.sx * s.sx * s.sx) *     // :657-659
+                       (((s.cosT * s.cosT) * vxx + (2.0f * s.sinT * s.cosT) * vxy) + (s.sinT * s.sinT) * vyy);
+    float dalpha_dsy = alpha / (s.sy * s.sy * s.sy) *     // :660-662
+                       (((s.sinT * s.sinT) * vxx + (-2.0f * s.sinT * s.cosT) * vxy) + (s.cosT * s.cosT) * vyy);
+    t[2] = dL_dalpha_rgb * dalpha_dsx;                    // :677-678
+    t[3] = dL_dalpha_rgb * dalpha_dsy;
+    float dalpha_dtheta = alpha * (s.sx * s.sx - s.sy * s.sy) / (s.sx * s.sx * s.sy * s.sy) * // :680-683
+                          ((s.cosT * s.cosT - s.sinT * s.sinT) * vx * vy - s.sinT * s.cosT * (vx * vx - vy * vy));
+    t[4] = (dL_dalpha_x + dL_dalpha_y + dL_dalpha_z) * dalpha_dtheta; // :685
+    t[8] = dL_dalpha_rgb * G;                             // :703-704
+    px.T = T * (1.0f - alpha);                            // :707
 }
 
 // ----------------------------------------------------------------------------------------------

@@ -1039,6 +1039,7 @@ int s2d_multi_create(const s2d_config* cfg, const int32_t* devices, int32_t n_de
     if (!cfg || !out || !devices || n_devices < 1 || n_devices > 32 || cfg->struct_size != sizeof(s2d_config)) return S2D_E_INVALID;
     *out = nullptr;
     if (cfg->row_begin != 0 || cfg->row_end != 0 || cfg->stream != nullptr) return S2D_E_INVALID; // the handle cuts the slabs itself
+    if (cfg->flags & S2D_CFG_REFERENCE_ORDER) return S2D_E_INVALID; // one device's validation mode: its chains run over all splats
     DeviceGuard guard;
     s2d_multi* m = new (std::nothrow) s2d_multi();
     if (!m) return S2D_E_NOMEM;

@@ -51,6 +51,7 @@ struct Options {
     int rebin_interval = 0;
     float lr = 0.0f;            // --lr: trainingRate, main.cpp:715 (0 = the reference's 0.05)
     bool deterministic = false; // --deterministic: bitwise reproducible gradient sums (S2D_CFG_DETERMINISTIC)
+    bool reference_order = false; // --reference-order: gradients, state and trace bytes-equal to the reference's (S2D_CFG_REFERENCE_ORDER)
     int stall_ms = -1;          // --stall-timeout-ms (multi-device handle): how long a rank may not answer before the step fails
     int gpus = 1;               // --gpus N: devices device .. device + N - 1, one row slab each, RCCL all-reduce of the gradients
     bool share_gpu = false;     // --share-gpu: all N ranks on --device (rehearsal on a box with fewer GPUs than ranks)
@@ -74,7 +75,7 @@ int usage()
                  "                     [--overlay file [--overlay-scale S] [--overlay-stride K] [--overlay-vertices file]]\n"
                  "       splat2d_train --convert in.(s2di|ppm|png|jpg) out.(s2di|ppm|png)\n"
                  "                     [--load-checkpoint file] [--save-checkpoint file]\n"
-                 "                     [--lr RATE] [--deterministic] [--device D] [--gpus N [--exchange halo|dense] [--share-gpu]\n"
+                 "                     [--lr RATE] [--deterministic] [--reference-order] [--device D] [--gpus N [--exchange halo|dense] [--share-gpu]\n"
                  "                     [--stall-timeout-ms MS]] [--rebin-interval R] [--quiet]\n");
     return 2;
 }
@@ -97,6 +98,7 @@ struct Session {
         cfg.rebin_interval = o.rebin_interval;
         cfg.training_rate = o.lr;
         if (o.deterministic) cfg.flags |= S2D_CFG_DETERMINISTIC;
+        if (o.reference_order) cfg.flags |= S2D_CFG_REFERENCE_ORDER;
         is_multi = o.gpus > 1 || std::getenv("S2D_TRAIN_FORCE_MULTI"); // (the variable sends --gpus 1 through the handle)
         if (!is_multi) {
             cfg.device = o.device;
@@ -200,6 +202,7 @@ int main(int argc, char** argv)
         else if (a == "--quiet") o.quiet = true;
         else if (a == "--lr") o.lr = (float)std::atof(next("--lr"));
         else if (a == "--deterministic") o.deterministic = true;
+        else if (a == "--reference-order") o.reference_order = true;
         else if (a == "--stall-timeout-ms") o.stall_ms = std::atoi(next("--stall-timeout-ms"));
         else return usage();
     }

@@ -29,7 +29,11 @@ class SplatRenderer:
     """A `Trainer` (one GPU, or one row slab: row_begin / row_end in trainer_kw) used as a renderer with a backward pass.
 
     The context needs a target to run (s2d_forward requires one, and s2d_backward on `trainer` still means the
-    reference's loss): the synthetic one is set here; `set_target` replaces it."""
+    reference's loss): the synthetic one is set here; `set_target` replaces it.
+
+    reference_order=True (passed through to the Trainer like every other keyword): the backward walk adds each splat's
+    terms in the reference's own order (S2D_CFG_REFERENCE_ORDER), so `splats.grad` is what the reference's loops would
+    accumulate from the same dL/d(img), bit for bit -- a validation mode, slower and memory-hungry."""
 
     def __init__(self, width, height, n_splats, **trainer_kw):
         if "stream" in trainer_kw:

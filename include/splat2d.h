@@ -110,6 +110,18 @@ typedef enum s2d_status {
 #define S2D_CFG_GENERIC_BINNING 0x20u /* diagnostic: build the tile lists with the generic builder (all (tile, splat) pairs
                                     * radix-sorted by tile) even where the two-level one applies (images of up to 512 tile
                                     * columns, csrc/s2d_tilelists.hip).  Same lists either way; wider images always use it. */
+#define S2D_CFG_REFERENCE_ORDER 0x40u /* validation mode: dSplats, the updated splats / splatAdams and the MSE come out
+                                    * bytes-equal to the reference's.  Every backward pass (s2d_backward, s2d_forward_backward,
+                                    * s2d_step, s2d_backward_image_grads) evaluates the nine addends of each (splat, pixel)
+                                    * with the reference's own expressions (main.cpp:618-704), stores them per (tile, splat)
+                                    * pair, and adds each splat's in ONE fp32 chain in the order of main.cpp:576-598 (pixel
+                                    * rows ascending, columns ascending); the squared error is the row-major double chain of
+                                    * main.cpp:796-805.  Only speed and memory differ from the reference: 9 KiB of scratch
+                                    * per pair of capacity, at most S2D_REFERENCE_ORDER_MAX_BYTES (environment, read at
+                                    * s2d_create; default 32 GiB), S2D_E_NOMEM beyond.  With S2D_CFG_DETERMINISTIC the
+                                    * result is that of this flag alone.  Not combinable with S2D_CFG_COUNT_PAIRS /
+                                    * S2D_CFG_FP16_IMAGES, s2d_multi_create or slab ownership (s2d_halo_commit with masks):
+                                    * S2D_E_INVALID; no index-range rendering (see s2d_forward). */
 
 typedef struct s2d_config {
     uint32_t struct_size;   /* = sizeof(s2d_config) */
@@ -179,7 +191,8 @@ int s2d_get_adam(s2d_ctx* ctx, s2d_splat_adam* adams, float* beta1t, float* beta
  * with 32 bits, and a scene with more of them than S2D_CHUNK_PAIRS (environment, read at s2d_create; default 2^30) is
  * rendered by consecutive INDEX RANGES of the splats -- the lists of one range at a time, front to back like main.cpp:419
  * and :552, the per-pixel colour and throughput carried from range to range -- with the same bits as one set of lists
- * (forward, backward and s2d_step alike; only S2D_CFG_COUNT_PAIRS contexts answer S2D_E_NOMEM there). */
+ * (forward, backward and s2d_step alike; only S2D_CFG_COUNT_PAIRS and S2D_CFG_REFERENCE_ORDER contexts answer S2D_E_NOMEM
+ * there, the latter because its term scratch is addressed by the pairs of one set of lists). */
 int s2d_forward(s2d_ctx* ctx);
 /* image0 as uploaded at main.cpp:794: width*height RGBA32F, .w = 1.  Rows outside the slab are returned as 0. */
 int s2d_get_image(s2d_ctx* ctx, float* rgba32f);

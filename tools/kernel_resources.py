@@ -47,6 +47,7 @@ def assembly(csrc, source="s2d_raster.hip"):
     bodies = {}
     for m in re.finditer(r"^(_ZN3s2d\w+):[^\n]*\n(.*?)^\.Lfunc_end\d+:", text, flags=re.S | re.M):
         body = re.sub(r"\.L\w+", "L", re.sub(r";.*", "", m.group(2)))
+        body = re.sub(r"[ \t]+$", "", body, flags=re.M)  # (the padding in front of a dropped comment depends on the label's digits)
         bodies[m.group(1)] = body.replace(m.group(1), "SELF")
     names = sorted(bodies)
     return {p: bodies[n] for n, p in zip(names, _plain(names))}
