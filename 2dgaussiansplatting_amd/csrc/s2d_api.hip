@@ -25,6 +25,7 @@
 #include "s2d_device.h"
 #include "s2d_lists.h"
 #include "s2d_owned.h"
+#include "s2d_state.h"
 
 using namespace s2d;
 
@@ -37,11 +38,8 @@ struct s2d_ctx {
     bool own_stream = false;
     float lr = 0.05f;
 
-    // parameters / optimiser state / gradients (AoS, the reference's layouts)
-    DevBuf<float> d_splats;      // n * 9
-    DevBuf<float> d_adams;       // n * 18
-    DevBuf<uint8_t> d_dormant;   // n: 1 = all of the splat's Adam moments are zero (adam_kernel keeps it; cleared with every outside write)
-    DevBuf<float> d_grads_own;
+    SplatState state;            // parameters, optimiser state, the held set of slab ownership (s2d_state.h)
+    DevBuf<float> d_grads_own;   // gradients (AoS, the reference's layout)
     float* d_grads = nullptr;    // buffer in use (own or bound)
     // projection + binning
     DevBuf<ProjRec> d_proj;
@@ -93,29 +91,11 @@ struct s2d_ctx {
     DevBuf<uint8_t> d_ref;
     bool half_images = false;
     size_t pixel_bytes = sizeof(float4);
-    DevBuf<double> d_tile_sqerr;
-    DevBuf<uint32_t> d_held_ids;      // ... and their ascending id list, *d_held_count long, for the Adam kernel
-    DevBuf<uint32_t> d_held_count;
-    DevBuf<uint32_t> d_held_work;     // n words of scan workspace
-    // Compact held state: with slab ownership the Adam step touches only the splats the rank holds -- a seventh of them at
-    // eight ranks, scattered through the id-indexed arrays (36- and 72-byte records, a cache line or two each).  Their
-    // parameters and moments are therefore kept in compact arrays in the order of d_held_ids, which the Adam kernel reads
-    // and writes in whole lines; the id-indexed arrays are brought up to date (compact_flush) before anything else reads
-    // them -- a projection pass, a hold-set refresh, a row transfer, a read-back -- and the compact copy is made afresh
-    // (compact_load) whenever the held set or the id-indexed arrays change from outside.
-    DevBuf<float> d_csplats;     // n * 9 (capacity: every splat)
-    DevBuf<float> d_cadams;      // n * 18
-    bool compact_live = false;   // the compact arrays mirror the held splats
-    bool compact_dirty = false;  // ... and are ahead of the id-indexed arrays (Adam steps since the last flush)
-    bool compact_enabled = true; // S2D_COMPACT_HELD=0 turns it off (A/B)
-    DevBuf<uint8_t> d_held;      // slab ownership: 1 = this rank holds (updates) the splat; nullptr = all (s2d_halo_commit)
-    DevBuf<double> d_sqerr_trace;
-    int trace_cap = 1 << 16;
+    SqerrTrace trace;          // the tile errors of a backward pass and the ring of per-iteration sums (s2d_state.h)
     DevBuf<DeviceStatus> d_status;
     DevBuf<PairCounters> d_counters;
     // pinned host mirrors
     HostBuf<DeviceStatus> h_status;
-    HostBuf<double> h_trace;            // kHostTrace squared errors: s2d_step reads its trace and the status word in ONE round trip
 
     // host-side state of the reference's main()
     float beta1t = 1.0f, beta2t = 1.0f; // main.cpp:274-275
@@ -125,15 +105,11 @@ struct s2d_ctx {
     bool have_target = false;
     bool have_forward = false;  // image0 holds the framebuffer of the CURRENT parameters (s2d_backward reads it)
     bool have_backward = false;
-    bool sqerr_deferred = false; // the squared-error reduction of the last backward pass rides on the next Adam launch
-    int last_sqerr_slot = -1;
     char err[512] = {0};
     S2D_LOCAL ~s2d_ctx() = default; // (named only to keep it out of the library's exports, like the owners it runs)
 };
 
 namespace {
-
-constexpr int kHostTrace = 4096;
 
 int fail(s2d_ctx* c, int code, const char* fmt, ...)
 {
@@ -190,13 +166,9 @@ int ensure_pair_capacity(s2d_ctx* c, uint64_t need)
     const auto hand_over = [&]() -> int {
         S2D_HIP(c, c->d_wave_masks.alloc((size_t)cap * 4));
         S2D_HIP(c, c->d_exec_list.alloc((size_t)cap));
-        if (c->deterministic) {
-            S2D_HIP(c, c->d_det_data.alloc((size_t)cap * kDetStride));
-            S2D_HIP(c, c->d_det_stamp.alloc((size_t)cap));
-            S2D_HIP(c, hipMemsetAsync(c->d_det_stamp, 0, (size_t)cap * sizeof(uint32_t), c->stream));
-        }
-        if (c->ref_order) {
-            S2D_HIP(c, c->d_ref_terms.alloc((size_t)cap * kRefTermsStride));
+        if (c->deterministic) S2D_HIP(c, c->d_det_data.alloc((size_t)cap * kDetStride));
+        if (c->ref_order) S2D_HIP(c, c->d_ref_terms.alloc((size_t)cap * kRefTermsStride));
+        if (c->deterministic || c->ref_order) { // either mode's slots carry stamps
             S2D_HIP(c, c->d_det_stamp.alloc((size_t)cap));
             S2D_HIP(c, hipMemsetAsync(c->d_det_stamp, 0, (size_t)cap * sizeof(uint32_t), c->stream));
         }
@@ -237,7 +209,7 @@ RasterArgs raster_args(const s2d_ctx* c, int first = 0, int count = -1)
     a.tile_off = c->lists.tile_off(); a.list = c->lists.list(); a.wave_masks = c->d_wave_masks;
     a.exec_list = c->d_exec_list; a.tile_exec = c->d_tile_exec; a.retire_hint = c->d_retire_hint;
     a.proj = c->d_proj + first; a.grads = c->d_grads + (size_t)first * 9;
-    a.image0 = c->d_image0; a.image_ref = c->d_ref; a.tile_sqerr = c->d_tile_sqerr;
+    a.image0 = c->d_image0; a.image_ref = c->d_ref; a.tile_sqerr = c->trace.tile_sqerr();
     a.g = c->g; a.status = c->d_status; a.iteration = c->iterations; a.counters = c->d_counters;
     a.state = c->d_state; a.any_alive = c->d_chunk_alive;
     if (c->deterministic) // (det.now stays 0, no gather, until with_backward_walk)
@@ -247,18 +219,37 @@ RasterArgs raster_args(const s2d_ctx* c, int first = 0, int count = -1)
     return a;
 }
 
+// What a projection pass works on.  mode 0: rectangles (inflated by the re-use margin), pair and row counts for a list
+// build; mode 1: the containment check against those rectangles, stamped with the check's sequence number.
+ProjectArgs project_args(const s2d_ctx* c, const float* splats, int mode)
+{
+    ProjectArgs a;
+    a.splats = splats; a.held = c->state.held(); a.n = c->n; a.g = c->g; a.mode = mode; a.proj = c->d_proj; a.counts = c->d_counts;
+    a.check = ContainmentCheck{c->d_rects, c->d_status, mode ? c->check_seq : 0, mode ? (int*)c->h_rebin_stamp : nullptr};
+    if (mode == 0) a.margin = c->margin, a.row_counts = c->lists.row_counts();
+    return a;
+}
+
+// What an Adam launch works on.  project: the kernel also projects what it wrote and runs the containment check.
+AdamArgs adam_args(s2d_ctx* c, uint32_t flags, bool project)
+{
+    const SplatState::AdamStep st = c->state.adam_step();
+    AdamArgs a;
+    a.splats = st.arrays.splats; a.adams = st.arrays.adams; a.grads = c->d_grads; a.compact = st.compact;
+    a.held_ids = st.held_ids; a.held_count = st.held_count; a.dormant = st.dormant; a.n = c->n; a.g = c->g;
+    a.beta1t = c->beta1t; a.beta2t = c->beta2t; a.lr = c->lr; a.iteration = c->iterations;
+    a.mode = ((flags & S2D_STEP_OPTIMIZE_OPACITY) ? 1 : 0) | ((c->cfg.flags & S2D_CFG_ADAM_FP32) ? 2 : 0);
+    a.proj = project ? (ProjRec*)c->d_proj : nullptr;
+    a.check = ContainmentCheck{c->d_rects, c->d_status, c->check_seq, c->h_rebin_stamp};
+    a.sq = c->trace.take_for_adam();
+    return a;
+}
+
 // The pass has a backward walk.  Deterministic mode: a fresh stamp for its slots (those of earlier passes become invalid).
 void with_backward_walk(s2d_ctx* c, RasterArgs& a, bool need_opacity_grad)
 {
     a.need_opacity_grad = need_opacity_grad;
     if (c->deterministic) a.det.now = ++c->det_epoch;
-}
-
-// The sum of the tile errors into ring slot `slot` of the trace, riding on another launch (slot < 0: none).
-SqerrJob sqerr_job(const s2d_ctx* c, int slot)
-{
-    if (slot < 0) return SqerrJob{nullptr, 0, nullptr, nullptr};
-    return SqerrJob{c->d_tile_sqerr, c->g.num_tiles, c->d_sqerr_trace + slot, c->d_tile_sqerr + c->g.num_tiles};
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -346,7 +337,6 @@ struct RasterJob {
     bool fused = false;        // forward + backward walk in one launch
     bool need_opacity_grad = true;
     bool write_image = true;   // fused only: store image0 (nothing but s2d_get_image reads it)
-    bool sum_sqerr = false;    // fused only, small images: the launch's last tile also adds up the tile errors
 };
 
 int launch_job(s2d_ctx* c, bool optimistic, const RasterJob& job)
@@ -356,7 +346,7 @@ int launch_job(s2d_ctx* c, bool optimistic, const RasterJob& job)
     if (job.fused) {
         with_backward_walk(c, a, job.need_opacity_grad);
         a.write_image = job.write_image;
-        a.sq = sqerr_job(c, job.sum_sqerr ? c->iterations % c->trace_cap : -1);
+        if (c->trace.plan(true, true) == SqerrBy::PassItself) a.sq = c->trace.job(c->iterations);
     }
     if (c->ref_order && a.exact_exp) // (never fused: queue_forward_backward)
         S2D_HIP(c, launch_reference_forward_exact(a, c->stream));
@@ -369,27 +359,28 @@ int launch_job(s2d_ctx* c, bool optimistic, const RasterJob& job)
 // What is current, and what makes it stale.  Three things are derived from the parameters, each from the one before:
 // the projection with its containment check (proj_fresh), the tile lists (lists_valid), and the frames -- image0 and
 // the gradients (have_forward, have_backward).  The functions that produce them set these flags (rebuild_lists,
-// queue_raster, queue_sqerr / queue_forward_backward, queue_adam); everything else names an event, and invalidate()
+// queue_raster, backward_queued, queue_adam); everything else names an event, and invalidate()
 // clears what the event reaches: Frames < Projection < Lists, a level with everything below it.
 //   target replaced (s2d_set_target, _synthetic): Frames.
-//   all splats replaced (s2d_init_splats, s2d_set_splats): Lists; splats_replaced() = state_written() + a fresh status
-//     word.  init also zeroes the gradients and restarts the counters, and flushes no compact copy first: every
+//   all splats replaced (s2d_init_splats, s2d_set_splats): Lists; splats_replaced() = state.written() + a fresh status
+//     word.  init also zeroes the gradients and restarts the counters, and asks for the arrays with discard_all(): every
 //     record, moments included, is new.
-//   some splat rows replaced (s2d_rows_scatter): Projection; state_written().  Not Lists: a row moves a splat a little,
+//   some splat rows replaced (s2d_rows_scatter): Projection; state.written().  Not Lists: a row moves a splat a little,
 //     and the containment check of the projection that follows asks for new lists if it left its rectangle.
 //   all splats replaced from device memory (s2d_set_splats_device): as some rows, over all of them -- Projection;
-//     state_written().  Not Lists, and no fresh status word: this is the call of an optimisation loop outside the
+//     state.written().  Not Lists, and no fresh status word: this is the call of an optimisation loop outside the
 //     library, which moves every splat a little per call; a splat that left its rectangle gets its new lists from the
 //     same containment check.
-//   moments replaced (s2d_set_adam, s2d_rows_scatter): nothing, what is drawn depends on the parameters only; state_written().
+//   moments replaced (s2d_set_adam, s2d_rows_scatter): nothing, what is drawn depends on the parameters only; state.written().
 //   held set changed (s2d_halo_commit): Lists if splats arrived, on the first commit and on the return to holding
 //     everything (the lists hold the held splats only); departures alone leave lists that still cover every held splat.
-//     compact_off() before, compact_load() after.
 //   Adam step queued (queue_adam): Projection, which the step itself renews when it projects (lists in re-use).
 //   non-finite step judged (judge_status): Frames; the counters are wound back to the failing step.
 //   index-range pass finished (queue_raster): the last range's lists are no lists of the scene, lists_valid stays false.
-// Before the id-indexed arrays are read or written from outside: compact_flush().  Before the iteration count changes
-// from outside: flush_sqerr(), whose ring slot is named by it.
+// Two rules are not in this table because no call site keeps them any more (s2d_state.h): the id-indexed parameter and
+// moment arrays are handed out by SplatState::current() only, which queues the write-back of a compact copy first; and a
+// squared-error sum still waiting for its Adam launch is queued by SqerrTrace's own read() and settle(), the latter
+// being what s2d_set_adam and s2d_init_splats call before they renumber the iterations.
 // ---------------------------------------------------------------------------------------------------------------------
 enum class Stale { Frames, Projection, Lists };
 
@@ -400,57 +391,12 @@ void invalidate(s2d_ctx* c, Stale reach)
     if (reach >= Stale::Lists) c->lists_valid = false;
 }
 
-// Compact held state (see s2d_ctx): bring the id-indexed parameter / moment arrays up to date ...
-int compact_flush(s2d_ctx* c)
-{
-    if (!c->compact_live || !c->compact_dirty) return S2D_OK;
-    S2D_HIP(c, launch_compact_copy(c->d_splats, 9, c->d_held_ids, c->d_held_count, c->n, c->d_csplats, false, c->stream));
-    S2D_HIP(c, launch_compact_copy(c->d_adams, 18, c->d_held_ids, c->d_held_count, c->n, c->d_cadams, false, c->stream));
-    c->compact_dirty = false;
-    return S2D_OK;
-}
-
-// ... for good: the held set is about to change, the id-indexed arrays take over until compact_load ...
-int compact_off(s2d_ctx* c)
-{
-    if (int rc = compact_flush(c)) return rc;
-    c->compact_live = false;
-    return S2D_OK;
-}
-
-// ... and make the compact copy afresh from them (the held set, or the arrays, changed from outside).
-int compact_load(s2d_ctx* c)
-{
-    c->compact_live = false;
-    c->compact_dirty = false;
-    if (!c->d_held || !c->compact_enabled || c->n <= 0) return S2D_OK;
-    if (!c->d_csplats) {
-        S2D_HIP(c, c->d_csplats.alloc((size_t)c->n * 9));
-        S2D_HIP(c, c->d_cadams.alloc((size_t)c->n * 18));
-    }
-    S2D_HIP(c, launch_compact_copy(c->d_splats, 9, c->d_held_ids, c->d_held_count, c->n, c->d_csplats, true, c->stream));
-    S2D_HIP(c, launch_compact_copy(c->d_adams, 18, c->d_held_ids, c->d_held_count, c->n, c->d_cadams, true, c->stream));
-    c->compact_live = true;
-    return S2D_OK;
-}
-
-// Splats or Adam moments have been written (queued) from outside the Adam kernel, all of them or some rows: the compact
-// copy is made again -- rows of held splats may be among them -- and nothing is known to be dormant any more (the next
-// step of every splat is a full one, which also applies the constraints to whatever was loaded).
-int state_written(s2d_ctx* c, bool all_rows)
-{
-    if (all_rows || c->compact_live)
-        if (int rc = compact_load(c)) return rc;
-    if (c->n > 0) S2D_HIP(c, hipMemsetAsync(c->d_dormant, 0, (size_t)c->n, c->stream));
-    return S2D_OK;
-}
-
 constexpr DeviceStatus kFreshStatus{0, INT_MAX, 0, 0}; // rebin_needed 0 matches no check (sequence numbers start at 1)
 
 // New parameters (init / set_splats): a non-finite event of the old ones no longer stops the queue.
 int splats_replaced(s2d_ctx* c)
 {
-    if (int rc = state_written(c, true)) return rc;
+    S2D_HIP(c, c->state.written(true));
     S2D_HIP(c, hipMemcpyAsync(c->d_status, &kFreshStatus, sizeof(DeviceStatus), hipMemcpyHostToDevice, c->stream));
     invalidate(c, Stale::Lists);
     return S2D_OK;
@@ -466,6 +412,14 @@ int splats_replaced(s2d_ctx* c)
 // no flag has to be copied or cleared.  If the check failed the lists are rebuilt and the raster kernel is
 // launched again.  (In deterministic mode the gather pass queued behind a voided fused launch adds nothing: the
 // slots carry no stamp of that pass.)
+int queue_project(s2d_ctx* c, int mode)
+{
+    SplatState::Arrays now;
+    S2D_HIP(c, c->state.current(&now));
+    S2D_HIP(c, launch_project(project_args(c, now.splats, mode), c->stream));
+    return S2D_OK;
+}
+
 int queue_raster(s2d_ctx* c, const RasterJob& job)
 {
     if (!c->have_target) return fail(c, S2D_E_STATE, "no target image set (s2d_set_target)");
@@ -474,10 +428,8 @@ int queue_raster(s2d_ctx* c, const RasterJob& job)
     bool stored_image0 = !job.fused || job.write_image; // a fused launch told not to store image0 leaves an older frame there
     if (!scheduled) {
         if (!c->proj_fresh) { // parameters changed without a fused projection: project + check now
-            if (int rc = compact_flush(c)) return rc;
             c->check_seq++;
-            S2D_HIP(c, launch_project(c->d_splats, c->d_held, c->n, c->g, 0.0f, 1, c->d_proj, c->d_rects, c->d_counts, nullptr, c->d_status,
-                                      c->check_seq, c->h_rebin_stamp, c->stream));
+            if (int rc = queue_project(c, 1)) return rc;
             S2D_HIP(c, hipEventRecord(c->ev_flag, c->stream));
             c->proj_fresh = true;
         }
@@ -486,13 +438,11 @@ int queue_raster(s2d_ctx* c, const RasterJob& job)
         rebuild = *(volatile int*)c->h_rebin_stamp == c->check_seq;
     }
     if (rebuild) {
-        if (int rc = compact_flush(c)) return rc;
-        S2D_HIP(c, launch_project(c->d_splats, c->d_held, c->n, c->g, c->margin, 0, c->d_proj, c->d_rects, c->d_counts,
-                                  c->lists.row_counts(), c->d_status, 0, nullptr, c->stream));
+        int rc = queue_project(c, 0);
+        if (rc != S2D_OK) return rc;
         c->chunks.clear();
         bool need_ranges = false;
-        int rc = rebuild_lists(c, 0, -1, &need_ranges);
-        if (rc != S2D_OK) return rc;
+        if ((rc = rebuild_lists(c, 0, -1, &need_ranges)) != S2D_OK) return rc;
         if (need_ranges && (c->cfg.flags & S2D_CFG_COUNT_PAIRS))
             return fail(c, S2D_E_NOMEM, "pair counting (S2D_CFG_COUNT_PAIRS) is not available for scenes beyond %llu (tile, splat) pairs",
                         (unsigned long long)c->chunk_pairs);
@@ -518,51 +468,39 @@ int queue_raster(s2d_ctx* c, const RasterJob& job)
 
 int queue_forward(s2d_ctx* c) { return queue_raster(c, RasterJob{}); }
 
-int flush_sqerr(s2d_ctx* c)
+// A backward pass of the current iteration has been queued; `by`: what becomes of its squared error (SqerrTrace::plan,
+// or what the pass has done about it already).
+int backward_queued(s2d_ctx* c, SqerrBy by)
 {
-    if (!c->sqerr_deferred) return S2D_OK;
-    c->sqerr_deferred = false;
-    S2D_HIP(c, launch_sqerr_finalize(sqerr_job(c, c->last_sqerr_slot), c->d_status, c->iterations, c->stream));
+    c->have_backward = true;
+    S2D_HIP(c, c->trace.record(c->iterations, by));
     return S2D_OK;
 }
 
-// Sum of the tile errors of the backward pass just queued -> ring slot of this iteration.  defer: leave it to the next
-// Adam launch, whose first workgroups do it on the way (one dispatch less per iteration); whoever wants the value
-// before that (s2d_get_mse, s2d_get_sqerr_trace) flushes it with the standalone kernel (flush_sqerr).
-int queue_sqerr(s2d_ctx* c, bool defer = false)
-{
-    c->last_sqerr_slot = c->iterations % c->trace_cap;
-    c->have_backward = true;
-    c->sqerr_deferred = true;
-    // (worth it only when the Adam launch has a workgroup per chunk: a 4-workgroup launch would walk 16 chunks each)
-    return defer && (c->n + 255) / 256 >= kSqerrChunks ? S2D_OK : flush_sqerr(c);
-}
-
 // S2D_CFG_REFERENCE_ORDER: terms into their slots, the ordered sums into the gradient buffer, and the squared error as one
-// ordered chain straight into the ring slot -- nothing is deferred to the Adam launch.  (Such a context never renders by
-// index ranges: queue_raster refuses the scene.)
+// ordered chain straight into the ring slot -- nothing is left to the Adam launch.  (Such a context never renders by
+// index ranges, queue_raster refuses the scene, and holds every splat: the state's write-back is a no-op.)
 int queue_backward_reference(s2d_ctx* c, bool need_opacity_grad, const float4* upstream)
 {
     RasterArgs a = raster_args(c);
     a.upstream = upstream;
     a.need_opacity_grad = need_opacity_grad;
+    SplatState::Arrays now;
+    S2D_HIP(c, c->state.current(&now));
     RefOrder ro;
-    ro.splats = c->d_splats; ro.rects = c->d_rects; ro.offsets = c->d_offsets; ro.counts = c->d_counts; ro.n = c->n;
+    ro.splats = now.splats; ro.rects = c->d_rects; ro.offsets = c->d_offsets; ro.counts = c->d_counts; ro.n = c->n;
     ro.terms = c->d_ref_terms; ro.stamp = c->d_det_stamp; ro.capacity = (uint32_t)c->lists.capacity(); ro.now = ++c->det_epoch;
     ro.pixel_sqerr = c->d_pixel_sqerr;
     S2D_HIP(c, launch_reference_backward(a, ro, c->stream));
-    c->have_backward = true;
-    if (upstream) return S2D_OK;
-    c->last_sqerr_slot = c->iterations % c->trace_cap;
-    c->sqerr_deferred = false;
-    S2D_HIP(c, launch_reference_sqerr(c->d_pixel_sqerr, (size_t)c->g.W * (size_t)(c->g.row_end - c->g.row_begin), c->d_sqerr_trace + c->last_sqerr_slot, c->d_status,
-                                      c->iterations, c->stream));
-    return S2D_OK;
+    if (upstream) return backward_queued(c, SqerrBy::NoLoss);
+    S2D_HIP(c, launch_reference_sqerr(c->d_pixel_sqerr, (size_t)c->g.W * (size_t)(c->g.row_end - c->g.row_begin),
+                                      c->trace.job(c->iterations).out, c->d_status, c->iterations, c->stream));
+    return backward_queued(c, SqerrBy::PassItself);
 }
 
 // upstream != nullptr (s2d_backward_image_grads): the walk starts from the caller's dL/d(image0) instead of
-// image0 - imageRef.  The loss is the caller's, so no squared error is formed or queued: the trace ring, last_sqerr_slot
-// and a reduction still deferred to the next Adam launch stay as the last s2d_backward left them.
+// image0 - imageRef.  The loss is the caller's, so no squared error is formed or queued: the trace ring and a sum still
+// waiting for the next Adam launch stay as the last s2d_backward left them (SqerrBy::NoLoss).
 int queue_backward(s2d_ctx* c, bool need_opacity_grad, const float4* upstream = nullptr)
 {
     if (!c->have_forward) return fail(c, S2D_E_STATE, "the backward pass needs s2d_forward on the current parameters");
@@ -575,16 +513,12 @@ int queue_backward(s2d_ctx* c, bool need_opacity_grad, const float4* upstream = 
         with_backward_walk(c, a, need_opacity_grad);
         S2D_HIP(c, launch_raster(RasterPass::Backward, a, c->stream));
     }
-    if (upstream) {
-        c->have_backward = true;
-        return S2D_OK;
-    }
-    return queue_sqerr(c);
+    return backward_queued(c, upstream ? SqerrBy::NoLoss : c->trace.plan(false, false));
 }
 
 // Forward + backward (+ squared error) of the current parameters through the fused kernel.  Pair counting is a
 // property of the separate kernels only, so a counting context takes those.
-int queue_forward_backward(s2d_ctx* c, bool need_opacity_grad, bool write_image, bool defer_sqerr = true)
+int queue_forward_backward(s2d_ctx* c, bool need_opacity_grad, bool write_image)
 {
     if ((c->cfg.flags & S2D_CFG_COUNT_PAIRS) || c->ref_order) { // (reference order: its backward pass is a launch of its own)
         if (int rc = queue_forward(c)) return rc;
@@ -594,18 +528,8 @@ int queue_forward_backward(s2d_ctx* c, bool need_opacity_grad, bool write_image,
     job.fused = true;
     job.need_opacity_grad = need_opacity_grad;
     job.write_image = write_image;
-    // Small scene (few tiles, and too few splats for the Adam launch to have a workgroup per chunk of tile errors): the
-    // raster launch's last tile adds up the tile errors itself.  (Where the Adam launch can do it on the way that is
-    // cheaper still: 535x426 / 50 k measured 6.9 % slower with the in-raster sum.)
-    job.sum_sqerr = c->g.num_tiles <= kSqerrSmallTiles && (c->n + 255) / 256 < kSqerrChunks;
     if (int rc = queue_raster(c, job)) return rc;
-    if (job.sum_sqerr && c->chunks.empty()) { // nothing left to queue
-        c->last_sqerr_slot = c->iterations % c->trace_cap;
-        c->have_backward = true;
-        c->sqerr_deferred = false;
-        return S2D_OK;
-    }
-    return queue_sqerr(c, defer_sqerr);
+    return backward_queued(c, c->trace.plan(true, c->chunks.empty())); // (launch_job asked the same plan about the fused launch)
 }
 
 int queue_adam(s2d_ctx* c, uint32_t flags)
@@ -616,16 +540,7 @@ int queue_adam(s2d_ctx* c, uint32_t flags)
     // rectangles (what the next forward needs), which saves a pass over the parameters per iteration.
     const bool fuse = c->lists_valid && c->rebin_interval > 1;
     if (fuse) c->check_seq++;
-    const bool compact = c->compact_live && c->d_held_ids != nullptr;
-    S2D_HIP(c, launch_adam(compact ? c->d_csplats : c->d_splats, compact ? c->d_cadams : c->d_adams, c->d_grads, c->d_held_ids,
-                           c->d_held_count, c->n, c->g, c->beta1t, c->beta2t,
-                           c->lr,
-                           ((flags & S2D_STEP_OPTIMIZE_OPACITY) ? 1 : 0) | ((c->cfg.flags & S2D_CFG_ADAM_FP32) ? 2 : 0),
-                           c->iterations, c->d_status,
-                           fuse ? c->d_proj : nullptr, c->d_rects, c->check_seq, c->h_rebin_stamp, c->d_dormant,
-                           sqerr_job(c, c->sqerr_deferred ? c->last_sqerr_slot : -1), compact, c->stream));
-    if (compact) c->compact_dirty = true;
-    c->sqerr_deferred = false;
+    S2D_HIP(c, launch_adam(adam_args(c, flags, fuse), c->stream));
     if (fuse) S2D_HIP(c, hipEventRecord(c->ev_flag, c->stream));
     invalidate(c, Stale::Projection);
     c->proj_fresh = fuse; // (then the step projected what it wrote)
@@ -637,17 +552,6 @@ int queue_adam(s2d_ctx* c, uint32_t flags)
 int queue_status_read(s2d_ctx* c) // -> h_status, valid once the stream has been synchronised
 {
     S2D_HIP(c, hipMemcpyAsync(c->h_status, c->d_status, sizeof(DeviceStatus), hipMemcpyDeviceToHost, c->stream));
-    return S2D_OK;
-}
-
-// Entries [first, first + count) of the squared-error trace (a ring of trace_cap slots) -> out, queued.
-int queue_trace_read(s2d_ctx* c, int first, int count, double* out)
-{
-    for (int got = 0; got < count;) {
-        const int slot = (first + got) % c->trace_cap, run = std::min(count - got, c->trace_cap - slot);
-        S2D_HIP(c, hipMemcpyAsync(out + got, c->d_sqerr_trace + slot, (size_t)run * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        got += run;
-    }
     return S2D_OK;
 }
 
@@ -736,9 +640,7 @@ int s2d_create(const s2d_config* cfg, s2d_ctx** out)
 
     const size_t n = std::max<size_t>((size_t)c->n, 1);           // >= 1 so that n == 0 still has buffers
     const size_t px = (size_t)g.W * (size_t)(g.row_end - g.row_begin); // pixels of the slab: all this context stores
-    S2D_HIP(c, c->d_splats.alloc(n * 9));
-    S2D_HIP(c, c->d_adams.alloc(n * 18));
-    S2D_HIP(c, c->d_dormant.alloc(n));
+    S2D_HIP(c, c->state.create(c->n, c->stream));
     S2D_HIP(c, c->d_grads_own.alloc(n * 9));
     c->d_grads = c->d_grads_own;
     S2D_HIP(c, c->d_proj.alloc(n));
@@ -747,7 +649,6 @@ int s2d_create(const s2d_config* cfg, s2d_ctx** out)
     S2D_HIP(c, c->d_offsets.alloc(n));
     S2D_HIP(c, c->d_scan_temp.alloc(scan_temp_words((int64_t)n)));
     S2D_HIP(c, c->lists.create(g, n, (cfg->flags & S2D_CFG_GENERIC_BINNING) != 0));
-    if (const char* e = getenv("S2D_COMPACT_HELD")) c->compact_enabled = atoi(e) != 0;
     if (const char* e = getenv("S2D_CHUNK_PAIRS")) { // pairs per index range (tests; default 2^30, never beyond 32-bit positions)
         const unsigned long long v = strtoull(e, nullptr, 10);
         if (v > 0) c->chunk_pairs = std::min<unsigned long long>(v, 0xFFFF0000ull - 1);
@@ -769,27 +670,20 @@ int s2d_create(const s2d_config* cfg, s2d_ctx** out)
     c->pixel_bytes = c->half_images ? 8 : sizeof(float4);
     S2D_HIP(c, c->d_image0.alloc(px * c->pixel_bytes));
     S2D_HIP(c, c->d_ref.alloc(px * c->pixel_bytes));
-    S2D_HIP(c, c->d_tile_sqerr.alloc((size_t)g.num_tiles + kSqerrScratchDoubles)); // + finalize scratch
     S2D_HIP(c, c->d_tile_exec.alloc((size_t)g.num_tiles));
     S2D_HIP(c, c->d_retire_hint.alloc((size_t)g.num_tiles));
     S2D_HIP(c, hipMemset(c->d_retire_hint, 0xFF, (size_t)g.num_tiles * sizeof(uint32_t)));
-    S2D_HIP(c, hipMemset(c->d_tile_sqerr + g.num_tiles, 0, kSqerrScratchDoubles * sizeof(double)));
-    S2D_HIP(c, c->d_sqerr_trace.alloc((size_t)c->trace_cap));
     S2D_HIP(c, c->d_status.alloc(1));
+    S2D_HIP(c, c->trace.create(g.num_tiles, c->n, c->d_status, c->stream));
     S2D_HIP(c, c->d_counters.alloc(1));
     S2D_HIP(c, c->ev_flag.create(hipEventDisableTiming));
     S2D_HIP(c, c->h_status.alloc(1, hipHostMallocDefault));
-    S2D_HIP(c, c->h_trace.alloc(kHostTrace, hipHostMallocDefault));
     S2D_HIP(c, c->h_rebin_stamp.alloc(16, hipHostMallocMapped));
     *c->h_rebin_stamp = 0;
 
-    S2D_HIP(c, hipMemsetAsync(c->d_splats, 0, n * 9 * sizeof(float), c->stream));
-    S2D_HIP(c, hipMemsetAsync(c->d_adams, 0, n * 18 * sizeof(float), c->stream));
-    S2D_HIP(c, hipMemsetAsync(c->d_dormant, 0, n, c->stream));
     S2D_HIP(c, hipMemsetAsync(c->d_grads_own, 0, n * 9 * sizeof(float), c->stream));
     S2D_HIP(c, hipMemsetAsync(c->d_image0, 0, px * c->pixel_bytes, c->stream));
     S2D_HIP(c, hipMemsetAsync(c->d_ref, 0, px * c->pixel_bytes, c->stream));
-    S2D_HIP(c, hipMemsetAsync(c->d_sqerr_trace, 0, (size_t)c->trace_cap * sizeof(double), c->stream));
     S2D_HIP(c, hipMemsetAsync(c->d_counters, 0, sizeof(PairCounters), c->stream));
     *c->h_status = kFreshStatus;
     S2D_HIP(c, hipMemcpyAsync(c->d_status, c->h_status, sizeof(DeviceStatus), hipMemcpyHostToDevice, c->stream));
@@ -850,9 +744,10 @@ int s2d_init_splats(s2d_ctx* c)
 {
     if (!c) return S2D_E_INVALID;
     if (int rc = use_device(c)) return rc;
-    if (int rc = flush_sqerr(c)) return rc;
-    S2D_HIP(c, launch_init_splats(c->d_splats, c->d_adams, c->n, c->g.W, c->g.H, c->stream));
-    if (int rc = splats_replaced(c)) return rc; // (every record is new: nothing of the old compact copy is worth flushing)
+    S2D_HIP(c, c->trace.settle()); // (the iteration count is about to restart)
+    const SplatState::Arrays all = c->state.discard_all(); // every record is new
+    S2D_HIP(c, launch_init_splats(all.splats, all.adams, c->n, c->g.W, c->g.H, c->stream));
+    if (int rc = splats_replaced(c)) return rc;
     if (c->n > 0) S2D_HIP(c, hipMemsetAsync(c->d_grads, 0, (size_t)c->n * 9 * sizeof(float), c->stream));
     c->beta1t = c->good_beta1t = 1.0f; // main.cpp:283-284
     c->beta2t = c->good_beta2t = 1.0f;
@@ -864,8 +759,9 @@ int s2d_set_splats(s2d_ctx* c, const s2d_splat* splats)
 {
     if (!c || (!splats && c->n)) return S2D_E_INVALID;
     if (int rc = use_device(c)) return rc;
-    if (int rc = compact_flush(c)) return rc; // the moments of the held splats must not be lost with the compact copy
-    S2D_HIP(c, hipMemcpyAsync(c->d_splats, splats, (size_t)c->n * sizeof(s2d_splat), hipMemcpyHostToDevice, c->stream));
+    SplatState::Arrays now; // (with the moments of the held splats: they must not be lost with the compact copy)
+    S2D_HIP(c, c->state.current(&now));
+    S2D_HIP(c, hipMemcpyAsync(now.splats, splats, (size_t)c->n * sizeof(s2d_splat), hipMemcpyHostToDevice, c->stream));
     if (int rc = splats_replaced(c)) return rc;
     S2D_HIP(c, hipStreamSynchronize(c->stream));
     return S2D_OK;
@@ -875,8 +771,9 @@ int s2d_get_splats(s2d_ctx* c, s2d_splat* splats)
 {
     if (!c || (!splats && c->n)) return S2D_E_INVALID;
     if (int rc = use_device(c)) return rc;
-    if (int rc = compact_flush(c)) return rc;
-    S2D_HIP(c, hipMemcpyAsync(splats, c->d_splats, (size_t)c->n * sizeof(s2d_splat), hipMemcpyDeviceToHost, c->stream));
+    SplatState::Arrays now;
+    S2D_HIP(c, c->state.current(&now));
+    S2D_HIP(c, hipMemcpyAsync(splats, now.splats, (size_t)c->n * sizeof(s2d_splat), hipMemcpyDeviceToHost, c->stream));
     S2D_HIP(c, hipStreamSynchronize(c->stream));
     return S2D_OK;
 }
@@ -885,10 +782,11 @@ int s2d_set_adam(s2d_ctx* c, const s2d_splat_adam* adams, float beta1t, float be
 {
     if (!c || (!adams && c->n) || iterations < 0) return S2D_E_INVALID;
     if (int rc = use_device(c)) return rc;
-    if (int rc = flush_sqerr(c)) return rc; // (its ring slot is named by the iteration count about to change)
-    if (int rc = compact_flush(c)) return rc; // the parameters of the held splats must not be lost with the compact copy
-    S2D_HIP(c, hipMemcpyAsync(c->d_adams, adams, (size_t)c->n * sizeof(s2d_splat_adam), hipMemcpyHostToDevice, c->stream));
-    if (int rc = state_written(c, true)) return rc;
+    S2D_HIP(c, c->trace.settle()); // (the iteration count is about to change)
+    SplatState::Arrays now; // (with the parameters of the held splats: they must not be lost with the compact copy)
+    S2D_HIP(c, c->state.current(&now));
+    S2D_HIP(c, hipMemcpyAsync(now.adams, adams, (size_t)c->n * sizeof(s2d_splat_adam), hipMemcpyHostToDevice, c->stream));
+    S2D_HIP(c, c->state.written(true));
     S2D_HIP(c, hipStreamSynchronize(c->stream));
     c->beta1t = c->good_beta1t = beta1t;
     c->beta2t = c->good_beta2t = beta2t;
@@ -901,8 +799,9 @@ int s2d_get_adam(s2d_ctx* c, s2d_splat_adam* adams, float* beta1t, float* beta2t
     if (!c) return S2D_E_INVALID;
     if (int rc = use_device(c)) return rc;
     if (adams) {
-        if (int rc = compact_flush(c)) return rc;
-        S2D_HIP(c, hipMemcpyAsync(adams, c->d_adams, (size_t)c->n * sizeof(s2d_splat_adam), hipMemcpyDeviceToHost, c->stream));
+        SplatState::Arrays now;
+        S2D_HIP(c, c->state.current(&now));
+        S2D_HIP(c, hipMemcpyAsync(adams, now.adams, (size_t)c->n * sizeof(s2d_splat_adam), hipMemcpyDeviceToHost, c->stream));
         S2D_HIP(c, hipStreamSynchronize(c->stream));
     }
     if (beta1t) *beta1t = c->beta1t;
@@ -975,10 +874,11 @@ int s2d_set_splats_device(s2d_ctx* c, const float* splats_device)
 {
     if (!c || (!splats_device && c->n)) return S2D_E_INVALID;
     if (int rc = use_device(c)) return rc;
-    if (int rc = compact_flush(c)) return rc; // the moments of the held splats must not be lost with the compact copy
+    SplatState::Arrays now; // (with the moments of the held splats: they must not be lost with the compact copy)
+    S2D_HIP(c, c->state.current(&now));
     if (c->n > 0)
-        S2D_HIP(c, hipMemcpyAsync(c->d_splats, splats_device, (size_t)c->n * sizeof(s2d_splat), hipMemcpyDeviceToDevice, c->stream));
-    if (int rc = state_written(c, true)) return rc;
+        S2D_HIP(c, hipMemcpyAsync(now.splats, splats_device, (size_t)c->n * sizeof(s2d_splat), hipMemcpyDeviceToDevice, c->stream));
+    S2D_HIP(c, c->state.written(true));
     invalidate(c, Stale::Projection); // (not Lists: see the table above invalidate())
     return S2D_OK;
 }
@@ -1022,22 +922,21 @@ int s2d_step(s2d_ctx* c, int32_t iters, uint32_t flags, double* mse_out)
     int done = 0;
     bool status_read = false;
     while (done < iters) {
-        const int chunk = std::min(iters - done, c->trace_cap);
+        const int chunk = std::min<int>(iters - done, SqerrTrace::kCapacity);
         const int first_iter = c->iterations;
         for (int k = 0; k < chunk; k++) {
             // image0 is stored by the last iteration of the call only: nothing else could observe the others
             const bool last = done + k + 1 == iters;
-            if (int rc = queue_forward_backward(c, (flags & S2D_STEP_OPTIMIZE_OPACITY) != 0, last, true)) return rc;
+            if (int rc = queue_forward_backward(c, (flags & S2D_STEP_OPTIMIZE_OPACITY) != 0, last)) return rc;
             if (int rc = queue_adam(c, flags)) return rc;
         }
         const bool last_chunk = done + chunk == iters;
-        if (mse_out && last_chunk && chunk <= kHostTrace) {
+        if (mse_out && last_chunk && chunk <= SqerrTrace::kPinned) {
             // the usual call (a frame, or a batch of frames, of the host loop): trace and status word in one round trip
-            if (int rc = flush_sqerr(c)) return rc;
-            if (int rc = queue_trace_read(c, first_iter, chunk, c->h_trace)) return rc;
+            S2D_HIP(c, c->trace.read(first_iter, chunk, c->trace.pinned()));
             if (int rc = queue_status_read(c)) return rc;
             S2D_HIP(c, hipStreamSynchronize(c->stream));
-            for (int k = 0; k < chunk; k++) mse_out[done + k] = c->h_trace[k] / norm; // main.cpp:805
+            for (int k = 0; k < chunk; k++) mse_out[done + k] = c->trace.pinned()[k] / norm; // main.cpp:805
             status_read = true;
         } else if (mse_out) {
             if (int rc = s2d_get_sqerr_trace(c, first_iter, chunk, mse_out + done)) return rc;
@@ -1059,10 +958,9 @@ int s2d_get_mse(s2d_ctx* c, double* mse)
 {
     if (!c || !mse) return S2D_E_INVALID;
     if (int rc = use_device(c)) return rc;
-    if (c->last_sqerr_slot < 0) return fail(c, S2D_E_STATE, "no backward pass has run yet");
-    if (int rc = flush_sqerr(c)) return rc;
+    if (c->trace.last_iteration() < 0) return fail(c, S2D_E_STATE, "no backward pass has run yet");
     double v = 0.0;
-    S2D_HIP(c, hipMemcpyAsync(&v, c->d_sqerr_trace + c->last_sqerr_slot, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    S2D_HIP(c, c->trace.read(c->trace.last_iteration(), 1, &v));
     S2D_HIP(c, hipStreamSynchronize(c->stream));
     *mse = v / mse_norm(c);
     return S2D_OK;
@@ -1088,8 +986,9 @@ int s2d_halo_masks(s2d_ctx* c, int32_t world, const int32_t* row_bounds, float m
     for (int q = 0; q < world; q++)
         if (row_bounds[q] > row_bounds[q + 1]) return S2D_E_INVALID;
     if (int rc = use_device(c)) return rc;
-    if (int rc = compact_flush(c)) return rc;
-    S2D_HIP(c, launch_halo_masks(c->d_splats, c->d_held, c->n, world, row_bounds, margin_rows, masks_device, c->stream));
+    SplatState::Arrays now;
+    S2D_HIP(c, c->state.current(&now));
+    S2D_HIP(c, launch_halo_masks(now.splats, c->state.held(), c->n, world, row_bounds, margin_rows, masks_device, c->stream));
     return S2D_OK;
 }
 
@@ -1099,38 +998,27 @@ int s2d_halo_commit(s2d_ctx* c, const uint32_t* masks_device, int32_t rank, int3
     if (masks_device && c->ref_order)
         return fail(c, S2D_E_INVALID, "reference order (S2D_CFG_REFERENCE_ORDER) has no slab ownership: the chains run over all splats");
     if (int rc = use_device(c)) return rc;
-    if (int rc = compact_off(c)) return rc;
-    if (!masks_device) { // back to holding every splat (the caller has made this context's copy complete again)
-        if (c->d_held) {
-            S2D_HIP(c, hipStreamSynchronize(c->stream));
-            c->d_held.release(), c->d_held_ids.release(), c->d_held_work.release(), c->d_held_count.release();
-            invalidate(c, Stale::Lists);
-        }
-        return S2D_OK;
-    }
-    const bool first = !c->d_held;
-    if (first) {
-        S2D_HIP(c, c->d_held.alloc((size_t)c->n));
-        S2D_HIP(c, c->d_held_ids.alloc((size_t)c->n));
-        S2D_HIP(c, c->d_held_work.alloc((size_t)c->n));
-        S2D_HIP(c, c->d_held_count.alloc(4));
-    }
-    S2D_HIP(c, launch_halo_commit(masks_device, c->n, rank, c->d_held, c->d_held_ids, c->d_held_count, c->d_held_work,
-                                  c->d_scan_temp, c->stream));
-    if (int rc = compact_load(c)) return rc;
-    // splats arrived: project the held ones and rebuild the tile lists before the next forward
-    if (added || first) invalidate(c, Stale::Lists);
+    const bool had = c->state.held() != nullptr;
+    S2D_HIP(c, c->state.commit(masks_device, rank, c->d_scan_temp));
+    // the lists hold the held splats only.  Splats arrived, or this is the first held set: project the held ones and
+    // rebuild the lists before the next forward; so on the return to holding everything
+    if (masks_device ? (added || !had) : had) invalidate(c, Stale::Lists);
     return S2D_OK;
 }
 
+// The array of a row call and its row width, on the context's device: the gradients, or the state's arrays with
+// everything queued so far in them.
 static int rows_base(s2d_ctx* c, int32_t what, float** base, int* w)
 {
-    switch (what) {
-    case S2D_ROWS_GRADS: *base = c->d_grads; *w = 9; return S2D_OK;
-    case S2D_ROWS_SPLATS: *base = c->d_splats; *w = 9; return S2D_OK;
-    case S2D_ROWS_ADAM: *base = c->d_adams; *w = 18; return S2D_OK;
-    default: return S2D_E_INVALID;
-    }
+    if (what != S2D_ROWS_GRADS && what != S2D_ROWS_SPLATS && what != S2D_ROWS_ADAM) return S2D_E_INVALID;
+    if (int rc = use_device(c)) return rc;
+    *base = c->d_grads;
+    *w = what == S2D_ROWS_ADAM ? 18 : 9;
+    if (what == S2D_ROWS_GRADS) return S2D_OK;
+    SplatState::Arrays now;
+    S2D_HIP(c, c->state.current(&now));
+    *base = what == S2D_ROWS_SPLATS ? now.splats : now.adams;
+    return S2D_OK;
 }
 
 int s2d_rows_gather(s2d_ctx* c, int32_t what, const int32_t* ids_device, int32_t count, float* out_device)
@@ -1139,9 +1027,6 @@ int s2d_rows_gather(s2d_ctx* c, int32_t what, const int32_t* ids_device, int32_t
     float* base;
     int w;
     if (int rc = rows_base(c, what, &base, &w)) return rc;
-    if (int rc = use_device(c)) return rc;
-    if (what != S2D_ROWS_GRADS)
-        if (int rc = compact_flush(c)) return rc;
     S2D_HIP(c, launch_rows_gather(base, w, ids_device, count, c->n, out_device, c->stream));
     return S2D_OK;
 }
@@ -1152,12 +1037,8 @@ int s2d_rows_scatter(s2d_ctx* c, int32_t what, const int32_t* ids_device, int32_
     float* base;
     int w;
     if (int rc = rows_base(c, what, &base, &w)) return rc;
-    if (int rc = use_device(c)) return rc;
-    if (what != S2D_ROWS_GRADS)
-        if (int rc = compact_flush(c)) return rc;
     S2D_HIP(c, launch_rows_scatter(base, w, ids_device, count, c->n, in_device, c->stream));
-    if (what != S2D_ROWS_GRADS)
-        if (int rc = state_written(c, false)) return rc;
+    if (what != S2D_ROWS_GRADS) S2D_HIP(c, c->state.written(false));
     if (what == S2D_ROWS_SPLATS) invalidate(c, Stale::Projection); // parameters changed behind the projection
     return S2D_OK;
 }
@@ -1173,10 +1054,9 @@ int s2d_grads_combine(s2d_ctx* c, const int32_t* rows_device, int32_t n_rows, co
 
 int s2d_get_sqerr_trace(s2d_ctx* c, int32_t first_iteration, int32_t count, double* out)
 {
-    if (!c || !out || count < 0 || first_iteration < 0 || count > c->trace_cap) return S2D_E_INVALID;
+    if (!c || !out || count < 0 || first_iteration < 0 || count > SqerrTrace::kCapacity) return S2D_E_INVALID;
     if (int rc = use_device(c)) return rc;
-    if (int rc = flush_sqerr(c)) return rc;
-    if (int rc = queue_trace_read(c, first_iteration, count, out)) return rc;
+    S2D_HIP(c, c->trace.read(first_iteration, count, out));
     S2D_HIP(c, hipStreamSynchronize(c->stream));
     return S2D_OK;
 }

@@ -118,13 +118,11 @@ __global__ __launch_bounds__(256) void tile_offsets_kernel(const uint32_t* __res
     for (int t = prev + 1; t <= cur; t++) tile_off[t] = p;
 }
 
-hipError_t launch_project(const float* splats, const uint8_t* held, int n, Geometry g, float margin, int mode, ProjRec* proj,
-                          TileRect* rects, uint32_t* counts, uint32_t* row_counts, DeviceStatus* status, int check_stamp,
-                          int* host_stamp, hipStream_t stream)
+hipError_t launch_project(const ProjectArgs& a, hipStream_t stream)
 {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(project_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, splats, held, n, g, margin, mode, proj,
-                       rects, counts, row_counts, status, check_stamp, host_stamp);
+    if (a.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(project_kernel, dim3((a.n + 255) / 256), dim3(256), 0, stream, a.splats, a.held, a.n, a.g, a.margin, a.mode,
+                       a.proj, a.check.rects, a.counts, a.row_counts, a.check.status, a.check.stamp, a.check.host_stamp);
     return hipGetLastError();
 }
 

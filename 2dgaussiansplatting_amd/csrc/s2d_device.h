@@ -155,13 +155,31 @@ size_t tile_first_temp_words(int num_keys);
 hipError_t launch_tile_offsets_from_first(const uint32_t* tile_first, int num_keys, uint32_t total, uint32_t* temp,
                                           uint32_t* tile_off, hipStream_t stream);
 
+// What a containment check works with: the rectangles the tile lists were built from, and the stamp it leaves in the
+// device word (status->rebin_needed) and the host-mapped word if a splat's exact rectangle has left its binned one.
+struct ContainmentCheck {
+    TileRect* rects = nullptr;
+    DeviceStatus* status = nullptr;
+    int stamp = 0;
+    int* host_stamp = nullptr;
+};
+
 // binning (s2d_binning.hip)
-// Projects every splat; mode 0: also writes rects[] (inflated by `margin` pixels) and counts[];
-// mode 1: checks that the exact rectangle lies inside rects[] and raises status->rebin_needed otherwise.
-// (mode 0, row_counts != nullptr: also the number of tile rows each rectangle covers)
-hipError_t launch_project(const float* splats, const uint8_t* held, int n, Geometry g, float margin, int mode, ProjRec* proj,
-                          TileRect* rects, uint32_t* counts, uint32_t* row_counts, DeviceStatus* status, int check_stamp,
-                          int* host_stamp, hipStream_t stream);
+// Projects every splat; mode 0: also writes check.rects[] (inflated by `margin` pixels) and counts[] (row_counts !=
+// nullptr: also the number of tile rows each rectangle covers); mode 1: the containment check against check.rects[].
+struct ProjectArgs {
+    const float* splats = nullptr;
+    const uint8_t* held = nullptr; // slab ownership: 1 = held; splats of other ranks have no footprint here (nullptr: all)
+    int n = 0;
+    Geometry g{};
+    float margin = 0.0f;
+    int mode = 0;
+    ProjRec* proj = nullptr;
+    uint32_t* counts = nullptr;
+    uint32_t* row_counts = nullptr;
+    ContainmentCheck check{};
+};
+hipError_t launch_project(const ProjectArgs& a, hipStream_t stream);
 // one (tile row, splat) entry per row of every splat's rectangle, in splat order, at the scanned row offsets
 hipError_t launch_emit_row_entries(const TileRect* rects, const uint32_t* row_offsets, const uint32_t* row_counts, int n,
                                    uint32_t* keys, uint32_t* vals, uint32_t capacity, hipStream_t stream);
@@ -367,18 +385,31 @@ hipError_t launch_sqerr_finalize(SqerrJob sq, const DeviceStatus* status, int it
 
 // optimiser / init (s2d_optim.hip)
 hipError_t launch_init_splats(float* splats, float* adams, int n, int W, int H, hipStream_t stream);
-// proj != nullptr: also project the UPDATED splat for the next iteration and check it against rects[]
-// (what project_kernel mode 1 would do), raising status->rebin_needed.
+// proj != nullptr: also project the UPDATED splat for the next iteration and run the containment check on it (what
+// project_kernel mode 1 would do).  check.status also takes the finite guard's verdict.
 // dormant (n bytes, or nullptr): dormant[i] = 1 while every Adam moment of splat i is zero -- maintained by the kernel,
 // cleared by whoever else writes splats or moments; a block whose splats are all dormant and received zero gradients skips
 // the step, which would leave them bit for bit as they are.
 // compact (only with held_ids): splats / adams are the COMPACT arrays of the held splats, record h = splat held_ids[h]:
 // whole lines instead of one gathered record per splat; gradients, projection and `dormant` stay indexed by splat id.
-hipError_t launch_adam(float* splats, float* adams, float* grads, const uint32_t* held_ids, const uint32_t* held_count, int n,
-                       Geometry g, float beta1t, float beta2t,
-                       float lr, int optimize_opacity, int iteration, DeviceStatus* status, ProjRec* proj,
-                       const TileRect* rects, int check_stamp, int* host_stamp, uint8_t* dormant, SqerrJob sq,
-                       bool compact, hipStream_t stream);
+struct AdamArgs {
+    float* splats = nullptr;
+    float* adams = nullptr;
+    float* grads = nullptr;
+    const uint32_t* held_ids = nullptr;   // slab ownership: the held splats, ascending, *held_count of them (nullptr: all)
+    const uint32_t* held_count = nullptr;
+    int n = 0;
+    Geometry g{};
+    float beta1t = 1.0f, beta2t = 1.0f, lr = 0.0f;
+    int mode = 0;                          // bit 0: optimise the opacity; bit 1: fp32 quotient (S2D_CFG_ADAM_FP32)
+    int iteration = 0;
+    ProjRec* proj = nullptr;
+    ContainmentCheck check{};
+    uint8_t* dormant = nullptr;
+    SqerrJob sq{};                         // the launch's first workgroups also add up the tile errors
+    bool compact = false;
+};
+hipError_t launch_adam(const AdamArgs& a, hipStream_t stream);
 // image_ref: rows [row_begin, row_end) of the W x H target
 hipError_t launch_synthetic_target(void* image_ref, bool half_images, int W, int H, int row_begin, int row_end, hipStream_t stream);
 // RGBA32F <-> 4 x fp16 (round to nearest even) for images that cross the boundary as floats

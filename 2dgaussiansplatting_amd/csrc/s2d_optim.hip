@@ -274,16 +274,13 @@ hipError_t launch_init_splats(float* splats, float* adams, int n, int W, int H, 
     return hipGetLastError();
 }
 
-hipError_t launch_adam(float* splats, float* adams, float* grads, const uint32_t* held_ids, const uint32_t* held_count,
-                       int n, Geometry g, float beta1t, float beta2t,
-                       float lr, int optimize_opacity, int iteration, DeviceStatus* status, ProjRec* proj,
-                       const TileRect* rects, int check_stamp, int* host_stamp, uint8_t* dormant, SqerrJob sq,
-                       bool compact, hipStream_t stream)
+hipError_t launch_adam(const AdamArgs& a, hipStream_t stream)
 {
-    if (n <= 0) return hipSuccess; // (callers queue the standalone squared-error reduction themselves when n == 0)
-    hipLaunchKernelGGL(adam_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, splats, adams, grads, held_ids, held_count, n, g,
-                       beta1t, beta2t, lr, optimize_opacity, iteration, status, proj, rects, check_stamp, host_stamp, dormant, sq,
-                       (compact && held_ids) ? 1 : 0);
+    if (a.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(adam_kernel, dim3((a.n + 255) / 256), dim3(256), 0, stream, a.splats, a.adams, a.grads, a.held_ids,
+                       a.held_count, a.n, a.g, a.beta1t, a.beta2t, a.lr, a.mode, a.iteration, a.check.status, a.proj,
+                       (const TileRect*)a.check.rects, a.check.stamp, a.check.host_stamp, a.dormant, a.sq,
+                       (a.compact && a.held_ids) ? 1 : 0);
     return hipGetLastError();
 }
 

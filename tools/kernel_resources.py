@@ -2,7 +2,7 @@
 
     python tools/kernel_resources.py report [csrc_dir] > new.json     (no GPU needed: hipcc -Rpass-analysis=kernel-resource-usage)
     python tools/kernel_resources.py compare old.json new.json
-    python tools/kernel_resources.py asm old_csrc_dir [new_csrc_dir]
+    python tools/kernel_resources.py asm old_csrc_dir [new_csrc_dir] [unit.hip ...]
 
 compare: every kernel instantiation of `old` must be in `new` with the same SGPRs, VGPRs, AGPRs, scratch, LDS and occupancy
 (exit status 1 otherwise); instantiations only `new` has are listed.  A kernel that gained a trailing template flag is
@@ -11,6 +11,8 @@ symbol and must change nothing else.  The order in which variants are instantiat
 unrelated kernels before (s2d_raster.hip, with_variant), which is what this is run for.
 asm: the device assembly (--offload-device-only -S) of every kernel of the old tree against the same kernel of the new one,
 comments dropped and local labels unnumbered: which are instruction for instruction the same (exit status 1 if one is not).
+Of the named translation units, by default of every one the build compiles (_build.HIP_SOURCES); a unit that only one of
+the trees has counts as one without kernels there.
 """
 import json
 import os
@@ -39,6 +41,8 @@ def _plain(names):
 def assembly(csrc, source="s2d_raster.hip"):
     """{kernel: its instructions as text} of one translation unit."""
     build, flags = _build_flags()
+    if not os.path.exists(os.path.join(csrc, source)):
+        return {}
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "out.s")
         subprocess.run([build.hipcc()] + [f for f in flags if f != "-fPIC"] + ["-I", os.path.join(ROOT, "include"), "--offload-device-only",
@@ -53,7 +57,7 @@ def assembly(csrc, source="s2d_raster.hip"):
     return {p: bodies[n] for n, p in zip(names, _plain(names))}
 
 
-def compare_assembly(old, new):
+def compare_assembly(old, new, label=""):
     same, changed = 0, []
     for name, want in sorted(old.items()):
         got = new.get(name, new.get(name[:-1] + ", false>") if name.endswith(">") else None)
@@ -61,7 +65,7 @@ def compare_assembly(old, new):
             same += 1
         else:
             changed.append(name)
-    print("%d of %d kernels of the old tree instruction for instruction the same (%d kernels in the new tree)" % (same, len(old), len(new)))
+    print("%s%d of %d kernels of the old tree instruction for instruction the same (%d kernels in the new tree)" % (label, same, len(old), len(new)))
     for n in changed:
         print("  CHANGED: " + n)
     return not changed
@@ -115,8 +119,11 @@ if __name__ == "__main__":
         json.dump(report(csrc), sys.stdout, indent=1, sort_keys=True)
     elif len(sys.argv) == 4 and sys.argv[1] == "compare":
         sys.exit(0 if compare(json.load(open(sys.argv[2])), json.load(open(sys.argv[3]))) else 1)
-    elif len(sys.argv) in (3, 4) and sys.argv[1] == "asm":
-        new = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "2dgaussiansplatting_amd", "csrc")
-        sys.exit(0 if compare_assembly(assembly(sys.argv[2]), assembly(new)) else 1)
+    elif len(sys.argv) >= 3 and sys.argv[1] == "asm":
+        dirs = [a for a in sys.argv[3:] if not a.endswith(".hip")]
+        units = [a for a in sys.argv[3:] if a.endswith(".hip")] or _build_flags()[0].HIP_SOURCES
+        new = dirs[0] if dirs else os.path.join(ROOT, "2dgaussiansplatting_amd", "csrc")
+        same = [compare_assembly(assembly(sys.argv[2], u), assembly(new, u), "%-20s " % u) for u in units]
+        sys.exit(0 if all(same) else 1)
     else:
         sys.exit(__doc__)
