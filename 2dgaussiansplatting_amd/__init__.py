@@ -75,7 +75,7 @@ ABI_SYMBOLS = [
     "s2d_bind_grads_device", "s2d_grads_device_ptr", "s2d_stream", "s2d_get_sqerr_trace", "s2d_synchronize", "s2d_get_stats",
     "s2d_get_rebuild_count",
     "s2d_last_error", "s2d_test_sincos", "s2d_test_sort_pairs", "s2d_test_exclusive_scan",
-    "s2d_debug_get_tile_lists",
+    "s2d_test_sort_tile_offsets", "s2d_debug_get_tile_lists",
     "s2d_halo_masks", "s2d_halo_commit", "s2d_rows_gather", "s2d_rows_scatter", "s2d_grads_combine",
     "s2d_multi_create", "s2d_multi_destroy", "s2d_multi_last_error", "s2d_multi_device_count", "s2d_multi_set_target",
     "s2d_multi_set_target_synthetic", "s2d_multi_init_splats", "s2d_multi_set_splats", "s2d_multi_get_splats",
@@ -244,6 +244,7 @@ def load_library(path=None):
     sig("s2d_test_sincos", [i32, vp, i32, vp, vp])
     sig("s2d_test_sort_pairs", [i32, vp, vp, i64, i32])
     sig("s2d_test_exclusive_scan", [i32, vp, i64, vp])
+    sig("s2d_test_sort_tile_offsets", [i32, vp, vp, i64, i32, vp])
     sig("s2d_debug_get_tile_lists", [vp, vp, vp, vp, i64, vp, i64])
     sig("s2d_halo_masks", [vp, i32, vp, C.c_float, vp])
     sig("s2d_halo_commit", [vp, vp, i32, i32])

@@ -1168,6 +1168,38 @@ int s2d_test_sort_pairs(int32_t device, uint32_t* keys, uint32_t* values, int64_
     return S2D_OK;
 }
 
+// The generic builder's last steps (TileLists::finish): the sort whose last pass records where every key's pairs begin
+// instead of writing the sorted keys, then the offsets from those.  Keys must be tile ids, < num_keys: the last pass
+// indexes tile_first with the whole key.
+int s2d_test_sort_tile_offsets(int32_t device, const uint32_t* keys, uint32_t* values, int64_t n, int32_t num_keys,
+                               uint32_t* tile_off)
+{
+    if (!keys || !values || !tile_off || n < 0 || n > 0xFFFFFFFFll || num_keys < 2 || num_keys > (1 << 30)) return S2D_E_INVALID;
+    for (int64_t i = 0; i < n; i++)
+        if (keys[i] >= (uint32_t)num_keys) return S2D_E_INVALID;
+    int key_bits = 0;
+    while ((1 << key_bits) < num_keys) key_bits++;
+    DevBuf<uint32_t> k[2], v[2], temp, first, off;
+    uint32_t *ko = nullptr, *vo = nullptr;
+    S2D_HIP(nullptr, hipSetDevice(device));
+    for (int i = 0; i < 2; i++) {
+        S2D_HIP(nullptr, k[i].alloc((size_t)n));
+        S2D_HIP(nullptr, v[i].alloc((size_t)n));
+    }
+    S2D_HIP(nullptr, temp.alloc(sort_temp_words(n)));
+    S2D_HIP(nullptr, first.alloc(((size_t)1 << key_bits) + tile_first_temp_words(num_keys)));
+    S2D_HIP(nullptr, off.alloc((size_t)num_keys + 1));
+    S2D_HIP(nullptr, hipMemcpy(k[0], keys, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    S2D_HIP(nullptr, hipMemcpy(v[0], values, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    S2D_HIP(nullptr, hipMemsetAsync(first, 0xFF, ((size_t)1 << key_bits) * sizeof(uint32_t), nullptr));
+    S2D_HIP(nullptr, sort_pairs_u32(k[0], v[0], k[1], v[1], n, key_bits, temp, &ko, &vo, first, nullptr));
+    S2D_HIP(nullptr, launch_tile_offsets_from_first(first, num_keys, (uint32_t)n, first + ((size_t)1 << key_bits), off, nullptr));
+    S2D_HIP(nullptr, hipDeviceSynchronize());
+    S2D_HIP(nullptr, hipMemcpy(values, vo, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    S2D_HIP(nullptr, hipMemcpy(tile_off, off, ((size_t)num_keys + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return S2D_OK;
+}
+
 int s2d_test_exclusive_scan(int32_t device, uint32_t* data, int64_t n, uint64_t* total)
 {
     if (!data || n < 0) return S2D_E_INVALID;

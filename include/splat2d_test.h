@@ -18,6 +18,11 @@ extern "C" {
 int s2d_test_sincos(int32_t device, const float* x, int32_t n, float* sin_out, float* cos_out);
 /* Stable LSD radix sort of (key, value) pairs by the low `key_bits` bits of key, on the GPU. */
 int s2d_test_sort_pairs(int32_t device, uint32_t* keys, uint32_t* values, int64_t n, int32_t key_bits);
+/* The same sort in the form the generic list builder uses it: keys are tile ids below num_keys, the last pass records
+ * where each key's pairs begin instead of writing the sorted keys.  values come back in stable key order, tile_off
+ * (num_keys + 1 entries) holds for every t the first position whose key is >= t, and n at tile_off[num_keys]. */
+int s2d_test_sort_tile_offsets(int32_t device, const uint32_t* keys, uint32_t* values, int64_t n, int32_t num_keys,
+                               uint32_t* tile_off /* num_keys + 1 */);
 /* Exclusive prefix sum on the GPU; returns the total in *total. */
 int s2d_test_exclusive_scan(int32_t device, uint32_t* data, int64_t n, uint64_t* total);
 /* The tile lists the raster kernels walk, for inspection: offsets has tiles+1 entries. */

@@ -84,6 +84,20 @@ def test_create_rejects_bad_configs(lib):
     assert lib.s2d_create(C.byref(cfg), C.byref(h)) == 1
     cfg.row_begin, cfg.row_end = 32, 16
     assert lib.s2d_create(C.byref(cfg), C.byref(h)) == 1
+    # the size limit is 65536 either way: one more is refused, the limit itself is not (without a device the call then
+    # fails where test_no_device_is_a_loud_error_not_a_fallback says, with S2D_E_HIP)
+    cfg.row_begin, cfg.row_end = 0, 0
+    for w, hh in ((65537, 16), (16, 65537)):
+        cfg.width, cfg.height = w, hh
+        h.value = None
+        assert lib.s2d_create(C.byref(cfg), C.byref(h)) == 1 and not h.value
+    for w, hh in ((65536, 16), (16, 65536)):
+        cfg.width, cfg.height = w, hh
+        h.value = None
+        rc = lib.s2d_create(C.byref(cfg), C.byref(h))
+        assert rc == (0 if _gpu_present() else 2), (w, hh, rc)
+        assert h.value
+        lib.s2d_destroy(h)
     assert lib.s2d_create(None, C.byref(h)) == 1
     assert lib.s2d_forward(None) == 1 and lib.s2d_step(None, 1, 0, None) == 1
 

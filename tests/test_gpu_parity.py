@@ -95,8 +95,15 @@ def test_exclusive_scan(n):
     assert tot.value == int(a.sum())
 
 
-@pytest.mark.parametrize("n,bits", [(0, 8), (1, 8), (4095, 8), (4096, 16), (4097, 16), (300_000, 9), (2_000_000, 16), (777_777, 18)])
-def test_radix_sort_stable(n, bits):
+# "high": random bits above the key, which the sort must carry along and not look at -- the row sort of the two-level list
+# builder at its widths (9, 11 and 12 row bits under 18 bits of column range, csrc/s2d_lists.hip)
+_SORT_CASES = [(0, 8), (1, 8), (4095, 8), (4096, 16), (4097, 16), (300_000, 9), (2_000_000, 16), (777_777, 18)]
+_SORT_CASES_HIGH = [(1, 9), (4097, 9), (300_000, 9), (4097, 11), (300_000, 11), (4097, 12), (300_000, 12)]
+
+
+@pytest.mark.parametrize("n,bits,high", [(n, b, False) for n, b in _SORT_CASES] + [(n, b, True) for n, b in _SORT_CASES_HIGH],
+                         ids=["%d-%d" % c for c in _SORT_CASES] + ["%d-%d-high" % c for c in _SORT_CASES_HIGH])
+def test_radix_sort_stable(n, bits, high):
     L = S2D.load_library()
     import ctypes as C
     rng = np.random.default_rng(n + bits)
@@ -105,10 +112,53 @@ def test_radix_sort_stable(n, bits):
         keys[: n // 3] = keys[0]  # long runs of one tile
     vals = np.arange(n, dtype=np.uint32)  # emission order
     order = np.argsort(keys, kind="stable")
+    if high:  # the same order, by the low bits alone; the keys come back whole
+        keys |= rng.integers(0, 1 << (32 - bits), n, dtype=np.uint32) << np.uint32(bits)
+        assert n < 10 or len(np.unique(keys >> np.uint32(bits))) > 1
     k, v = keys.copy(), vals.copy()
     assert L.s2d_test_sort_pairs(0, k.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), n, bits) == 0
     assert np.array_equal(k, keys[order])
     assert np.array_equal(v, vals[order])  # stability: equal keys keep emission (= splat index) order
+
+
+def _tile_keys(dist, n, num_keys, rng):
+    third = -(-num_keys // 3)
+    if dist == "uniform":
+        return rng.integers(0, num_keys, n, dtype=np.uint32)
+    if dist == "one_key":             # the highest one: every digit's top value, and every tile in front of it empty
+        return np.full(n, num_keys - 1, dtype=np.uint32)
+    if dist == "empty_first_third":
+        return rng.integers(third, num_keys, n, dtype=np.uint32)
+    if dist == "empty_last_third":    # the trailing empty tiles take the total
+        return rng.integers(0, num_keys - third, n, dtype=np.uint32)
+    runs = rng.integers(1, 9000, n // 4000 + 2)     # long runs: across the sort's blocks of 4096 items
+    while runs.sum() < n:
+        runs = np.concatenate([runs, runs])
+    return np.repeat(rng.integers(0, num_keys, len(runs), dtype=np.uint32), runs)[:n]
+
+
+@pytest.mark.parametrize("dist", ["uniform", "one_key", "empty_first_third", "empty_last_third", "long_runs"])
+@pytest.mark.parametrize("num_keys", [2, 1023, 1024, 1025, 4096, 65536, 66049, (1 << 20) + 1])
+def test_sort_with_tile_offsets(num_keys, dist):
+    """The sort as the generic list builder runs it (s2d_test_sort_tile_offsets): the last radix pass -- of 1, 2, 3, 4, 5 or 8
+    bits here -- records where each tile's pairs begin instead of writing the keys, and launch_tile_offsets_from_first turns
+    that into the offsets -- chunks of 1024 keys: one, exactly one, one and a key, many.  Against numpy: the values in
+    stable key order, tile_off[t] = first position whose key is >= t."""
+    L = S2D.load_library()
+    import ctypes as C
+    for n in (0, 1, 4097, 300_000):
+        rng = np.random.default_rng(num_keys + n)
+        keys = _tile_keys(dist, n, num_keys, rng)
+        assert keys.shape == (n,) and (n == 0 or keys.max() < num_keys)
+        order = np.argsort(keys, kind="stable")
+        want_off = np.searchsorted(keys[order], np.arange(num_keys + 1)).astype(np.uint32)
+        v = np.arange(n, dtype=np.uint32)
+        off = np.full(num_keys + 1, 0xDEADBEEF, dtype=np.uint32)
+        assert L.s2d_test_sort_tile_offsets(0, keys.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), n, num_keys,
+                                            off.ctypes.data_as(C.c_void_p)) == 0
+        assert np.array_equal(v, order.astype(np.uint32)), (n, "values")
+        assert np.array_equal(off, want_off), (n, "offsets")
+        assert off[0] == 0 and off[-1] == n
 
 
 def test_trig_bitwise():
