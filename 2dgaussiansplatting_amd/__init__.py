@@ -26,6 +26,7 @@ SPLAT_DTYPE = np.dtype([("pos", "<f4", 2), ("sx", "<f4"), ("sy", "<f4"), ("rot",
 ADAM_DTYPE = np.dtype([("mv", "<f4", (9, 2))])
 
 S2D_STEP_OPTIMIZE_OPACITY = 0x1
+S2D_STEP_DENSITY_STATS = 0x2
 S2D_CFG_COUNT_PAIRS = 0x1
 S2D_CFG_FP16_IMAGES = 0x2
 S2D_CFG_DETERMINISTIC = 0x4
@@ -35,6 +36,7 @@ S2D_CFG_GENERIC_BINNING = 0x20
 S2D_CFG_REFERENCE_ORDER = 0x40
 S2D_BWD_SKIP_OPACITY_GRAD = 0x1
 S2D_FB_SKIP_IMAGE = 0x2
+S2D_BWD_DENSITY_STATS = 0x4
 STATUS_NAMES = {0: "S2D_OK", 1: "S2D_E_INVALID", 2: "S2D_E_HIP", 3: "S2D_E_NONFINITE", 4: "S2D_E_NOMEM",
                 5: "S2D_E_STATE"}
 
@@ -50,6 +52,10 @@ class _Config(C.Structure):
                 ("n_splats", C.c_int32), ("device", C.c_int32), ("row_begin", C.c_int32),
                 ("row_end", C.c_int32), ("training_rate", C.c_float), ("flags", C.c_uint32),
                 ("rebin_interval", C.c_int32), ("rebin_margin", C.c_float), ("stream", C.c_void_p)]
+
+
+class _RelocateConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_moves", C.c_int32), ("min_weight", C.c_float), ("shrink", C.c_float)]
 
 
 ROWS_GRADS, ROWS_SPLATS, ROWS_ADAM = 0, 1, 2  # S2D_ROWS_* (row arrays of the slab-ownership calls)
@@ -73,7 +79,7 @@ ABI_SYMBOLS = [
     "s2d_init_splats", "s2d_set_splats", "s2d_get_splats", "s2d_set_adam", "s2d_get_adam", "s2d_forward",
     "s2d_get_image", "s2d_get_image_rows", "s2d_backward", "s2d_backward_image_grads", "s2d_set_splats_device", "s2d_get_image_rows_device", "s2d_forward_backward", "s2d_get_grads", "s2d_adam_step", "s2d_step", "s2d_get_mse",
     "s2d_bind_grads_device", "s2d_grads_device_ptr", "s2d_stream", "s2d_get_sqerr_trace", "s2d_synchronize", "s2d_get_stats",
-    "s2d_get_rebuild_count",
+    "s2d_get_rebuild_count", "s2d_density_get", "s2d_density_get_device", "s2d_density_reset", "s2d_relocate",
     "s2d_last_error", "s2d_test_sincos", "s2d_test_sort_pairs", "s2d_test_exclusive_scan",
     "s2d_test_sort_tile_offsets", "s2d_debug_get_tile_lists",
     "s2d_halo_masks", "s2d_halo_commit", "s2d_rows_gather", "s2d_rows_scatter", "s2d_grads_combine",
@@ -231,6 +237,10 @@ def load_library(path=None):
     sig("s2d_get_image_rows_device", [vp, vp])
     sig("s2d_get_grads", [vp, vp])
     sig("s2d_adam_step", [vp, u32])
+    sig("s2d_density_get", [vp, vp, vp])
+    sig("s2d_density_get_device", [vp, vp, vp])
+    sig("s2d_density_reset", [vp])
+    sig("s2d_relocate", [vp, C.POINTER(_RelocateConfig), vp])
     sig("s2d_step", [vp, i32, u32, vp])
     sig("s2d_get_mse", [vp, vp])
     sig("s2d_bind_grads_device", [vp, vp])
@@ -406,12 +416,14 @@ class Trainer:
         self._ck(self.L.s2d_get_image_rows(self._h, _p(a)))
         return a
 
-    def backward(self, skip_opacity_grad=None):
+    def backward(self, skip_opacity_grad=None, density_stats=False):
         """Backward pass.  skip_opacity_grad=None: skip dSplats.opacity exactly when optimize_opacity is off and
-        `lean_backward` was requested (bench / training loops); False: always compute it, as the reference does."""
+        `lean_backward` was requested (bench / training loops); False: always compute it, as the reference does.
+        density_stats: the pass also accumulates the density statistics (S2D_BWD_DENSITY_STATS, density())."""
         if skip_opacity_grad is None:
             skip_opacity_grad = self.lean_backward and not self.optimize_opacity
-        self._ck(self.L.s2d_backward(self._h, S2D_BWD_SKIP_OPACITY_GRAD if skip_opacity_grad else 0))
+        self._ck(self.L.s2d_backward(self._h, (S2D_BWD_SKIP_OPACITY_GRAD if skip_opacity_grad else 0) |
+                                     (S2D_BWD_DENSITY_STATS if density_stats else 0)))
 
     def forward_backward(self, skip_opacity_grad=None, skip_image=False):
         """forward() + backward() in one launch per tile (same results); skip_opacity_grad as backward();
@@ -436,22 +448,50 @@ class Trainer:
         """The slab's rows of image0 into device memory, always RGBA32F (s2d_get_image_rows_device)."""
         self._ck(self.L.s2d_get_image_rows_device(self._h, C.c_void_p(ptr) if ptr else None))
 
-    def backward_image_grads(self, ptr, skip_opacity_grad=None):
+    def backward_image_grads(self, ptr, skip_opacity_grad=None, density_stats=False):
         """Backward pass from the caller's dL/d(image0) (device pointer, the slab's rows, RGBA32F, .w ignored) instead of
-        image0 - imageRef; skip_opacity_grad as backward()."""
+        image0 - imageRef; skip_opacity_grad and density_stats as backward()."""
         if skip_opacity_grad is None:
             skip_opacity_grad = self.lean_backward and not self.optimize_opacity
         self._ck(self.L.s2d_backward_image_grads(self._h, C.c_void_p(ptr) if ptr else None,
-                                                 S2D_BWD_SKIP_OPACITY_GRAD if skip_opacity_grad else 0))
+                                                 (S2D_BWD_SKIP_OPACITY_GRAD if skip_opacity_grad else 0) |
+                                                 (S2D_BWD_DENSITY_STATS if density_stats else 0)))
 
     def adam_step(self):
         self._ck(self.L.s2d_adam_step(self._h, self._flags()))
 
-    def step(self, iters=1, want_mse=True):
-        """iters whole iterations; returns the MSE values the reference would print (main.cpp:807)."""
+    def step(self, iters=1, want_mse=True, density_stats=False):
+        """iters whole iterations; returns the MSE values the reference would print (main.cpp:807).  density_stats: every
+        iteration is a statistics pass (S2D_STEP_DENSITY_STATS: the separate launches instead of the fused one)."""
         out = np.zeros(iters, dtype=np.float64) if want_mse else None
-        self._ck(self.L.s2d_step(self._h, int(iters), self._flags(), _p(out) if want_mse else None))
+        flags = self._flags() | (S2D_STEP_DENSITY_STATS if density_stats else 0)
+        self._ck(self.L.s2d_step(self._h, int(iters), flags, _p(out) if want_mse else None))
         return out
+
+    # -- density control (include/splat2d.h, "density control")
+    def density(self):
+        """-> ((n, 3) float32: sum |dpos.x|, sum |dpos.y|, sum T * alpha over the accumulated passes, and their number)."""
+        a = np.zeros((self.n, 3), dtype=np.float32)
+        passes = C.c_int32()
+        self._ck(self.L.s2d_density_get(self._h, _p(a), C.byref(passes)))
+        return a, passes.value
+
+    def density_device(self, ptr):
+        """The same n x 3 floats into device memory, queued on the context's stream; returns the number of passes."""
+        passes = C.c_int32()
+        self._ck(self.L.s2d_density_get_device(self._h, C.c_void_p(ptr) if ptr else None, C.byref(passes)))
+        return passes.value
+
+    def density_reset(self):
+        self._ck(self.L.s2d_density_reset(self._h))
+
+    def relocate(self, max_moves, min_weight, shrink=0.0):
+        """s2d_relocate: starved splats (weight per pass < min_weight) onto halves of the splats with the largest summed
+        |dpos|; returns the number of pairs moved.  The statistics are reset."""
+        cfg = _RelocateConfig(C.sizeof(_RelocateConfig), int(max_moves), float(min_weight), float(shrink))
+        moved = C.c_int32()
+        self._ck(self.L.s2d_relocate(self._h, C.byref(cfg), C.byref(moved)))
+        return moved.value
 
     def mse(self):
         v = C.c_double()

@@ -23,6 +23,7 @@
 #include <new>
 
 #include "s2d_device.h"
+#include "s2d_density.h" // (behind s2d_device.h: s2d_math.h's qualifiers need the HIP runtime header under hipcc)
 #include "s2d_lists.h"
 #include "s2d_owned.h"
 #include "s2d_state.h"
@@ -92,6 +93,7 @@ struct s2d_ctx {
     bool half_images = false;
     size_t pixel_bytes = sizeof(float4);
     SqerrTrace trace;          // the tile errors of a backward pass and the ring of per-iteration sums (s2d_state.h)
+    DensityStats density;      // what the passes with S2D_BWD_DENSITY_STATS accumulated (s2d_state.h)
     DevBuf<DeviceStatus> d_status;
     DevBuf<PairCounters> d_counters;
     // pinned host mirrors
@@ -498,18 +500,33 @@ int queue_backward_reference(s2d_ctx* c, bool need_opacity_grad, const float4* u
     return backward_queued(c, SqerrBy::PassItself);
 }
 
+// A context whose configuration has no density-statistics walk (the STATS kernels exist without pair counting and the
+// exact exponential; reference order has kernels of its own).
+int density_refused(s2d_ctx* c)
+{
+    if ((c->cfg.flags & (S2D_CFG_COUNT_PAIRS | S2D_CFG_EXACT_EXP)) || c->ref_order)
+        return fail(c, S2D_E_INVALID, "density statistics are not available with S2D_CFG_COUNT_PAIRS, S2D_CFG_EXACT_EXP or "
+                    "S2D_CFG_REFERENCE_ORDER");
+    return S2D_OK;
+}
+
 // upstream != nullptr (s2d_backward_image_grads): the walk starts from the caller's dL/d(image0) instead of
 // image0 - imageRef.  The loss is the caller's, so no squared error is formed or queued: the trace ring and a sum still
 // waiting for the next Adam launch stay as the last s2d_backward left them (SqerrBy::NoLoss).
-int queue_backward(s2d_ctx* c, bool need_opacity_grad, const float4* upstream = nullptr)
+// density (S2D_BWD_DENSITY_STATS; density_refused() has been asked): the walk also accumulates the density statistics.
+int queue_backward(s2d_ctx* c, bool need_opacity_grad, const float4* upstream = nullptr, bool density = false)
 {
     if (!c->have_forward) return fail(c, S2D_E_STATE, "the backward pass needs s2d_forward on the current parameters");
     if (c->ref_order) return queue_backward_reference(c, need_opacity_grad, upstream);
+    if (density && !c->chunks.empty())
+        return fail(c, S2D_E_NOMEM, "density statistics are not available for scenes beyond %llu (tile, splat) pairs (index-range rendering)",
+                    (unsigned long long)c->chunk_pairs);
     if (!c->chunks.empty()) { // the forward pass went over index ranges: so does this one
         if (int rc = chunked_backward(c, need_opacity_grad, upstream)) return rc;
     } else {
         RasterArgs a = raster_args(c);
         a.upstream = upstream;
+        if (density) S2D_HIP(c, c->density.next_pass(&a.density));
         with_backward_walk(c, a, need_opacity_grad);
         S2D_HIP(c, launch_raster(RasterPass::Backward, a, c->stream));
     }
@@ -675,6 +692,7 @@ int s2d_create(const s2d_config* cfg, s2d_ctx** out)
     S2D_HIP(c, hipMemset(c->d_retire_hint, 0xFF, (size_t)g.num_tiles * sizeof(uint32_t)));
     S2D_HIP(c, c->d_status.alloc(1));
     S2D_HIP(c, c->trace.create(g.num_tiles, c->n, c->d_status, c->stream));
+    c->density.create(c->n, c->stream);
     S2D_HIP(c, c->d_counters.alloc(1));
     S2D_HIP(c, c->ev_flag.create(hipEventDisableTiming));
     S2D_HIP(c, c->h_status.alloc(1, hipHostMallocDefault));
@@ -749,6 +767,7 @@ int s2d_init_splats(s2d_ctx* c)
     S2D_HIP(c, launch_init_splats(all.splats, all.adams, c->n, c->g.W, c->g.H, c->stream));
     if (int rc = splats_replaced(c)) return rc;
     if (c->n > 0) S2D_HIP(c, hipMemsetAsync(c->d_grads, 0, (size_t)c->n * 9 * sizeof(float), c->stream));
+    S2D_HIP(c, c->density.reset()); // (statistics of splats that no longer exist)
     c->beta1t = c->good_beta1t = 1.0f; // main.cpp:283-284
     c->beta2t = c->good_beta2t = 1.0f;
     c->iterations = c->good_iterations = 0; // main.cpp:281
@@ -849,6 +868,8 @@ int s2d_get_image(s2d_ctx* c, float* rgba32f)
 int s2d_forward_backward(s2d_ctx* c, uint32_t flags)
 {
     if (!c) return S2D_E_INVALID;
+    if (flags & S2D_BWD_DENSITY_STATS)
+        return fail(c, S2D_E_INVALID, "the fused launch has no density-statistics variant: s2d_forward, then s2d_backward with the flag");
     if (int rc = use_device(c)) return rc;
     return queue_forward_backward(c, !(flags & S2D_BWD_SKIP_OPACITY_GRAD), !(flags & S2D_FB_SKIP_IMAGE));
 }
@@ -856,8 +877,11 @@ int s2d_forward_backward(s2d_ctx* c, uint32_t flags)
 int s2d_backward(s2d_ctx* c, uint32_t flags)
 {
     if (!c) return S2D_E_INVALID;
+    const bool density = (flags & S2D_BWD_DENSITY_STATS) != 0;
+    if (density)
+        if (int rc = density_refused(c)) return rc;
     if (int rc = use_device(c)) return rc;
-    return queue_backward(c, !(flags & S2D_BWD_SKIP_OPACITY_GRAD));
+    return queue_backward(c, !(flags & S2D_BWD_SKIP_OPACITY_GRAD), nullptr, density);
 }
 
 int s2d_backward_image_grads(s2d_ctx* c, const float* dimage_rows_device, uint32_t flags)
@@ -866,8 +890,11 @@ int s2d_backward_image_grads(s2d_ctx* c, const float* dimage_rows_device, uint32
     if ((uintptr_t)dimage_rows_device & 15u) return fail(c, S2D_E_INVALID, "the image gradient must be 16-byte aligned");
     if (c->cfg.flags & S2D_CFG_COUNT_PAIRS)
         return fail(c, S2D_E_INVALID, "pair counting (S2D_CFG_COUNT_PAIRS) has no backward pass from a caller's image gradient");
+    const bool density = (flags & S2D_BWD_DENSITY_STATS) != 0;
+    if (density)
+        if (int rc = density_refused(c)) return rc;
     if (int rc = use_device(c)) return rc;
-    return queue_backward(c, !(flags & S2D_BWD_SKIP_OPACITY_GRAD), reinterpret_cast<const float4*>(dimage_rows_device));
+    return queue_backward(c, !(flags & S2D_BWD_SKIP_OPACITY_GRAD), reinterpret_cast<const float4*>(dimage_rows_device), density);
 }
 
 int s2d_set_splats_device(s2d_ctx* c, const float* splats_device)
@@ -905,6 +932,94 @@ int s2d_get_grads(s2d_ctx* c, s2d_splat* dsplats)
     return S2D_OK;
 }
 
+int s2d_density_get_device(s2d_ctx* c, float* out_device, int32_t* passes)
+{
+    if (!c || (!out_device && c->n)) return S2D_E_INVALID;
+    if (int rc = use_device(c)) return rc;
+    const size_t bytes = (size_t)c->n * sizeof(s2d_density);
+    if (bytes && c->density.data()) S2D_HIP(c, hipMemcpyAsync(out_device, c->density.data(), bytes, hipMemcpyDeviceToDevice, c->stream));
+    else if (bytes) S2D_HIP(c, hipMemsetAsync(out_device, 0, bytes, c->stream));
+    if (passes) *passes = c->density.passes();
+    return S2D_OK;
+}
+
+int s2d_density_get(s2d_ctx* c, s2d_density* host, int32_t* passes)
+{
+    if (!c) return S2D_E_INVALID;
+    if (int rc = use_device(c)) return rc;
+    const size_t bytes = (size_t)c->n * sizeof(s2d_density);
+    if (host && bytes && c->density.data()) {
+        S2D_HIP(c, hipMemcpyAsync(host, c->density.data(), bytes, hipMemcpyDeviceToHost, c->stream));
+        S2D_HIP(c, hipStreamSynchronize(c->stream));
+    } else if (host && bytes) {
+        std::memset(host, 0, bytes);
+    }
+    if (passes) *passes = c->density.passes();
+    return S2D_OK;
+}
+
+int s2d_density_reset(s2d_ctx* c)
+{
+    if (!c) return S2D_E_INVALID;
+    if (int rc = use_device(c)) return rc;
+    S2D_HIP(c, c->density.reset());
+    return S2D_OK;
+}
+
+int s2d_relocate(s2d_ctx* c, const s2d_relocate_config* cfg, int32_t* moved)
+{
+    if (!c || !cfg || cfg->struct_size != sizeof(s2d_relocate_config)) return S2D_E_INVALID;
+    if (moved) *moved = 0;
+    const float shrink = cfg->shrink == 0.0f ? 1.6f : cfg->shrink;
+    if (cfg->max_moves < 0 || !(shrink > 0.0f) || std::isinf(shrink) || std::isnan(cfg->min_weight))
+        return fail(c, S2D_E_INVALID, "s2d_relocate: max_moves >= 0, a finite shrink > 0 (0: 1.6) and a min_weight that is a number");
+    if (c->g.row_begin != 0 || c->g.row_end != c->g.H)
+        return fail(c, S2D_E_INVALID, "s2d_relocate needs the statistics of the whole image: this context owns a row slab");
+    if (c->state.held()) return fail(c, S2D_E_INVALID, "s2d_relocate: this context holds a subset of the splats (s2d_halo_commit)");
+    if (c->ref_order) return fail(c, S2D_E_INVALID, "s2d_relocate is not available with S2D_CFG_REFERENCE_ORDER");
+    const int passes = c->density.passes();
+    if (passes == 0) return fail(c, S2D_E_STATE, "s2d_relocate needs a pass with S2D_BWD_DENSITY_STATS since the last reset");
+    if (int rc = use_device(c)) return rc;
+    const size_t n = (size_t)c->n;
+    std::vector<float> stats(n * 3), splats(n * 9), adams(n * 18);
+    std::vector<int32_t> ids(2 * std::min<size_t>((size_t)cfg->max_moves, n));
+    SplatState::Arrays now;
+    S2D_HIP(c, c->state.current(&now));
+    if (n > 0) {
+        S2D_HIP(c, hipMemcpyAsync(stats.data(), c->density.data(), n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        S2D_HIP(c, hipMemcpyAsync(splats.data(), now.splats, n * 9 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        S2D_HIP(c, hipMemcpyAsync(adams.data(), now.adams, n * 18 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    S2D_HIP(c, hipStreamSynchronize(c->stream));
+    const int moves = density_plan(c->n, stats.data(), passes, cfg->max_moves, cfg->min_weight, shrink, c->g.W, c->g.H, splats.data(),
+                                   adams.data(), ids.data());
+    if (moves > 0) { // the changed rows, through the row calls' scatter
+        const size_t rows = 2 * (size_t)moves;
+        std::vector<float> srows(rows * 9), arows(rows * 18);
+        for (size_t r = 0; r < rows; r++) {
+            std::memcpy(&srows[r * 9], &splats[(size_t)ids[r] * 9], 9 * sizeof(float));
+            std::memcpy(&arows[r * 18], &adams[(size_t)ids[r] * 18], 18 * sizeof(float));
+        }
+        DevBuf<int32_t> d_ids;
+        DevBuf<float> d_srows, d_arows;
+        S2D_HIP(c, d_ids.alloc(rows));
+        S2D_HIP(c, d_srows.alloc(rows * 9));
+        S2D_HIP(c, d_arows.alloc(rows * 18));
+        const IdleAtExit idle{c->stream}; // (before the three go)
+        S2D_HIP(c, hipMemcpyAsync(d_ids, ids.data(), rows * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        S2D_HIP(c, hipMemcpyAsync(d_srows, srows.data(), rows * 9 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        S2D_HIP(c, hipMemcpyAsync(d_arows, arows.data(), rows * 18 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        S2D_HIP(c, launch_rows_scatter(now.splats, 9, d_ids, (int)rows, c->n, d_srows, c->stream));
+        S2D_HIP(c, launch_rows_scatter(now.adams, 18, d_ids, (int)rows, c->n, d_arows, c->stream));
+        S2D_HIP(c, c->state.written(false));
+        invalidate(c, Stale::Projection); // (as s2d_rows_scatter: the containment check asks for new lists where a row left its rectangle)
+        S2D_HIP(c, hipStreamSynchronize(c->stream)); // (the host copies are read by the stream until here)
+    }
+    S2D_HIP(c, c->density.reset());
+    if (moved) *moved = moves;
+    return S2D_OK;
+}
+
 int s2d_adam_step(s2d_ctx* c, uint32_t flags)
 {
     if (!c) return S2D_E_INVALID;
@@ -916,6 +1031,9 @@ int s2d_adam_step(s2d_ctx* c, uint32_t flags)
 int s2d_step(s2d_ctx* c, int32_t iters, uint32_t flags, double* mse_out)
 {
     if (!c || iters < 0) return S2D_E_INVALID;
+    const bool density = (flags & S2D_STEP_DENSITY_STATS) != 0;
+    if (density)
+        if (int rc = density_refused(c)) return rc;
     if (int rc = use_device(c)) return rc;
     const double norm = mse_norm(c);
     const int call_first_iter = c->iterations;
@@ -927,7 +1045,12 @@ int s2d_step(s2d_ctx* c, int32_t iters, uint32_t flags, double* mse_out)
         for (int k = 0; k < chunk; k++) {
             // image0 is stored by the last iteration of the call only: nothing else could observe the others
             const bool last = done + k + 1 == iters;
-            if (int rc = queue_forward_backward(c, (flags & S2D_STEP_OPTIMIZE_OPACITY) != 0, last)) return rc;
+            if (density) { // the separate passes: only s2d_backward's kernel gathers the statistics (image0 stored every time)
+                if (int rc = queue_forward(c)) return rc;
+                if (int rc = queue_backward(c, (flags & S2D_STEP_OPTIMIZE_OPACITY) != 0, nullptr, true)) return rc;
+            } else if (int rc = queue_forward_backward(c, (flags & S2D_STEP_OPTIMIZE_OPACITY) != 0, last)) {
+                return rc;
+            }
             if (int rc = queue_adam(c, flags)) return rc;
         }
         const bool last_chunk = done + chunk == iters;

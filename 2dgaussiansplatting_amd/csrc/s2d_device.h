@@ -232,6 +232,9 @@ struct RasterArgs {
     // Backward, BackwardRange (not with `count`): the caller's dL/d(image0) for the rows of the slab, RGBA32F whatever the
     // image format, .w ignored -- the walk starts from it instead of image0 - image_ref and forms no squared error
     const float4* upstream = nullptr;
+    // Backward only (not with `count` or `exact_exp`): n x 3 floats, per splat (sum |dpos.x|, sum |dpos.y|, sum T * alpha) over
+    // the pixels of the slab; the walk ACCUMULATES into it next to the gradients (the STATS kernels)
+    float* density = nullptr;
     // forward -> backward walk: lane masks and splat indices of the entries the forward walk executed, compacted to the
     // front of each tile's list range, and their number per tile (s2d_raster.hip forward_tile)
     unsigned long long* wave_masks = nullptr;

@@ -564,7 +564,9 @@ struct DetSlots {
 // LDS of the backward walk.  Entries per staged batch: 64, or 32 in deterministic mode, whose four per-wave slot sets would
 // otherwise lift the workgroup from 18.9 to ~25 KB of LDS -- six instead of eight workgroups per CU, which alone costs
 // ~14 % (profiles/r03/r03_bound_experiments.txt); with half-size batches it is 17.1 KB.
-template <bool DET>
+// STATS (the density-statistics walk): a slot also carries |dpos.x|, |dpos.y| and the blend weight in
+// words 9..11, so deterministic mode's per-wave slots are 12 floats too (18.6 KB); nothing else changes.
+template <bool DET, bool STATS = false>
 struct BwdShared {
     static constexpr int kBatch = DET ? 32 : B;
     float4 q0[kBatch]; // pos.x, pos.y, a, b
@@ -578,7 +580,7 @@ struct BwdShared {
     // per entry with ds_add_f32 (eight lanes, eight addresses per wave and entry): the order of those four
     // additions is as free as the order of the global atomics that follow, and 9 KB less LDS per workgroup is
     // one to two more resident workgroups per CU.  The flush zeroes what it read.
-    static constexpr int kPartStride = DET ? 9 : 12; // floats per slot (deterministic mode packs its four slots per entry tightly)
+    static constexpr int kPartStride = (DET && !STATS) ? 9 : 12; // floats per slot (deterministic mode packs its four slots per entry tightly)
     __attribute__((aligned(16))) float part[(DET ? 4 : 1) * kBatch * kPartStride];
     // Splat index of each staged entry: the flush addresses gradients without going back to the list.  Two copies, by batch
     // parity: a batch's flush runs behind the last barrier of the batch, so fast threads already stage the NEXT batch
@@ -603,17 +605,22 @@ struct BwdShared {
 // has a body to run in some wave; a counting walk (COUNT) goes through the tile's whole list and ignores both.
 // CHUNK: as in forward_tile -- the list is one index range of the splats, *state_io (running colour r, g, b and T of
 // main.cpp:601-625, :707) is the pixel's state after the ranges before it on entry and after this range on return.
-template <bool COUNT, bool NEED_OP, bool DET, bool EXACT, bool CHUNK = false, bool UPSTREAM = false>
-__device__ __forceinline__ void backward_tile(BwdShared<DET>& s, const TileCtx& c, const float4 fin, const float4 dL,
+// STATS: next to the nine gradients the walk sums |g_px|, |g_py| and alpha * T (the blend weight, main.cpp:618) of every
+// (pixel, splat) the reference's body reaches -- words 9..11 of the same slots, flushed into `stats` (n x 3 floats, float
+// atomics) or, in deterministic mode, into words 9..11 of the tile's global slot for gather_stats_kernel.
+template <bool COUNT, bool NEED_OP, bool DET, bool EXACT, bool CHUNK = false, bool UPSTREAM = false, bool STATS = false>
+__device__ __forceinline__ void backward_tile(BwdShared<DET, STATS>& s, const TileCtx& c, const float4 fin, const float4 dL,
                                               const uint32_t* __restrict__ tile_off, const uint32_t* __restrict__ list,
                                               const ProjRec* __restrict__ proj,
                                               const unsigned long long* __restrict__ wave_masks,
                                               const uint32_t* __restrict__ exec_list, uint32_t n_handed,
                                               float* __restrict__ grads, double* __restrict__ tile_sqerr,
                                               const Geometry& g, const DetSlots& det, PairCounters* __restrict__ counters,
-                                              const SqerrJob& sq, float4* state_io = nullptr)
+                                              const SqerrJob& sq, float4* state_io = nullptr, float* __restrict__ stats = nullptr)
 {
-    constexpr int BB = BwdShared<DET>::kBatch; // entries per staged batch
+    using Shared = BwdShared<DET, STATS>;
+    constexpr int BB = Shared::kBatch;      // entries per staged batch
+    constexpr int KF = STATS ? 12 : 9;      // floats of a slot the flush moves
     const int tid = c.tid, lane = c.lane, w = c.w;
     const bool inside = c.inside;
     const f2 pxy = c.pxy;
@@ -730,6 +737,7 @@ __device__ __forceinline__ void backward_tile(BwdShared<DET>& s, const TileCtx& 
                     if (lane == 0) atomicAdd(&counters->bwd_quadrant_execs, (unsigned long long)nq);
                 }
                 float g_px, g_py, g_sx, g_sy, g_rot, g_r, g_g, g_b, g_op = 0.f;
+                float st_w = 0.f; // STATS: alpha * T of this pixel
                 {
                     const float4 q0 = s.q0[e], q1 = s.q1[e], q2 = s.q2[e];
                     const float4 e0 = s.e0[e], e1 = s.e1[e];
@@ -752,6 +760,7 @@ __device__ __forceinline__ void backward_tile(BwdShared<DET>& s, const TileCtx& 
                     g_r = g_rg.x;
                     g_g = g_rg.y;
                     g_b = dLb * dC_dc;
+                    if constexpr (STATS) st_w = dC_dc;
                     // S / (1 - alpha + 1e-15), main.cpp:627-628: three quotients over one denominator (div_by_recip)
                     const float den = 1.0f - alpha + 1.0e-15f;
                     const float rd = __builtin_amdgcn_rcpf(den); // 1 ulp; the correction below does the rest
@@ -789,13 +798,24 @@ __device__ __forceinline__ void backward_tile(BwdShared<DET>& s, const TileCtx& 
                 // v_mad_u64_u32 in the blend loop.
                 float* const part = s.part;
                 int pe;
-                asm("s_mul_i32 %0, %1, %2" : "=s"(pe) : "s"((DET ? __builtin_amdgcn_readfirstlane(w) : 0) * BB + e), "n"(BwdShared<DET>::kPartStride));
+                asm("s_mul_i32 %0, %1, %2" : "=s"(pe) : "s"((DET ? __builtin_amdgcn_readfirstlane(w) : 0) * BB + e), "n"(Shared::kPartStride));
                 if (DET) {
                     if ((lane & 7) == 0) part[pe + part_slot] = tot;
                     if (NEED_OP && lane == 63) part[pe + 8] = g_op;
                 } else {
                     const float val = op_lane ? g_op : tot; // one LDS instruction for the eight totals and the ninth sum
                     if (adds) __hip_atomic_fetch_add(part + (pe + part_slot), val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+                if constexpr (STATS) {
+                    // a second round of the same transpose: the totals of |g_px|, |g_py| and alpha * T end in the 8-lane
+                    // groups 0..2 (lanes outside the reference's body hold exact zeros: every term is a multiple of alpha)
+                    float none = 0.f;
+                    const float st = wave_sum8_lds<false>(s.xpose[w], lane, __builtin_fabsf(g_px), __builtin_fabsf(g_py), st_w, 0.f, 0.f,
+                                                          0.f, 0.f, 0.f, none);
+                    if ((lane & 7) == 0 && lane < 24) {
+                        if (DET) part[pe + 9 + (lane >> 3)] = st;
+                        else __hip_atomic_fetch_add(part + (pe + 9 + (lane >> 3)), st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
                 }
             }
         }
@@ -806,8 +826,8 @@ __device__ __forceinline__ void backward_tile(BwdShared<DET>& s, const TileCtx& 
         else __syncthreads();
         // one burst per (tile, splat): 9 consecutive floats -- float atomics into grads[idx], or (deterministic
         // mode) plain stores into this tile's own slot of the splat, summed later in a fixed order
-        for (int i = tid; i < cnt * 9; i += 256) {
-            const int e = i / 9, k = i - e * 9;
+        for (int i = tid; i < cnt * KF; i += 256) {
+            const int e = i / KF, k = i - e * KF;
             if (!NEED_OP && k == 8 && !DET) continue; // dSplats.opacity left at zero on request
             float v = 0.0f;
             bool any_w = false;
@@ -815,11 +835,11 @@ __device__ __forceinline__ void backward_tile(BwdShared<DET>& s, const TileCtx& 
 #pragma unroll
                 for (int ww = 0; ww < (DET ? 4 : 1); ww++)
                     if ((s.touched[ww] >> e) & 1ull) {
-                        v += s.part[(ww * BB + e) * BwdShared<DET>::kPartStride + k];
+                        v += s.part[(ww * BB + e) * Shared::kPartStride + k];
                         any_w = true;
                     }
             } else {
-                float* slot = s.part + e * BwdShared<DET>::kPartStride + k;
+                float* slot = s.part + e * Shared::kPartStride + k;
                 v = *slot;
                 *slot = 0.0f; // the next batch's waves add after the staging barrier
                 any_w = true;
@@ -834,7 +854,8 @@ __device__ __forceinline__ void backward_tile(BwdShared<DET>& s, const TileCtx& 
                     }
                 }
             } else if (any_w && v != 0.0f) {
-                atomicAdd(grads + (size_t)s.idx[pb][e] * 9 + k, v);
+                if (STATS && k >= 9) atomicAdd(stats + (size_t)s.idx[pb][e] * 3 + (k - 9), v);
+                else atomicAdd(grads + (size_t)s.idx[pb][e] * 9 + k, v);
             }
         }
         if (!any) break;
@@ -848,8 +869,14 @@ __device__ __forceinline__ void backward_tile(BwdShared<DET>& s, const TileCtx& 
     }
 }
 
+// The per-splat statistics array of a STATS kernel (n x 3 floats) is one trailing argument that only those kernels have:
+// the argument list of every other instantiation, and with it the kernel as the compiler emits it, stays what it was.
+__device__ __forceinline__ float* stats_of() { return nullptr; }
+__device__ __forceinline__ float* stats_of(float* p) { return p; }
+
 // UPSTREAM (both backward kernels): image_ref is not the target but the caller's dL/d(image0), see load_ref_or_upstream.
-template <bool COUNT, bool NEED_OP, bool HALF, bool DET, bool EXACT, bool UPSTREAM = false>
+// STATS: backward_tile's density statistics (never with COUNT or EXACT).
+template <bool COUNT, bool NEED_OP, bool HALF, bool DET, bool EXACT, bool UPSTREAM = false, bool STATS = false, typename... STATS_OUT>
 __global__ __launch_bounds__(256) void raster_backward_kernel(const uint32_t* __restrict__ tile_off,
                                                               const uint32_t* __restrict__ list,
                                                               const ProjRec* __restrict__ proj,
@@ -861,9 +888,11 @@ __global__ __launch_bounds__(256) void raster_backward_kernel(const uint32_t* __
                                                               float* __restrict__ grads,
                                                               double* __restrict__ tile_sqerr, Geometry g,
                                                               DetSlots det, const DeviceStatus* __restrict__ status,
-                                                              int iteration, PairCounters* __restrict__ counters)
+                                                              int iteration, PairCounters* __restrict__ counters,
+                                                              STATS_OUT... stats_out)
 {
-    __shared__ BwdShared<DET> s;
+    static_assert(sizeof...(STATS_OUT) == (STATS ? 1 : 0) && !(STATS && (COUNT || EXACT)), "float* stats for the STATS kernels alone");
+    __shared__ BwdShared<DET, STATS> s;
     if (launch_is_void(status, 0, iteration)) return; // the reference abort()ed in an earlier iteration
     const int tile = tile_of_block(blockIdx.x, g);
     if (tile < 0) return;
@@ -874,8 +903,8 @@ __global__ __launch_bounds__(256) void raster_backward_kernel(const uint32_t* __
         ref = load_ref_or_upstream<HALF, UPSTREAM>(image_ref, pixel_index(c, g));
     }
     const uint32_t n_exec = COUNT ? 0u : tile_exec[tile];
-    backward_tile<COUNT, NEED_OP, DET, EXACT, false, UPSTREAM>(s, c, fin, loss_grad<UPSTREAM>(fin, ref), tile_off, list, proj, wave_masks, exec_list, n_exec, grads, tile_sqerr,
-                                              g, det, counters, SqerrJob{nullptr, 0, nullptr, nullptr});
+    backward_tile<COUNT, NEED_OP, DET, EXACT, false, UPSTREAM, STATS>(s, c, fin, loss_grad<UPSTREAM>(fin, ref), tile_off, list, proj, wave_masks, exec_list, n_exec, grads, tile_sqerr,
+                                              g, det, counters, SqerrJob{nullptr, 0, nullptr, nullptr}, nullptr, stats_of(stats_out...));
 }
 
 // Forward and backward walk of a tile in ONE launch (what s2d_step and s2d_forward_backward queue): a tile's backward
@@ -1074,6 +1103,43 @@ __global__ __launch_bounds__(256) void gather_grads_kernel(const uint32_t* __res
     for (int k = 0; k < 9; k++) gr[k] += acc[k]; // += : the buffer is zero here unless the caller accumulates slabs
 }
 
+// Deterministic mode, density statistics: words 9..11 of the same slots, in the same order, into stats[i] (n x 3, accumulated
+// over passes).  Runs BEFORE gather_grads_kernel, which clears the `touched` words both read: the statistics ride in the
+// gradient slots of their own pass, so a slot is read here exactly when that pass wrote all twelve of its words.
+__global__ __launch_bounds__(256) void gather_stats_kernel(const uint32_t* __restrict__ offsets,
+                                                           const uint32_t* __restrict__ counts, int n,
+                                                           const float* __restrict__ data,
+                                                           const uint32_t* __restrict__ stamp,
+                                                           const uint32_t* __restrict__ touched, uint32_t now,
+                                                           float* __restrict__ stats)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t m = touched[i];
+    if (m == 0u) return;
+    float acc[3] = {0.f, 0.f, 0.f};
+    const uint32_t o = offsets[i];
+    const bool tail = (m >> 31) != 0u;
+    m &= 0x7FFFFFFFu;
+    while (m != 0u) { // ascending slot order
+        const uint32_t j = (uint32_t)__builtin_ctz(m);
+        m &= m - 1u;
+        const float4 c = reinterpret_cast<const float4*>(data + (size_t)(o + j) * kDetStride)[2];
+        acc[0] += c.y; acc[1] += c.z; acc[2] += c.w;
+    }
+    if (tail) {
+        const uint32_t cnt = counts[i];
+        for (uint32_t s = o + 31u; s < o + cnt; s++)
+            if (stamp[s] == now) {
+                const float4 c = reinterpret_cast<const float4*>(data + (size_t)s * kDetStride)[2];
+                acc[0] += c.y; acc[1] += c.z; acc[2] += c.w;
+            }
+    }
+    float* st = stats + (size_t)i * 3;
+#pragma unroll
+    for (int k = 0; k < 3; k++) st[k] += acc[k];
+}
+
 // Sum of the per-tile squared errors in a fixed order (deterministic MSE trace), two stages in one launch:
 // kSqerrChunks blocks each reduce a contiguous chunk to partial[b] (sqerr_reduce, s2d_device.h); the block that finishes last (ticket counter)
 // adds the partials, again in a fixed order, and re-arms the counter.  scratch = kSqerrChunks doubles + one
@@ -1122,7 +1188,10 @@ hipError_t launch_raster(RasterPass pass, const RasterArgs& a, hipStream_t strea
     const std::false_type no; // a flag the pass has no variants of
     const std::true_type yes;
     hipError_t e = hipErrorInvalidValue;
-    if (a.upstream == nullptr) switch (pass) {
+    const bool stats = a.density != nullptr;
+    if (stats) {
+        // (dispatched at the end of this function)
+    } else if (a.upstream == nullptr) switch (pass) {
     case RasterPass::Forward:
         e = with_variant([&](auto exact, auto count, auto half) {
             hipLaunchKernelGGL((raster_forward_kernel<count, half, exact>), grid, block, 0, stream, a.tile_off, a.list, a.proj,
@@ -1175,7 +1244,19 @@ hipError_t launch_raster(RasterPass pass, const RasterArgs& a, hipStream_t strea
                                a.proj, a.image0, a.upstream, a.state, first, a.wave_masks, a.exec_list, a.grads, nullptr, a.g, det,
                                a.status, a.iteration);
         }, a.exact_exp, no, a.half_images, a.need_opacity_grad, gather, yes);
+    // The density-statistics walk (a.density): the separate backward kernel only, from the reference's loss or a caller's
+    // gradient, without pair counting or the exact exponential.  Behind everything else for the same reason as above.
+    if (stats && pass == RasterPass::Backward && !a.count && !a.exact_exp)
+        e = with_variant([&](auto, auto, auto half, auto op, auto d, auto up, auto st) {
+            hipLaunchKernelGGL((raster_backward_kernel<false, op, half, d, false, up, st>), grid, block, 0, stream, a.tile_off, a.list,
+                               a.proj, a.image0, up ? (const void*)a.upstream : a.image_ref, a.wave_masks, a.exec_list, a.tile_exec,
+                               a.grads, up ? nullptr : a.tile_sqerr, a.g, det, a.status, a.iteration, nullptr,
+                               a.density);
+        }, no, no, a.half_images, a.need_opacity_grad, gather, a.upstream != nullptr, yes);
     if (e != hipSuccess) return e;
+    if (stats && gather && dg.n > 0)
+        hipLaunchKernelGGL(gather_stats_kernel, dim3((dg.n + 255) / 256), dim3(256), 0, stream, dg.offsets, dg.counts, dg.n,
+                           dg.data, dg.stamp, dg.touched, dg.now, a.density);
     if (gather && dg.n > 0)
         hipLaunchKernelGGL(gather_grads_kernel, dim3((dg.n + 255) / 256), dim3(256), 0, stream, dg.offsets, dg.counts, dg.n,
                            dg.data, dg.stamp, dg.touched, dg.now, a.grads);

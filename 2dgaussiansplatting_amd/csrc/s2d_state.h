@@ -100,4 +100,23 @@ private:
     bool waiting_ = false; // the sum of iteration last_ rides on the next Adam launch
 };
 
+// Per-splat density statistics (S2D_BWD_DENSITY_STATS): n x 3 floats -- sum |dL/dpos.x|, sum |dL/dpos.y|,
+// sum T * alpha over the pixels of the slab and the passes since the last reset -- and the number of those passes.  Allocated
+// (zeroed) by the first pass that asks, so a context that never does pays nothing.
+class S2D_LOCAL DensityStats {
+public:
+    void create(int n, hipStream_t stream) { n_ = n, stream_ = stream; }
+    // The array a statistics pass about to be queued accumulates into; counts the pass.
+    hipError_t next_pass(float** out);
+    hipError_t reset(); // zeros (queued), passes = 0
+    int passes() const { return passes_; }
+    const float* data() const { return buf_; } // null: no pass has asked yet (all zeros)
+    int n() const { return n_; }
+
+private:
+    int n_ = 0, passes_ = 0;
+    hipStream_t stream_ = nullptr;
+    DevBuf<float> buf_;
+};
+
 } // namespace s2d

@@ -147,4 +147,21 @@ hipError_t SqerrTrace::read(int first, int count, double* out)
     return hipSuccess;
 }
 
+hipError_t DensityStats::next_pass(float** out)
+{
+    if (!buf_) {
+        S2D_TRY(buf_.alloc((size_t)n_ * 3));
+        S2D_TRY(hipMemsetAsync(buf_, 0, buf_.capacity() * sizeof(float), stream_));
+    }
+    passes_++;
+    *out = buf_;
+    return hipSuccess;
+}
+
+hipError_t DensityStats::reset()
+{
+    passes_ = 0;
+    return buf_ ? hipMemsetAsync(buf_, 0, buf_.capacity() * sizeof(float), stream_) : hipSuccess;
+}
+
 } // namespace s2d

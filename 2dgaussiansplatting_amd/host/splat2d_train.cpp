@@ -55,6 +55,12 @@ struct Options {
     int stall_ms = -1;          // --stall-timeout-ms (multi-device handle): how long a rank may not answer before the step fails
     int gpus = 1;               // --gpus N: devices device .. device + N - 1, one row slab each, RCCL all-reduce of the gradients
     bool share_gpu = false;     // --share-gpu: all N ranks on --device (rehearsal on a box with fewer GPUs than ranks)
+    // Density control (include/splat2d.h "density control"; one context only).  The defaults of the window, the fraction and
+    // the weight are PROVISIONAL: nobody has measured them yet.
+    int relocate_every = 0;          // --relocate-every K: s2d_relocate before iteration K, 2K, ... (0: never, the reference's loop)
+    int relocate_window = 10;        // --relocate-window S: the last S iterations before each relocation gather the statistics
+    float relocate_max_fraction = 0.05f; // --relocate-max-fraction f: at most f * splats moved per relocation
+    float relocate_min_weight = 0.5f;    // --relocate-min-weight w: a splat whose sum of T * alpha per pass is below w is starved
     bool replicated = false;    // --exchange dense: replicated state + RCCL all-reduce of all gradients (default: slab ownership)
                                 // (RCCL takes one rank per GPU): a rehearsal of the N-rank host logic on a box with fewer GPUs
 };
@@ -76,7 +82,11 @@ int usage()
                  "       splat2d_train --convert in.(s2di|ppm|png|jpg) out.(s2di|ppm|png)\n"
                  "                     [--load-checkpoint file] [--save-checkpoint file]\n"
                  "                     [--lr RATE] [--deterministic] [--reference-order] [--device D] [--gpus N [--exchange halo|dense] [--share-gpu]\n"
-                 "                     [--stall-timeout-ms MS]] [--rebin-interval R] [--quiet]\n");
+                 "                     [--stall-timeout-ms MS]] [--rebin-interval R] [--quiet]\n"
+                 "                     [--relocate-every K [--relocate-window S] [--relocate-max-fraction F] [--relocate-min-weight W]]\n"
+                 "  --relocate-every K: before iteration K, 2K, ... move the starved splats (summed T * alpha per pass below W) onto\n"
+                 "    halves of the splats with the largest summed |dL/dpos|, from statistics of the S iterations before, at most\n"
+                 "    F * splats at a time (one GPU only).  Defaults S = 10, F = 0.05, W = 0.5 are provisional: not measured yet.\n");
     return 2;
 }
 
@@ -204,6 +214,10 @@ int main(int argc, char** argv)
         else if (a == "--deterministic") o.deterministic = true;
         else if (a == "--reference-order") o.reference_order = true;
         else if (a == "--stall-timeout-ms") o.stall_ms = std::atoi(next("--stall-timeout-ms"));
+        else if (a == "--relocate-every") o.relocate_every = std::atoi(next("--relocate-every"));
+        else if (a == "--relocate-window") o.relocate_window = std::atoi(next("--relocate-window"));
+        else if (a == "--relocate-max-fraction") o.relocate_max_fraction = (float)std::atof(next("--relocate-max-fraction"));
+        else if (a == "--relocate-min-weight") o.relocate_min_weight = (float)std::atof(next("--relocate-min-weight"));
         else return usage();
     }
     if (!o.convert_in.empty()) { // file conversion between .s2di / .ppm / .png; touches no GPU
@@ -234,6 +248,11 @@ int main(int argc, char** argv)
     }
 
     if (o.gpus < 1) return usage();
+    if (o.relocate_every < 0 || o.relocate_window < 1 || !(o.relocate_max_fraction >= 0.0f) || !(o.relocate_min_weight >= 0.0f)) return usage();
+    if (o.relocate_every > 0 && (o.gpus > 1 || std::getenv("S2D_TRAIN_FORCE_MULTI"))) {
+        std::fprintf(stderr, "--relocate-every works on one context: the multi-device handle has no relocation\n");
+        return 2;
+    }
     Session S;
     CK(S.create(o, W, H));
     if (S.is_multi && o.stall_ms >= 0) CK(s2d_multi_set_stall_timeout(S.multi, o.stall_ms));
@@ -284,7 +303,28 @@ int main(int argc, char** argv)
         if (o.optimize_opacity && iterations < o.opacity_from && iterations + k > o.opacity_from) k = o.opacity_from - iterations;
         if (o.restart_at > iterations && iterations + k > o.restart_at) k = o.restart_at - iterations;
         const bool opacity_now = o.optimize_opacity && iterations >= o.opacity_from; // bool optimizeOpacity, main.cpp:317
-        CK(S.step(k, opacity_now ? S2D_STEP_OPTIMIZE_OPACITY : 0u, mse.data()));
+        uint32_t density = 0u;
+        if (o.relocate_every > 0) {
+            // iterations [mK - S, mK) gather the statistics; the relocation runs in front of iteration mK
+            const int K = o.relocate_every, S_ = o.relocate_window < K ? o.relocate_window : K;
+            int32_t passes = 0;
+            if (iterations > 0 && iterations % K == 0) CK(s2d_density_get(S.ctx, nullptr, &passes));
+            if (passes > 0) { // (none: the run began here, from a checkpoint or a Restart)
+                s2d_relocate_config rc;
+                rc.struct_size = sizeof(rc);
+                rc.max_moves = (int32_t)(o.relocate_max_fraction * (float)o.n_splats);
+                rc.min_weight = o.relocate_min_weight;
+                rc.shrink = 0.0f;
+                int32_t moved = 0;
+                CK(s2d_relocate(S.ctx, &rc, &moved));
+                std::fprintf(stderr, "relocated %d splats before iteration %d\n", (int)moved, iterations);
+            }
+            const int next_reloc = (iterations / K + 1) * K, window_begin = next_reloc - S_;
+            if (iterations >= window_begin) density = S2D_STEP_DENSITY_STATS;
+            else if (iterations + k > window_begin) k = window_begin - iterations;
+            if (iterations + k > next_reloc) k = next_reloc - iterations;
+        }
+        CK(S.step(k, (opacity_now ? S2D_STEP_OPTIMIZE_OPACITY : 0u) | density, mse.data()));
         if (!o.quiet)
             for (int j = 0; j < k; j++) std::printf("%d itr, mse %.4f\n", iterations + j, mse[(size_t)j]); // main.cpp:807
         iterations += k; // main.cpp:809

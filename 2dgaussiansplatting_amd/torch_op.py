@@ -77,23 +77,35 @@ class SplatRenderer:
         self.trainer.forward()
         self.generation += 1
 
-    def render(self, splats):
+    def render(self, splats, density_stats=False):
         """(n, 9) float32 contiguous tensor on the renderer's device -> the slab's rows of the image, (rows, W, 4), .w = 1;
-        differentiable with respect to `splats`."""
+        differentiable with respect to `splats`.  density_stats: the backward call of this frame also accumulates the
+        density statistics (S2D_BWD_DENSITY_STATS; density() returns them, trainer.relocate() acts on them)."""
         if not (isinstance(splats, torch.Tensor) and splats.dtype == torch.float32 and splats.device == self.device and
                 tuple(splats.shape) == (self.n, 9) and splats.is_contiguous()):
             raise ValueError("render() takes a contiguous float32 tensor of shape (%d, 9) on %s" % (self.n, self.device))
-        return _Render.apply(splats, self)
+        return _Render.apply(splats, self, bool(density_stats))
+
+    def density(self):
+        """-> ((n, 3) float32 tensor: sum |dL/dpos.x|, sum |dL/dpos.y|, sum T * alpha per splat over the accumulated
+        statistics passes, and the number of those passes); queued on the renderer's stream like everything else."""
+        self._check_stream()
+        out = torch.empty((max(self.n, 1), 3), dtype=torch.float32, device=self.device)
+        passes = self.trainer.density_device(out.data_ptr())
+        return out[:self.n], passes
+
+    def density_reset(self):
+        self.trainer.density_reset()
 
 
 class _Render(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, splats, r):
+    def forward(ctx, splats, r, density_stats=False):
         r._check_stream()
         r._draw(splats)
         img = torch.empty((r.rows, r.W, 4), dtype=torch.float32, device=r.device)
         r.trainer.get_image_rows_device(img.data_ptr())
-        ctx.renderer, ctx.generation = r, r.generation
+        ctx.renderer, ctx.generation, ctx.density_stats = r, r.generation, density_stats
         ctx.save_for_backward(splats)
         return img
 
@@ -108,5 +120,5 @@ class _Render(torch.autograd.Function):
             r._draw(splats)
         g = grad_image.to(torch.float32).contiguous()
         r.grads.zero_()
-        r.trainer.backward_image_grads(g.data_ptr(), skip_opacity_grad=False)
-        return r.grads[:r.n].clone(), None
+        r.trainer.backward_image_grads(g.data_ptr(), skip_opacity_grad=False, density_stats=ctx.density_stats)
+        return r.grads[:r.n].clone(), None, None

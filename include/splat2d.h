@@ -73,12 +73,22 @@ typedef enum s2d_status {
 
 /* s2d_step / s2d_adam_step flags */
 #define S2D_STEP_OPTIMIZE_OPACITY 0x1u /* the "Optimize opacity" checkbox, main.cpp:317, :735-738, :825 */
+#define S2D_STEP_DENSITY_STATS 0x2u    /* s2d_step only: these iterations run as s2d_forward, s2d_backward with
+                                        * S2D_BWD_DENSITY_STATS, s2d_adam_step instead of the fused launch -- the same
+                                        * results (bitwise with S2D_CFG_DETERMINISTIC), one statistics pass per iteration.
+                                        * Refused like S2D_BWD_DENSITY_STATS. */
 
 /* s2d_backward / s2d_forward_backward flags */
 #define S2D_BWD_SKIP_OPACITY_GRAD 0x1u /* leave dSplats.opacity at zero.  The reference always accumulates it
                                         * (main.cpp:704) but reads it only when "Optimize opacity" is on (main.cpp:735):
                                         * a caller whose next s2d_adam_step runs without S2D_STEP_OPTIMIZE_OPACITY
                                         * may skip it.  s2d_step does so by itself. */
+#define S2D_BWD_DENSITY_STATS 0x4u     /* s2d_backward, s2d_backward_image_grads: the pass also ACCUMULATES the density
+                                        * statistics of every splat (s2d_density, below) and counts one statistics pass; the
+                                        * gradients come out as without the flag.  S2D_E_INVALID for s2d_forward_backward
+                                        * (the fused launch has no such variant) and for S2D_CFG_COUNT_PAIRS,
+                                        * S2D_CFG_EXACT_EXP and S2D_CFG_REFERENCE_ORDER contexts; S2D_E_NOMEM for a scene
+                                        * rendered by index ranges (see s2d_forward). */
 #define S2D_FB_SKIP_IMAGE 0x2u         /* s2d_forward_backward only: do not store image0 (the backward walk takes the final
                                         * colours from registers); s2d_get_image then returns an older frame.  For training
                                         * loops that never look at it. */
@@ -224,6 +234,43 @@ int s2d_backward_image_grads(s2d_ctx* ctx, const float* dimage_rows_device, uint
  * rectangle) and the status word; the image buffer must be 16-byte aligned. */
 int s2d_set_splats_device(s2d_ctx* ctx, const float* splats_device);     /* n_splats * 9 floats */
 int s2d_get_image_rows_device(s2d_ctx* ctx, float* rgba32f_rows_device); /* always RGBA32F */
+
+/* ---- density control (no counterpart in the reference, whose splat set is frozen at init(), main.cpp:280-305; DESIGN.md
+ * section 12).  Two statistics per splat, gathered by the backward walk where the per-pixel addends exist:
+ *   abs_dpos = sum over pixels of |dL_p/dpos.x|, |dL_p/dpos.y| -- the magnitudes of the addends of main.cpp:654-655, which no
+ *              upstream gradient handed to s2d_backward_image_grads can produce (the sum of magnitudes is not linear in it);
+ *   weight   = sum over pixels of T * alpha (main.cpp:618): how much of the image the splat is responsible for; a splat
+ *              buried below the throughput cut-off (main.cpp:604) has 0 and receives no gradient at all.
+ * Sums over the pixels of the context's slab and over the statistics passes since the last reset; every term is >= 0, so
+ * the values of slab contexts add up to the whole image's.  The buffer exists from the first pass that asks for it. */
+typedef struct s2d_density {
+    float abs_dpos[2];
+    float weight;
+} s2d_density;
+/* host[n_splats] and the number of accumulated passes (either may be NULL).  All zeros and 0 before any statistics pass.
+ * s2d_init_splats resets the statistics; s2d_set_splats and s2d_set_splats_device do not (a caller that moves parameters
+ * decides for itself). */
+int s2d_density_get(s2d_ctx* ctx, s2d_density* host, int32_t* passes);
+/* The same into DEVICE memory (n_splats * 3 floats), queued on the context's stream. */
+int s2d_density_get_device(s2d_ctx* ctx, float* out_device, int32_t* passes);
+int s2d_density_reset(s2d_ctx* ctx);
+/* Moves up to max_moves STARVED splats (weight / passes < min_weight, the lowest first) onto halves of the splats with the
+ * largest |abs_dpos| / passes: the donor's larger scale is divided by `shrink` (0 -> 1.6) and clamped to [1, 1024], the donor
+ * moves half of that along the scale's axis one way, the starved row becomes a copy of it the other way, and the Adam moments
+ * of both are zeroed; everything else, beta1t / beta2t / iterations included, is untouched (the exact rules:
+ * csrc/s2d_density.h, deterministic, no random numbers).  The starved row keeps its INDEX and with it its place in the
+ * blend order (main.cpp:419).  A rare, host-side call: it fetches statistics, parameters and moments, plans on the host,
+ * writes the changed rows back the way s2d_rows_scatter does (projection and lists follow as they do there) and resets the
+ * statistics.  *moved (may be NULL): pairs moved.  S2D_E_STATE without a statistics pass since the last reset;
+ * S2D_E_INVALID for a slab context, a context with a held set (s2d_halo_commit) or S2D_CFG_REFERENCE_ORDER.  The
+ * multi-device handle (s2d_multi) has no relocation: out of scope here. */
+typedef struct s2d_relocate_config {
+    uint32_t struct_size; /* = sizeof(s2d_relocate_config) */
+    int32_t max_moves;    /* >= 0 */
+    float min_weight;     /* per pass; +infinity: every splat counts as starved */
+    float shrink;         /* 0 -> 1.6; otherwise > 0 */
+} s2d_relocate_config;
+int s2d_relocate(s2d_ctx* ctx, const s2d_relocate_config* cfg, int32_t* moved);
 
 /* Adam + constraints + finite guard, main.cpp:714-785, on the current gradient buffer; then iterations++ (809). */
 int s2d_adam_step(s2d_ctx* ctx, uint32_t flags);
