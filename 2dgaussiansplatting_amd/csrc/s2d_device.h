@@ -390,9 +390,9 @@ hipError_t launch_sqerr_finalize(SqerrJob sq, const DeviceStatus* status, int it
 hipError_t launch_init_splats(float* splats, float* adams, int n, int W, int H, hipStream_t stream);
 // proj != nullptr: also project the UPDATED splat for the next iteration and run the containment check on it (what
 // project_kernel mode 1 would do).  check.status also takes the finite guard's verdict.
-// dormant (n bytes, or nullptr): dormant[i] = 1 while every Adam moment of splat i is zero -- maintained by the kernel,
-// cleared by whoever else writes splats or moments; a block whose splats are all dormant and received zero gradients skips
-// the step, which would leave them bit for bit as they are.
+// dormant (n bytes, or nullptr): dormant[i] = 1 while every Adam moment of splat i is +0 -- maintained by the kernel,
+// cleared by whoever else writes splats or moments; a block whose splats are all dormant and received +0 gradients skips
+// the step, which would leave them bit for bit as they are (not so with a -0.0 among either: those run the step).
 // compact (only with held_ids): splats / adams are the COMPACT arrays of the held splats, record h = splat held_ids[h]:
 // whole lines instead of one gathered record per splat; gradients, projection and `dormant` stay indexed by splat id.
 struct AdamArgs {

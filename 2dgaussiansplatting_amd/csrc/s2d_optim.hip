@@ -164,13 +164,16 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ splats, f
     for (int k = 0; k < 9; k++) gr[k] = mine ? buf[t * 9 + k] : 0.0f;
     // A splat no live pixel sees receives a zero gradient; if its moments are zero as well (dormant[i]: they were after its
     // last full update, and nothing but this kernel has touched it since) the whole of main.cpp:721-750 leaves it exactly as
-    // it is: m = v = 0, the step 0 / (0 + 1e-15), the clamps already applied.  Splats are blended in index order, so the
+    // it is: m = v = 0, the step 0 / (0 + 1e-15), the clamps already applied.  Zero means +0, bit for bit, on both sides:
+    // a first moment of -0.0 becomes +0 under a +0 gradient (0.9 * -0 + 0.1 * +0) and takes the sign of a -0.0 parameter
+    // with it (-0 - -0 = +0), and a -0.0 gradient left in the buffer is not the +0 the reference starts its sums from
+    // (main.cpp:550), so neither may be skipped over.  Splats are blended in index order, so the
     // hidden ones sit together at the high indices (about 60 % of 10^6 on a 4096^2 image): a block made of them has nothing
     // to read, write, project or check beyond the gradients it has just looked at.
     bool live = false;
     if (mine) {
 #pragma unroll
-        for (int k = 0; k < 9; k++) live = live || (gr[k] != 0.0f);
+        for (int k = 0; k < 9; k++) live = live || (f32_bits(gr[k]) != 0u);
         if (!live) live = dormant == nullptr || dormant[i] == 0;
     }
     if (!__syncthreads_or(live)) return;
@@ -191,10 +194,10 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ splats, f
     for (int k = 0; k < 18; k++) mv[k] = mine ? buf[t * 18 + k] : 0.0f;
     if (mine) {
         adam_update_one(v, mv, gr, g.W, g.H, beta1t, beta2t, lr, mode, iteration, status);
-        if (dormant) { // all eighteen moments zero (+0 or -0): the next zero gradient changes nothing
+        if (dormant) { // all eighteen moments +0: the next +0 gradient changes nothing
             uint32_t any = 0u;
 #pragma unroll
-            for (int k = 0; k < 18; k++) any |= f32_bits(mv[k]) << 1;
+            for (int k = 0; k < 18; k++) any |= f32_bits(mv[k]);
             dormant[i] = any == 0u ? 1 : 0;
         }
         // moments out (each thread rewrites only its own record of the block's copy; the opacity slot goes back

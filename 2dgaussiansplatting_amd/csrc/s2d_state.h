@@ -23,7 +23,7 @@ public:
         Arrays arrays; // compact: record h is splat held_ids[h]'s; otherwise the id-indexed ones
         bool compact;
         const uint32_t *held_ids, *held_count; // the held splats, ascending, *held_count of them; null: all
-        uint8_t* dormant; // [n]: 1 = all of the splat's moments are zero (adam_kernel keeps it; written() clears it)
+        uint8_t* dormant; // [n]: 1 = all of the splat's moments are +0, bit for bit (adam_kernel keeps it; written() clears it)
     };
 
     hipError_t create(int n, hipStream_t stream); // zeroed (queued); S2D_COMPACT_HELD=0 turns the compact copy off (A/B)

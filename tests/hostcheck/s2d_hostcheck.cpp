@@ -63,6 +63,14 @@ float hc_adam(float* m, float* v, float value, float g, float lr, float b1t, flo
     return adam_optimize(*m, *v, value, g, lr, b1t, b2t);
 }
 
+// The same over `count` scalars in place (values[i], mv[2i] = m, mv[2i+1] = v), in either form of the quotient
+// (fp32_quotient: S2D_CFG_ADAM_FP32).
+void hc_adam_n(float* values, float* mv, const float* g, int count, float lr, float b1t, float b2t, int fp32_quotient)
+{
+    for (int i = 0; i < count; i++)
+        values[i] = adam_optimize(mv[2 * i], mv[2 * i + 1], values[i], g[i], lr, b1t, b2t, fp32_quotient != 0);
+}
+
 // Bounding rectangle test: does the conservative x extent used for binning (pos_x +- (hx + 1)) contain
 // every column the exact per-row ranges visit?  Returns the number of violations over all rows.
 int hc_check_bounds(const float* splats9, int n, int W, int H)

@@ -6,30 +6,18 @@ restatement errors in the shared math before any GPU time is spent.
 """
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostcheck_lib
 import oracle_lib as O
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-HC_DIR = os.path.join(HERE, "hostcheck")
 
 
 @pytest.fixture(scope="module")
 def hc():
-    so = os.path.join(HC_DIR, "libs2d_hostcheck.so")
-    srcs = [os.path.join(HC_DIR, "s2d_hostcheck.cpp"),
-            os.path.join(O.ROOT, "2dgaussiansplatting_amd", "csrc", "s2d_math.h"),
-            os.path.join(O.ROOT, "2dgaussiansplatting_amd", "host", "overlay.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(so) < os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-I", os.path.join(O.ROOT, "include"),
-                               "-o", so, srcs[0], "-lm", "-lz"])
-    L = C.CDLL(so)
-    L.hc_adam.restype = C.c_float
-    L.hc_adam.argtypes = [C.c_void_p, C.c_void_p] + [C.c_float] * 5
-    return L
+    return hostcheck_lib.load()
 
 
 def p(a):
