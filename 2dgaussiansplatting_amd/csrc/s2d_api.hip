@@ -242,6 +242,7 @@ AdamArgs adam_args(s2d_ctx* c, uint32_t flags, bool project)
     a.beta1t = c->beta1t; a.beta2t = c->beta2t; a.lr = c->lr; a.iteration = c->iterations;
     a.mode = ((flags & S2D_STEP_OPTIMIZE_OPACITY) ? 1 : 0) | ((c->cfg.flags & S2D_CFG_ADAM_FP32) ? 2 : 0);
     a.proj = project ? (ProjRec*)c->d_proj : nullptr;
+    a.proj_current = c->proj_fresh; // (every event that replaces parameters clears it: invalidate())
     a.check = ContainmentCheck{c->d_rects, c->d_status, c->check_seq, c->h_rebin_stamp};
     a.sq = c->trace.take_for_adam();
     return a;
@@ -376,7 +377,9 @@ int launch_job(s2d_ctx* c, bool optimistic, const RasterJob& job)
 //   moments replaced (s2d_set_adam, s2d_rows_scatter): nothing, what is drawn depends on the parameters only; state.written().
 //   held set changed (s2d_halo_commit): Lists if splats arrived, on the first commit and on the return to holding
 //     everything (the lists hold the held splats only); departures alone leave lists that still cover every held splat.
-//   Adam step queued (queue_adam): Projection, which the step itself renews when it projects (lists in re-use).
+//   Adam step queued (queue_adam): Projection, which the step itself renews when it projects (lists in re-use).  The
+//     launch is told proj_fresh as it stands BEFORE the step: only then may it leave the record and the check of a splat
+//     it does not move as they are (adam_kernel); after any of the events above it projects and checks every splat.
 //   non-finite step judged (judge_status): Frames; the counters are wound back to the failing step.
 //   index-range pass finished (queue_raster): the last range's lists are no lists of the scene, lists_valid stays false.
 // Two rules are not in this table because no call site keeps them any more (s2d_state.h): the id-indexed parameter and

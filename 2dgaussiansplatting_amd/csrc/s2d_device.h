@@ -391,8 +391,10 @@ hipError_t launch_init_splats(float* splats, float* adams, int n, int W, int H, 
 // proj != nullptr: also project the UPDATED splat for the next iteration and run the containment check on it (what
 // project_kernel mode 1 would do).  check.status also takes the finite guard's verdict.
 // dormant (n bytes, or nullptr): dormant[i] = 1 while every Adam moment of splat i is +0 -- maintained by the kernel,
-// cleared by whoever else writes splats or moments; a block whose splats are all dormant and received +0 gradients skips
-// the step, which would leave them bit for bit as they are (not so with a -0.0 among either: those run the step).
+// cleared by whoever else writes splats or moments; a dormant splat that received a +0 gradient is skipped: the step would
+// leave it bit for bit as it is (not so with a -0.0 among either: those run the step).
+// proj_current (with proj): proj[] and the containment check already describe the parameters the launch starts from, so
+// a skipped splat's record and check stand; otherwise no splat is skipped.
 // compact (only with held_ids): splats / adams are the COMPACT arrays of the held splats, record h = splat held_ids[h]:
 // whole lines instead of one gathered record per splat; gradients, projection and `dormant` stay indexed by splat id.
 struct AdamArgs {
@@ -407,6 +409,7 @@ struct AdamArgs {
     int mode = 0;                          // bit 0: optimise the opacity; bit 1: fp32 quotient (S2D_CFG_ADAM_FP32)
     int iteration = 0;
     ProjRec* proj = nullptr;
+    bool proj_current = false;
     ContainmentCheck check{};
     uint8_t* dormant = nullptr;
     SqerrJob sq{};                         // the launch's first workgroups also add up the tile errors

@@ -99,31 +99,118 @@ __device__ __forceinline__ bool adam_prologue(const DeviceStatus* status, int it
 //     element e of the block's copy is dword e % w of record ids[e / w], so consecutive lanes still read consecutive
 //     dwords of a record (and usually of neighbouring records).
 // Also re-zeroes the gradient records (main.cpp:550 value-initialises dSplats every iteration).
+//
+// Parameters and moments move only where a LIVE record needs them (s_live: bit r of the block's 256 = record r runs the
+// step): a 16-byte line is loaded and stored when one of the (at most two) records it holds words of is live, and the
+// words of an inert neighbour on such a line go back as they came.  s_live == nullptr: every record of the block is live
+// (small scenes, where nothing is hidden: the arrays move as whole lines without a look at the masks).
+__device__ __forceinline__ bool record_live(const uint64_t* s_live, int r)
+{
+    return s_live == nullptr || ((s_live[r >> 6] >> (r & 63)) & 1ull) != 0ull;
+}
+
 template <int WIDTH>
-__device__ __forceinline__ void lds_fill(float* lds, const float* __restrict__ src, const uint32_t* s_ids, int base, int cnt)
+__device__ __forceinline__ bool line_live(const uint64_t* s_live, int q) // WIDTH >= 4: words 4q .. 4q + 3 lie in two records at most
+{
+    return s_live == nullptr || record_live(s_live, (4 * q) / WIDTH) || record_live(s_live, (4 * q + 3) / WIDTH);
+}
+
+template <int WIDTH>
+__device__ __forceinline__ void lds_fill(float* lds, const float* __restrict__ src, const uint32_t* s_ids, const uint64_t* s_live,
+                                         int base, int cnt)
 {
     const int floats = cnt * WIDTH;
     if (s_ids == nullptr) { // contiguous and 16-byte aligned: a block starts at a multiple of 256 records
         const float* p = src + (size_t)base * WIDTH;
         const int vec = floats >> 2;
-        for (int q = threadIdx.x; q < vec; q += 256) reinterpret_cast<float4*>(lds)[q] = reinterpret_cast<const float4*>(p)[q];
-        for (int q = (vec << 2) + threadIdx.x; q < floats; q += 256) lds[q] = p[q];
+        // every load of the thread asked for before the first is waited for: one memory round trip, not one per line (a
+        // launch of a few workgroups lasts as long as one block's chain of them)
+        constexpr int kLines = (256 * WIDTH / 4 + 255) / 256;
+        float4 x[kLines];
+        uint32_t take = 0u;
+#pragma unroll
+        for (int j = 0; j < kLines; j++) {
+            const int q = (int)threadIdx.x + 256 * j;
+            take |= (q < vec && line_live<WIDTH>(s_live, q) ? 1u : 0u) << j;
+        }
+#pragma unroll
+        for (int j = 0; j < kLines; j++) {
+            x[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if ((take >> j) & 1u) x[j] = reinterpret_cast<const float4*>(p)[(int)threadIdx.x + 256 * j];
+        }
+#pragma unroll
+        for (int j = 0; j < kLines; j++)
+            if ((take >> j) & 1u) reinterpret_cast<float4*>(lds)[(int)threadIdx.x + 256 * j] = x[j];
+        for (int q = (vec << 2) + threadIdx.x; q < floats; q += 256)
+            if (record_live(s_live, q / WIDTH)) lds[q] = p[q];
     } else {
-        for (int q = threadIdx.x; q < floats; q += 256) lds[q] = src[(size_t)s_ids[q / WIDTH] * WIDTH + q % WIDTH];
+        for (int q = threadIdx.x; q < floats; q += 256)
+            if (record_live(s_live, q / WIDTH)) lds[q] = src[(size_t)s_ids[q / WIDTH] * WIDTH + q % WIDTH];
     }
 }
 
 template <int WIDTH>
-__device__ __forceinline__ void lds_drain(float* __restrict__ dst, const float* lds, const uint32_t* s_ids, int base, int cnt)
+__device__ __forceinline__ void lds_drain(float* __restrict__ dst, const float* lds, const uint32_t* s_ids, const uint64_t* s_live,
+                                          int base, int cnt)
 {
     const int floats = cnt * WIDTH;
     if (s_ids == nullptr) {
         float* p = dst + (size_t)base * WIDTH;
         const int vec = floats >> 2;
-        for (int q = threadIdx.x; q < vec; q += 256) reinterpret_cast<float4*>(p)[q] = reinterpret_cast<const float4*>(lds)[q];
-        for (int q = (vec << 2) + threadIdx.x; q < floats; q += 256) p[q] = lds[q];
+        for (int q = threadIdx.x; q < vec; q += 256)
+            if (line_live<WIDTH>(s_live, q)) reinterpret_cast<float4*>(p)[q] = reinterpret_cast<const float4*>(lds)[q];
+        for (int q = (vec << 2) + threadIdx.x; q < floats; q += 256)
+            if (record_live(s_live, q / WIDTH)) p[q] = lds[q];
     } else {
-        for (int q = threadIdx.x; q < floats; q += 256) dst[(size_t)s_ids[q / WIDTH] * WIDTH + q % WIDTH] = lds[q];
+        for (int q = threadIdx.x; q < floats; q += 256)
+            if (record_live(s_live, q / WIDTH)) dst[(size_t)s_ids[q / WIDTH] * WIDTH + q % WIDTH] = lds[q];
+    }
+}
+
+// The block's gradient records into LDS, all of them: whether a record is live is read off them.  Returns which of the
+// thread's loads (bit j: its j-th) brought a word that is not +0 -- the only ones grads_rezero has to store over.
+__device__ __forceinline__ uint32_t grads_fill(float* lds, const float* __restrict__ grads, const uint32_t* s_ids, int base, int cnt)
+{
+    const int floats = cnt * 9;
+    uint32_t nz = 0u;
+    int j = 0;
+    if (s_ids == nullptr) {
+        const float* p = grads + (size_t)base * 9;
+        const int vec = floats >> 2;
+        for (int q = threadIdx.x; q < vec; q += 256, j++) {
+            const float4 x = reinterpret_cast<const float4*>(p)[q];
+            reinterpret_cast<float4*>(lds)[q] = x;
+            nz |= ((f32_bits(x.x) | f32_bits(x.y) | f32_bits(x.z) | f32_bits(x.w)) != 0u ? 1u : 0u) << j;
+        }
+        for (int q = (vec << 2) + threadIdx.x; q < floats; q += 256, j++) {
+            const float x = p[q];
+            lds[q] = x;
+            nz |= (f32_bits(x) != 0u ? 1u : 0u) << j;
+        }
+    } else {
+        for (int q = threadIdx.x; q < floats; q += 256, j++) {
+            const float x = grads[(size_t)s_ids[q / 9] * 9 + q % 9];
+            lds[q] = x;
+            nz |= (f32_bits(x) != 0u ? 1u : 0u) << j;
+        }
+    }
+    return nz;
+}
+
+__device__ __forceinline__ void grads_rezero(float* __restrict__ grads, const uint32_t* s_ids, int base, int cnt, uint32_t nz)
+{
+    const int floats = cnt * 9;
+    int j = 0;
+    if (s_ids == nullptr) {
+        float* p = grads + (size_t)base * 9;
+        const int vec = floats >> 2;
+        for (int q = threadIdx.x; q < vec; q += 256, j++)
+            if ((nz >> j) & 1u) reinterpret_cast<float4*>(p)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int q = (vec << 2) + threadIdx.x; q < floats; q += 256, j++)
+            if ((nz >> j) & 1u) p[q] = 0.0f;
+    } else {
+        for (int q = threadIdx.x; q < floats; q += 256, j++)
+            if ((nz >> j) & 1u) grads[(size_t)s_ids[q / 9] * 9 + q % 9] = 0.0f;
     }
 }
 
@@ -134,11 +221,14 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ splats, f
                                                    DeviceStatus* __restrict__ status, ProjRec* __restrict__ proj,
                                                    const TileRect* __restrict__ rects, int check_stamp,
                                                    int* __restrict__ host_stamp, uint8_t* __restrict__ dormant, SqerrJob sq,
-                                                   int compact)
+                                                   int compact, int proj_current)
 {
     __shared__ __attribute__((aligned(16))) float buf[256 * 18];
     __shared__ uint32_t s_idbuf[256];
+    __shared__ uint64_t s_live_words[4];
     if (!adam_prologue(status, iteration, sq)) return;
+    // (asked for here, beside the word the prologue has just read, and not where it is used: behind the gradients)
+    const int last_failed_check = __hip_atomic_load(&status->rebin_needed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int total = held_ids ? (int)min(*held_count, (uint32_t)n) : n;
     const int base = blockIdx.x * 256, cnt = min(256, total - base), t = threadIdx.x;
     if (cnt <= 0) return;
@@ -157,8 +247,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ splats, f
     // own: whole lines, like the all-splats case); the gradient records stay where the raster kernels' atomics put them
     const uint32_t* const s_ids_state = compact ? nullptr : s_ids;
     float v[9], mv[18], gr[9];
-    // gradients in, zeros out
-    lds_fill<9>(buf, grads, s_ids, base, cnt);
+    const bool asleep = mine && dormant != nullptr && dormant[i] != 0; // (in flight together with the gradients)
+    // gradients in
+    const uint32_t grads_nonzero = grads_fill(buf, grads, s_ids, base, cnt);
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < 9; k++) gr[k] = mine ? buf[t * 9 + k] : 0.0f;
@@ -167,32 +258,44 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ splats, f
     // it is: m = v = 0, the step 0 / (0 + 1e-15), the clamps already applied.  Zero means +0, bit for bit, on both sides:
     // a first moment of -0.0 becomes +0 under a +0 gradient (0.9 * -0 + 0.1 * +0) and takes the sign of a -0.0 parameter
     // with it (-0 - -0 = +0), and a -0.0 gradient left in the buffer is not the +0 the reference starts its sums from
-    // (main.cpp:550), so neither may be skipped over.  Splats are blended in index order, so the
-    // hidden ones sit together at the high indices (about 60 % of 10^6 on a 4096^2 image): a block made of them has nothing
-    // to read, write, project or check beyond the gradients it has just looked at.
+    // (main.cpp:550), so neither may be skipped over.  Such a splat is INERT in this launch: nothing of it is read beyond
+    // the gradients just looked at and its dormant byte, nothing is written, and its projection record and containment
+    // check stand as they are -- PROVIDED the record was made from these very parameters and the check was passed, which is
+    // the context's proj_fresh (s2d_api.hip, invalidate()) handed over as proj_current, with one addition the host cannot
+    // see without waiting: the check before this one must not be a failed one that no list rebuild has answered yet
+    // (rebuilds and checks share one sequence, so that is the stamp before ours), or a splat that failed it and went inert
+    // would not fail this one.  Where the record is not known current every splat runs the step, which changes nothing
+    // about an inert one but projects and checks it.  Splats are blended in index order, so the hidden ones are the later
+    // ones -- 58 % of 10^6 on a 4096^2 image, nine in ten of them above index 440 000 -- but in runs between live ones: one
+    // block in nine is made of them alone (profiles/r11).  Such a block returns here; any other moves the lines of its live
+    // records only.
+    const bool may_skip = proj == nullptr || (proj_current != 0 && last_failed_check != check_stamp - 1);
     bool live = false;
     if (mine) {
 #pragma unroll
         for (int k = 0; k < 9; k++) live = live || (f32_bits(gr[k]) != 0u);
-        if (!live) live = dormant == nullptr || dormant[i] == 0;
+        if (!live) live = !may_skip || !asleep;
     }
+    const uint64_t wave_live = __ballot(live);
+    if ((t & 63) == 0) s_live_words[t >> 6] = wave_live;
     if (!__syncthreads_or(live)) return;
-    for (int q = t; q < 256 * 9 / 4; q += 256) reinterpret_cast<float4*>(buf)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-    __syncthreads();
-    lds_drain<9>(grads, buf, s_ids, base, cnt);
-    __syncthreads();
-    // parameters in
-    lds_fill<9>(buf, splats, s_ids_state, base, cnt);
+    const int inert_records = cnt - (__popcll(s_live_words[0]) + __popcll(s_live_words[1]) + __popcll(s_live_words[2]) + __popcll(s_live_words[3]));
+    const uint64_t* const s_live = __builtin_amdgcn_readfirstlane(inert_records) == 0 ? nullptr : s_live_words;
+    // zeros out, over the words that are not +0 already
+    grads_rezero(grads, s_ids, base, cnt, grads_nonzero);
+    // parameters in.  Every thread keeps its record's words, whichever of them were loaded: the copy is overwritten by the
+    // moments below, and an inert record's words on a line it shares with a live one have to go back with that line.
+    lds_fill<9>(buf, splats, s_ids_state, s_live, base, cnt);
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < 9; k++) v[k] = mine ? buf[t * 9 + k] : 0.0f;
     __syncthreads();
     // moments in
-    lds_fill<18>(buf, adams, s_ids_state, base, cnt);
+    lds_fill<18>(buf, adams, s_ids_state, s_live, base, cnt);
     __syncthreads();
+    if (live) {
 #pragma unroll
-    for (int k = 0; k < 18; k++) mv[k] = mine ? buf[t * 18 + k] : 0.0f;
-    if (mine) {
+        for (int k = 0; k < 18; k++) mv[k] = buf[t * 18 + k];
         adam_update_one(v, mv, gr, g.W, g.H, beta1t, beta2t, lr, mode, iteration, status);
         if (dormant) { // all eighteen moments +0: the next +0 gradient changes nothing
             uint32_t any = 0u;
@@ -206,7 +309,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ splats, f
         for (int k = 0; k < 18; k++) buf[t * 18 + k] = mv[k];
     }
     __syncthreads();
-    lds_drain<18>(adams, buf, s_ids_state, base, cnt);
+    lds_drain<18>(adams, buf, s_ids_state, s_live, base, cnt);
     __syncthreads();
     // parameters out
     if (mine) {
@@ -214,8 +317,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ splats, f
         for (int k = 0; k < 9; k++) buf[t * 9 + k] = v[k];
     }
     __syncthreads();
-    lds_drain<9>(splats, buf, s_ids_state, base, cnt);
-    if (proj && mine) project_updated(v, i, g, status, proj, rects, check_stamp, host_stamp);
+    lds_drain<9>(splats, buf, s_ids_state, s_live, base, cnt);
+    if (proj && live) project_updated(v, i, g, status, proj, rects, check_stamp, host_stamp);
 }
 
 // ref(x,y) = (x/W, 1 - x/W, y/H, 1): main.cpp:261-267's commented generator plus a blue ramp.
@@ -283,7 +386,7 @@ hipError_t launch_adam(const AdamArgs& a, hipStream_t stream)
     hipLaunchKernelGGL(adam_kernel, dim3((a.n + 255) / 256), dim3(256), 0, stream, a.splats, a.adams, a.grads, a.held_ids,
                        a.held_count, a.n, a.g, a.beta1t, a.beta2t, a.lr, a.mode, a.iteration, a.check.status, a.proj,
                        (const TileRect*)a.check.rects, a.check.stamp, a.check.host_stamp, a.dormant, a.sq,
-                       (a.compact && a.held_ids) ? 1 : 0);
+                       (a.compact && a.held_ids) ? 1 : 0, a.proj_current ? 1 : 0);
     return hipGetLastError();
 }
 
