@@ -58,6 +58,14 @@ class _RelocateConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("max_moves", C.c_int32), ("min_weight", C.c_float), ("shrink", C.c_float)]
 
 
+class _LossConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("w_mse", C.c_float), ("w_l1", C.c_float), ("w_dssim", C.c_float)]
+
+
+class _LossTerms(C.Structure):
+    _fields_ = [("mse", C.c_double), ("l1", C.c_double), ("dssim", C.c_double), ("total", C.c_double)]
+
+
 ROWS_GRADS, ROWS_SPLATS, ROWS_ADAM = 0, 1, 2  # S2D_ROWS_* (row arrays of the slab-ownership calls)
 
 
@@ -80,6 +88,7 @@ ABI_SYMBOLS = [
     "s2d_get_image", "s2d_get_image_rows", "s2d_backward", "s2d_backward_image_grads", "s2d_set_splats_device", "s2d_get_image_rows_device", "s2d_forward_backward", "s2d_get_grads", "s2d_adam_step", "s2d_step", "s2d_get_mse",
     "s2d_bind_grads_device", "s2d_grads_device_ptr", "s2d_stream", "s2d_get_sqerr_trace", "s2d_synchronize", "s2d_get_stats",
     "s2d_get_rebuild_count", "s2d_density_get", "s2d_density_get_device", "s2d_density_reset", "s2d_relocate",
+    "s2d_loss_image_grads_device", "s2d_loss_backward", "s2d_loss_get", "s2d_step_loss",
     "s2d_last_error", "s2d_test_sincos", "s2d_test_sort_pairs", "s2d_test_exclusive_scan",
     "s2d_test_sort_tile_offsets", "s2d_debug_get_tile_lists",
     "s2d_halo_masks", "s2d_halo_commit", "s2d_rows_gather", "s2d_rows_scatter", "s2d_grads_combine",
@@ -241,6 +250,10 @@ def load_library(path=None):
     sig("s2d_density_get_device", [vp, vp, vp])
     sig("s2d_density_reset", [vp])
     sig("s2d_relocate", [vp, C.POINTER(_RelocateConfig), vp])
+    sig("s2d_loss_image_grads_device", [vp, C.POINTER(_LossConfig), vp])
+    sig("s2d_loss_backward", [vp, C.POINTER(_LossConfig), u32])
+    sig("s2d_loss_get", [vp, C.POINTER(_LossTerms)])
+    sig("s2d_step_loss", [vp, i32, u32, C.POINTER(_LossConfig), vp, vp])
     sig("s2d_step", [vp, i32, u32, vp])
     sig("s2d_get_mse", [vp, vp])
     sig("s2d_bind_grads_device", [vp, vp])
@@ -467,6 +480,44 @@ class Trainer:
         flags = self._flags() | (S2D_STEP_DENSITY_STATS if density_stats else 0)
         self._ck(self.L.s2d_step(self._h, int(iters), flags, _p(out) if want_mse else None))
         return out
+
+    # -- image losses formed by the library (include/splat2d.h, "image losses"): L = sum of w_mse * d^2 / 2 + w_l1 * |d| +
+    # w_dssim * (1 - SSIM) over pixels and channels; a term with weight 0 is not evaluated
+    @staticmethod
+    def _loss_config(w_mse, w_l1, w_dssim):
+        return _LossConfig(C.sizeof(_LossConfig), float(w_mse), float(w_l1), float(w_dssim))
+
+    def loss_image_grads_device(self, ptr, w_mse, w_l1, w_dssim):
+        """dL/d(image0) of the current frame alone into device memory (H x W RGBA32F, .w = 0, 16-byte aligned), queued on
+        the context's stream; loss_terms() then returns this pass's terms."""
+        cfg = self._loss_config(w_mse, w_l1, w_dssim)
+        self._ck(self.L.s2d_loss_image_grads_device(self._h, C.byref(cfg), C.c_void_p(ptr) if ptr else None))
+
+    def loss_backward(self, w_mse, w_l1, w_dssim, skip_opacity_grad=None, density_stats=False):
+        """backward() for the loss L (s2d_loss_backward); skip_opacity_grad and density_stats as backward()."""
+        if skip_opacity_grad is None:
+            skip_opacity_grad = self.lean_backward and not self.optimize_opacity
+        cfg = self._loss_config(w_mse, w_l1, w_dssim)
+        self._ck(self.L.s2d_loss_backward(self._h, C.byref(cfg), (S2D_BWD_SKIP_OPACITY_GRAD if skip_opacity_grad else 0) |
+                                          (S2D_BWD_DENSITY_STATS if density_stats else 0)))
+
+    def loss_terms(self):
+        """-> dict(mse, l1, dssim, total) of the last loss pass: means over 3 * H * W, NaN for a term whose weight was 0
+        (mse is always formed; 255^2 * mse is what mse() returns)."""
+        t = _LossTerms()
+        self._ck(self.L.s2d_loss_get(self._h, C.byref(t)))
+        return {"mse": t.mse, "l1": t.l1, "dssim": t.dssim, "total": t.total}
+
+    def step_loss(self, iters, w_mse, w_l1, w_dssim, want=True, density_stats=False):
+        """iters whole iterations with the loss L (s2d_step_loss); returns (loss, mse): `total` of every iteration and the
+        MSE values of step(), or (None, None) with want=False."""
+        loss = np.zeros(iters, dtype=np.float64) if want else None
+        mse = np.zeros(iters, dtype=np.float64) if want else None
+        cfg = self._loss_config(w_mse, w_l1, w_dssim)
+        flags = self._flags() | (S2D_STEP_DENSITY_STATS if density_stats else 0)
+        self._ck(self.L.s2d_step_loss(self._h, int(iters), flags, C.byref(cfg), _p(loss) if want else None,
+                                      _p(mse) if want else None))
+        return loss, mse
 
     # -- density control (include/splat2d.h, "density control")
     def density(self):

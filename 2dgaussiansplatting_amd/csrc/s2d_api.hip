@@ -25,6 +25,7 @@
 #include "s2d_device.h"
 #include "s2d_density.h" // (behind s2d_device.h: s2d_math.h's qualifiers need the HIP runtime header under hipcc)
 #include "s2d_lists.h"
+#include "s2d_loss.h"
 #include "s2d_owned.h"
 #include "s2d_state.h"
 
@@ -94,6 +95,10 @@ struct s2d_ctx {
     size_t pixel_bytes = sizeof(float4);
     SqerrTrace trace;          // the tile errors of a backward pass and the ring of per-iteration sums (s2d_state.h)
     DensityStats density;      // what the passes with S2D_BWD_DENSITY_STATS accumulated (s2d_state.h)
+    // loss passes (s2d_loss_*, s2d_loss.h): everything here is allocated by the first call that needs it
+    LossTrace loss;                // per-tile sums and the ring of per-iteration totals
+    DevBuf<float> d_loss_maps;     // [9][pixels]: the derivative maps between the two window passes (w_dssim > 0 only)
+    DevBuf<float4> d_loss_grad;    // dL/d(image0) of s2d_loss_backward / s2d_step_loss
     DevBuf<DeviceStatus> d_status;
     DevBuf<PairCounters> d_counters;
     // pinned host mirrors
@@ -609,6 +614,66 @@ double mse_norm(const s2d_ctx* c) { return (double)((long long)c->g.H * c->g.W *
 
 size_t slab_pixels(const s2d_ctx* c) { return (size_t)c->g.W * (size_t)(c->g.row_end - c->g.row_begin); }
 
+// ---- loss passes (s2d_loss.h) --------------------------------------------------------------------------------------
+// Everything s2d_loss_* refuses for the configuration or the context, before any device work.
+int loss_refused(s2d_ctx* c, const s2d_loss_config* cfg)
+{
+    if (!cfg || cfg->struct_size != sizeof(s2d_loss_config)) return fail(c, S2D_E_INVALID, "s2d_loss_config: NULL or wrong struct_size");
+    const float w[3] = {cfg->w_mse, cfg->w_l1, cfg->w_dssim};
+    for (float v : w)
+        if (!(v >= 0.0f) || std::isinf(v)) return fail(c, S2D_E_INVALID, "loss weights must be finite and >= 0");
+    if (w[0] == 0.0f && w[1] == 0.0f && w[2] == 0.0f) return fail(c, S2D_E_INVALID, "all loss weights are zero");
+    if (c->g.row_begin != 0 || c->g.row_end != c->g.H)
+        return fail(c, S2D_E_INVALID, "the loss window crosses slab rows: this context owns a row slab");
+    if (c->state.held()) return fail(c, S2D_E_INVALID, "the loss passes need every splat: this context holds a subset (s2d_halo_commit)");
+    if (c->cfg.flags & S2D_CFG_COUNT_PAIRS)
+        return fail(c, S2D_E_INVALID, "pair counting (S2D_CFG_COUNT_PAIRS) has no backward pass from an image gradient");
+    return S2D_OK;
+}
+
+// The loss kernels of the current frame: dL/d(image0) -> dimage, the totals -> `slot` of the loss ring, the squared error
+// also -> sqerr_out (the iteration's slot of the squared-error ring, or null).
+int queue_loss(s2d_ctx* c, const s2d_loss_config* cfg, float4* dimage, int slot, double* sqerr_out)
+{
+    if (!c->have_forward) return fail(c, S2D_E_STATE, "the loss needs s2d_forward on the current parameters");
+    S2D_HIP(c, c->loss.ensure(c->g.W, c->g.H, c->stream));
+    if (cfg->w_dssim > 0.0f && !c->d_loss_maps) S2D_HIP(c, c->d_loss_maps.alloc((size_t)kLossMapPlanes * slab_pixels(c)));
+    LossArgs a;
+    a.image0 = c->d_image0; a.image_ref = c->d_ref; a.half_images = c->half_images; a.W = c->g.W; a.H = c->g.H;
+    a.w_mse = cfg->w_mse; a.w_l1 = cfg->w_l1; a.w_dssim = cfg->w_dssim;
+    a.maps = c->d_loss_maps; a.dimage = dimage; a.partial = c->loss.partial(); a.out3 = c->loss.slot(slot); a.sqerr_out = sqerr_out;
+    a.status = c->d_status; a.iteration = c->iterations;
+    S2D_HIP(c, launch_loss(a, c->stream));
+    c->loss.record(slot, cfg->w_mse, cfg->w_l1, cfg->w_dssim);
+    return S2D_OK;
+}
+
+// s2d_backward for the loss: the loss kernels into the context's gradient image, the backward walk from it, and the
+// squared error of the iteration in the ring as the loss finalize left it (SqerrBy::LossPass).
+int queue_loss_backward(s2d_ctx* c, const s2d_loss_config* cfg, bool need_opacity_grad, bool density)
+{
+    if (!c->have_forward) return fail(c, S2D_E_STATE, "the backward pass needs s2d_forward on the current parameters");
+    if (!c->d_loss_grad) S2D_HIP(c, c->d_loss_grad.alloc(slab_pixels(c)));
+    if (int rc = queue_loss(c, cfg, c->d_loss_grad, LossTrace::slot_of(c->iterations), c->trace.job(c->iterations).out)) return rc;
+    if (int rc = queue_backward(c, need_opacity_grad, c->d_loss_grad, density)) return rc;
+    return backward_queued(c, SqerrBy::LossPass);
+}
+
+// Sums of a loss pass (squared error on the 255 scale, |d|, 1 - s) -> the means and the total; a term with weight 0 was not formed.
+s2d_loss_terms loss_terms_of(const s2d_ctx* c, const double* sums, const float* w)
+{
+    const double n3 = mse_norm(c);
+    s2d_loss_terms t;
+    t.mse = sums[0] / (255.0 * 255.0) / n3;
+    t.l1 = w[1] > 0.0f ? sums[1] / n3 : std::nan("");
+    t.dssim = w[2] > 0.0f ? sums[2] / n3 : std::nan("");
+    t.total = 0.0;
+    if (w[0] > 0.0f) t.total += (double)w[0] * 0.5 * t.mse;
+    if (w[1] > 0.0f) t.total += (double)w[1] * t.l1;
+    if (w[2] > 0.0f) t.total += (double)w[2] * t.dssim;
+    return t;
+}
+
 } // namespace
 
 extern "C" {
@@ -1021,6 +1086,79 @@ int s2d_relocate(s2d_ctx* c, const s2d_relocate_config* cfg, int32_t* moved)
     S2D_HIP(c, c->density.reset());
     if (moved) *moved = moves;
     return S2D_OK;
+}
+
+int s2d_loss_image_grads_device(s2d_ctx* c, const s2d_loss_config* cfg, float* dimage_rows_device)
+{
+    if (!c || !dimage_rows_device) return S2D_E_INVALID;
+    if (int rc = loss_refused(c, cfg)) return rc;
+    if ((uintptr_t)dimage_rows_device & 15u) return fail(c, S2D_E_INVALID, "the image gradient must be 16-byte aligned");
+    if (int rc = use_device(c)) return rc;
+    return queue_loss(c, cfg, reinterpret_cast<float4*>(dimage_rows_device), LossTrace::kEvalSlot, nullptr);
+}
+
+int s2d_loss_backward(s2d_ctx* c, const s2d_loss_config* cfg, uint32_t flags)
+{
+    if (!c) return S2D_E_INVALID;
+    if (int rc = loss_refused(c, cfg)) return rc;
+    const bool density = (flags & S2D_BWD_DENSITY_STATS) != 0;
+    if (density)
+        if (int rc = density_refused(c)) return rc;
+    if (int rc = use_device(c)) return rc;
+    return queue_loss_backward(c, cfg, !(flags & S2D_BWD_SKIP_OPACITY_GRAD), density);
+}
+
+int s2d_loss_get(s2d_ctx* c, s2d_loss_terms* out)
+{
+    if (!c || !out) return S2D_E_INVALID;
+    if (c->loss.last_slot() < 0) return fail(c, S2D_E_STATE, "no loss pass has run yet");
+    if (int rc = use_device(c)) return rc;
+    double sums[3];
+    S2D_HIP(c, hipMemcpyAsync(sums, c->loss.slot(c->loss.last_slot()), sizeof(sums), hipMemcpyDeviceToHost, c->stream));
+    S2D_HIP(c, hipStreamSynchronize(c->stream));
+    *out = loss_terms_of(c, sums, c->loss.last_weights());
+    return S2D_OK;
+}
+
+int s2d_step_loss(s2d_ctx* c, int32_t iters, uint32_t flags, const s2d_loss_config* cfg, double* loss_out, double* mse_out)
+{
+    if (!c || iters < 0) return S2D_E_INVALID;
+    if (int rc = loss_refused(c, cfg)) return rc;
+    const bool density = (flags & S2D_STEP_DENSITY_STATS) != 0;
+    if (density)
+        if (int rc = density_refused(c)) return rc;
+    if (int rc = use_device(c)) return rc;
+    const double norm = mse_norm(c);
+    const float w[3] = {cfg->w_mse, cfg->w_l1, cfg->w_dssim};
+    const int call_first_iter = c->iterations;
+    std::vector<double> sums;
+    for (int done = 0; done < iters;) {
+        const int chunk = std::min<int>(iters - done, LossTrace::kCapacity); // (both rings have this many slots)
+        const int first_iter = c->iterations;
+        for (int k = 0; k < chunk; k++) {
+            if (int rc = queue_forward(c)) return rc;
+            if (int rc = queue_loss_backward(c, cfg, (flags & S2D_STEP_OPTIMIZE_OPACITY) != 0, density)) return rc;
+            if (int rc = queue_adam(c, flags)) return rc;
+        }
+        if (loss_out) {
+            sums.resize((size_t)3 * chunk);
+            S2D_HIP(c, c->loss.read(first_iter, chunk, sums.data()));
+        }
+        if (mse_out) S2D_HIP(c, c->trace.read(first_iter, chunk, mse_out + done));
+        if (loss_out || mse_out) S2D_HIP(c, hipStreamSynchronize(c->stream));
+        for (int k = 0; loss_out && k < chunk; k++) loss_out[done + k] = loss_terms_of(c, &sums[(size_t)3 * k], w).total;
+        for (int k = 0; mse_out && k < chunk; k++) mse_out[done + k] /= norm; // main.cpp:805
+        done += chunk;
+    }
+    const int rc = check_status(c);
+    if (rc == S2D_E_NONFINITE) { // as s2d_step: the trace ends with the failing iteration's line
+        const int last_valid = c->h_status->first_nonfinite_iter - call_first_iter;
+        for (int k = std::max(last_valid + 1, 0); k < iters; k++) {
+            if (loss_out) loss_out[k] = std::nan("");
+            if (mse_out) mse_out[k] = std::nan("");
+        }
+    }
+    return rc;
 }
 
 int s2d_adam_step(s2d_ctx* c, uint32_t flags)

@@ -65,6 +65,7 @@ enum class SqerrBy {
     PassItself, // the launch wrote the total: the fused raster launch's last tile, or the reference-order chain
     NextAdam,   // the first workgroups of the next Adam launch; whoever reads or renumbers before that gets OwnKernel
     OwnKernel,  // sqerr_finalize, queued at once
+    LossPass,   // a loss pass (s2d_loss.h): its finalize wrote the total of the squared-error term beside its own ring
 };
 
 class S2D_LOCAL SqerrTrace {

@@ -118,7 +118,7 @@ hipError_t SqerrTrace::record(int iteration, SqerrBy by)
 {
     if (by == SqerrBy::NoLoss) return hipSuccess; // (a sum still waiting stays as the last pass with a loss left it)
     last_ = iteration;
-    waiting_ = by != SqerrBy::PassItself;
+    waiting_ = by != SqerrBy::PassItself && by != SqerrBy::LossPass;
     return by == SqerrBy::OwnKernel ? settle() : hipSuccess;
 }
 

@@ -61,6 +61,10 @@ struct Options {
     int relocate_window = 10;        // --relocate-window S: the last S iterations before each relocation gather the statistics
     float relocate_max_fraction = 0.05f; // --relocate-max-fraction f: at most f * splats moved per relocation
     float relocate_min_weight = 0.5f;    // --relocate-min-weight w: a splat whose sum of T * alpha per pass is below w is starved
+    // --loss-weights M,L,D: train with L = sum of M * d^2 / 2 + L * |d| + D * (1 - SSIM) (include/splat2d.h "image losses"; one
+    // context only) instead of the reference's squared error; the trace line gains ", loss %.6f"
+    bool have_loss = false;
+    s2d_loss_config loss{};
     bool replicated = false;    // --exchange dense: replicated state + RCCL all-reduce of all gradients (default: slab ownership)
                                 // (RCCL takes one rank per GPU): a rehearsal of the N-rank host logic on a box with fewer GPUs
 };
@@ -84,6 +88,9 @@ int usage()
                  "                     [--lr RATE] [--deterministic] [--reference-order] [--device D] [--gpus N [--exchange halo|dense] [--share-gpu]\n"
                  "                     [--stall-timeout-ms MS]] [--rebin-interval R] [--quiet]\n"
                  "                     [--relocate-every K [--relocate-window S] [--relocate-max-fraction F] [--relocate-min-weight W]]\n"
+                 "                     [--loss-weights M,L,D]\n"
+                 "  --loss-weights M,L,D: train with the sum over pixels and channels of M * d^2 / 2 + L * |d| + D * (1 - SSIM), e.g.\n"
+                 "    0,0.8,0.2, instead of the reference's squared error (one GPU only); every line ends with the loss's mean.\n"
                  "  --relocate-every K: before iteration K, 2K, ... move the starved splats (summed T * alpha per pass below W) onto\n"
                  "    halves of the splats with the largest summed |dL/dpos|, from statistics of the S iterations before, at most\n"
                  "    F * splats at a time (one GPU only).  Defaults S = 10, F = 0.05, W = 0.5 are provisional: not measured yet.\n");
@@ -214,6 +221,11 @@ int main(int argc, char** argv)
         else if (a == "--deterministic") o.deterministic = true;
         else if (a == "--reference-order") o.reference_order = true;
         else if (a == "--stall-timeout-ms") o.stall_ms = std::atoi(next("--stall-timeout-ms"));
+        else if (a == "--loss-weights") {
+            o.loss.struct_size = sizeof(o.loss);
+            if (std::sscanf(next("--loss-weights"), "%f,%f,%f", &o.loss.w_mse, &o.loss.w_l1, &o.loss.w_dssim) != 3) return usage();
+            o.have_loss = true;
+        }
         else if (a == "--relocate-every") o.relocate_every = std::atoi(next("--relocate-every"));
         else if (a == "--relocate-window") o.relocate_window = std::atoi(next("--relocate-window"));
         else if (a == "--relocate-max-fraction") o.relocate_max_fraction = (float)std::atof(next("--relocate-max-fraction"));
@@ -249,6 +261,10 @@ int main(int argc, char** argv)
 
     if (o.gpus < 1) return usage();
     if (o.relocate_every < 0 || o.relocate_window < 1 || !(o.relocate_max_fraction >= 0.0f) || !(o.relocate_min_weight >= 0.0f)) return usage();
+    if (o.have_loss && (o.gpus > 1 || std::getenv("S2D_TRAIN_FORCE_MULTI"))) {
+        std::fprintf(stderr, "--loss-weights works on one context: the multi-device handle has no loss but the squared error\n");
+        return 2;
+    }
     if (o.relocate_every > 0 && (o.gpus > 1 || std::getenv("S2D_TRAIN_FORCE_MULTI"))) {
         std::fprintf(stderr, "--relocate-every works on one context: the multi-device handle has no relocation\n");
         return 2;
@@ -288,7 +304,7 @@ int main(int argc, char** argv)
         iterations = h.iterations;
         o.iters += iterations; // --iters counts iterations to run from the checkpoint
     }
-    std::vector<double> mse((size_t)o.batch);
+    std::vector<double> mse((size_t)o.batch), loss((size_t)o.batch);
     int frames = 0; // iterations run by this process (the trace numbering restarts at Restart, this does not)
     const auto t0 = std::chrono::steady_clock::now();
     while (iterations < o.iters) { // while (pr::NextFrame() == false), main.cpp:334
@@ -324,9 +340,15 @@ int main(int argc, char** argv)
             else if (iterations + k > window_begin) k = window_begin - iterations;
             if (iterations + k > next_reloc) k = next_reloc - iterations;
         }
-        CK(S.step(k, (opacity_now ? S2D_STEP_OPTIMIZE_OPACITY : 0u) | density, mse.data()));
+        const uint32_t step_flags = (opacity_now ? S2D_STEP_OPTIMIZE_OPACITY : 0u) | density;
+        if (o.have_loss) CK(s2d_step_loss(S.ctx, k, step_flags, &o.loss, loss.data(), mse.data()));
+        else CK(S.step(k, step_flags, mse.data()));
         if (!o.quiet)
-            for (int j = 0; j < k; j++) std::printf("%d itr, mse %.4f\n", iterations + j, mse[(size_t)j]); // main.cpp:807
+            for (int j = 0; j < k; j++) {
+                std::printf("%d itr, mse %.4f", iterations + j, mse[(size_t)j]); // main.cpp:807
+                if (o.have_loss) std::printf(", loss %.6f", loss[(size_t)j]);
+                std::printf("\n");
+            }
         iterations += k; // main.cpp:809
         frames += k;
     }

@@ -272,6 +272,52 @@ typedef struct s2d_relocate_config {
 } s2d_relocate_config;
 int s2d_relocate(s2d_ctx* ctx, const s2d_relocate_config* cfg, int32_t* moved);
 
+/* ---- image losses formed by the library (no counterpart in the reference, whose only loss is the squared error of
+ * main.cpp:616).  With x = image0, y = imageRef, d = x - y, over all pixels p and channels c of .rgb:
+ *
+ *   L = sum_{p,c} [ w_mse * 1/2 * d^2  +  w_l1 * |d|  +  w_dssim * (1 - s) ]
+ *
+ * s is the SSIM index under the 11 x 11 Gaussian window w = g (x) g, g[i] = exp(-(i-5)^2 / (2 * 1.5^2)) normalised to sum 1,
+ * with ZERO PADDING of 5 (pixels outside the image count as 0, the window is not renormalised: conv2d(padding=5)):
+ *   mu_x = w*x, mu_y = w*y, var_x = w*x^2 - mu_x^2, var_y = w*y^2 - mu_y^2, cov = w*xy - mu_x mu_y, C1 = 0.01^2, C2 = 0.03^2,
+ *   s = (2 mu_x mu_y + C1)(2 cov + C2) / ((mu_x^2 + mu_y^2 + C1)(var_x + var_y + C2)).
+ * L is a SUM, on the scale of the reference's gradient: dL/dx = w_mse * d + w_l1 * sign(d) + w_dssim * d(sum(1 - s))/dx with
+ * sign(0) = 0, and weights (1, 0, 0) give image0 - imageRef, main.cpp:616, bit for bit.  The usual mix of means
+ * (1 - lambda) * L1 + lambda * (1 - SSIM) is w_l1 = 1 - lambda, w_dssim = lambda up to the common factor 1 / (3 H W), which Adam's
+ * normalisation removes.  A term whose weight is 0 is neither evaluated nor added; no window kernel runs when w_dssim == 0.
+ * All arithmetic is fp32 on either image format; the sums are doubles added in a fixed order (no atomics: two calls give the
+ * same bytes).
+ * S2D_E_INVALID, before any device work: a NULL config or wrong struct_size; a negative or non-finite weight, or all three
+ * zero; a slab context (row_begin / row_end) or one with a held set (s2d_halo_commit) -- the window crosses slab rows;
+ * S2D_CFG_COUNT_PAIRS; S2D_BWD_DENSITY_STATS / S2D_STEP_DENSITY_STATS where s2d_backward refuses them.  S2D_E_STATE without
+ * s2d_forward on the current parameters.  The multi-device handle (s2d_multi) has no loss but the squared error: out of
+ * scope here. */
+typedef struct s2d_loss_config {
+    uint32_t struct_size; /* = sizeof(s2d_loss_config) */
+    float w_mse, w_l1, w_dssim; /* each >= 0 and finite, not all 0 */
+} s2d_loss_config;
+/* MEANS over 3 * H * W of d^2, |d| and 1 - s, and total = w_mse * 1/2 * mse + w_l1 * l1 + w_dssim * dssim = L / (3 H W).  mse is on
+ * the scale of the images ([0,1] channels): 255^2 * mse is what s2d_get_mse returns.  A term with weight 0 was not formed and
+ * is NaN -- except mse, which every loss pass forms. */
+typedef struct s2d_loss_terms {
+    double mse, l1, dssim, total;
+} s2d_loss_terms;
+/* dL/d(image0) alone, into the caller's DEVICE buffer (height * width RGBA32F, .w = 0, 16-byte aligned), queued on the
+ * context's stream; its terms are what s2d_loss_get returns next.  Touches neither the gradients nor the squared-error ring. */
+int s2d_loss_image_grads_device(s2d_ctx* ctx, const s2d_loss_config* cfg, float* dimage_rows_device);
+/* s2d_backward for the loss L: dL/d(image0) into an image the context owns (allocated by the first call, like the 9 floats
+ * per pixel of scratch the window passes need), then the backward walk of s2d_backward_image_grads from it.  The squared
+ * error of the iteration goes into the ring as after s2d_backward: s2d_get_mse and s2d_get_sqerr_trace keep working.
+ * flags: S2D_BWD_SKIP_OPACITY_GRAD, S2D_BWD_DENSITY_STATS. */
+int s2d_loss_backward(s2d_ctx* ctx, const s2d_loss_config* cfg, uint32_t flags);
+/* The terms of the last loss pass (s2d_loss_backward, s2d_step_loss's last iteration or s2d_loss_image_grads_device);
+ * S2D_E_STATE before any. */
+int s2d_loss_get(s2d_ctx* ctx, s2d_loss_terms* out);
+/* s2d_step with the loss L: per iteration s2d_forward, s2d_loss_backward, s2d_adam_step (image0 is stored every iteration).
+ * loss_out (may be NULL): `total` of every iteration; mse_out (may be NULL): as for s2d_step.  flags:
+ * S2D_STEP_OPTIMIZE_OPACITY, S2D_STEP_DENSITY_STATS.  S2D_E_NONFINITE and the NaN tail of both outputs as for s2d_step. */
+int s2d_step_loss(s2d_ctx* ctx, int32_t iters, uint32_t flags, const s2d_loss_config* cfg, double* loss_out, double* mse_out);
+
 /* Adam + constraints + finite guard, main.cpp:714-785, on the current gradient buffer; then iterations++ (809). */
 int s2d_adam_step(s2d_ctx* ctx, uint32_t flags);
 

@@ -1,6 +1,7 @@
 """Register / LDS / occupancy report of the raster kernels from the gfx950 cross-compile, and its comparison between two trees.
 
-    python tools/kernel_resources.py report [csrc_dir] > new.json     (no GPU needed: hipcc -Rpass-analysis=kernel-resource-usage)
+    python tools/kernel_resources.py report [csrc_dir] [unit.hip] > new.json     (no GPU needed: hipcc -Rpass-analysis=kernel-resource-usage;
+                                                                  unit: default s2d_raster.hip, e.g. s2d_loss.hip)
     python tools/kernel_resources.py compare old.json new.json
     python tools/kernel_resources.py asm old_csrc_dir [new_csrc_dir] [unit.hip ...]
 
@@ -115,8 +116,10 @@ def compare(old, new):
 
 if __name__ == "__main__":
     if len(sys.argv) >= 2 and sys.argv[1] == "report":
-        csrc = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "2dgaussiansplatting_amd", "csrc")
-        json.dump(report(csrc), sys.stdout, indent=1, sort_keys=True)
+        units = [a for a in sys.argv[2:] if a.endswith(".hip")] or ["s2d_raster.hip"]
+        dirs = [a for a in sys.argv[2:] if not a.endswith(".hip")]
+        csrc = dirs[0] if dirs else os.path.join(ROOT, "2dgaussiansplatting_amd", "csrc")
+        json.dump(report(csrc, units[0]), sys.stdout, indent=1, sort_keys=True)
     elif len(sys.argv) == 4 and sys.argv[1] == "compare":
         sys.exit(0 if compare(json.load(open(sys.argv[2])), json.load(open(sys.argv[3]))) else 1)
     elif len(sys.argv) >= 3 and sys.argv[1] == "asm":
