@@ -19,10 +19,10 @@
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
-#include <cstdlib>
 #include <new>
 
 #include "s2d_device.h"
+#include "s2d_context.h"
 #include "s2d_density.h" // (behind s2d_device.h: s2d_math.h's qualifiers need the HIP runtime header under hipcc)
 #include "s2d_lists.h"
 #include "s2d_loss.h"
@@ -50,42 +50,11 @@ struct s2d_ctx {
     DevBuf<uint32_t> d_offsets;
     DevBuf<uint32_t> d_scan_temp;               // lent to the list builds and to s2d_halo_commit
     TileLists lists;                            // the per-tile lists and everything only their builds use
-    // the raster's per-pair hand-over, sized by lists.capacity() (ensure_pair_capacity)
-    DevBuf<unsigned long long> d_wave_masks;    // 4 x u64 per listed pair (capacity; written per executed pair): forward -> backward lane masks
-    DevBuf<uint32_t> d_exec_list;               // per listed pair (capacity): splat indices of a tile's executed entries, compacted
-    DevBuf<uint32_t> d_tile_exec;               // [tiles]: how many entries the tile's last forward walk handed over
-    DevBuf<uint32_t> d_retire_hint;             // [tiles]: list position at which the tile retired in the last launch (0xFFFFFFFF: unknown);
-                                                // a hint for batch sizes only, so it survives list rebuilds and new splats (measured better than a reset)
-    bool deterministic = false;                 // S2D_CFG_DETERMINISTIC
-    DevBuf<float> d_det_data;                   // [pair capacity][9] per-(tile, splat) partial gradients
-    DevBuf<uint32_t> d_det_stamp;               // [pair capacity]
-    DevBuf<uint32_t> d_det_touched;             // [n]: which of a splat's slots the current pass wrote (zero between passes)
-    uint32_t det_epoch = 0;                     // stamps written so far (monotone; 0 = never)
-    // S2D_CFG_REFERENCE_ORDER: every backward pass stores its per-pixel terms and adds them in the reference's order
-    // (s2d_raster.hip, reference_*_kernel).  Slots and stamps are deterministic mode's (d_det_stamp, det_epoch), which this
-    // mode replaces: `deterministic` is false in such a context.
-    bool ref_order = false;
-    uint64_t ref_max_bytes = 32ull << 30;       // S2D_REFERENCE_ORDER_MAX_BYTES overrides: bound on d_ref_terms
-    DevBuf<float> d_ref_terms;                  // [pair capacity][kRefTermsStride]
-    DevBuf<float> d_pixel_sqerr;                // [pixels of the slab]
-    // Index-range ("chunked") rendering: when the (tile, splat) pairs of a scene exceed chunk_pairs -- at the latest 2^32 - 65536,
-    // what 32-bit list positions can address -- the splats are cut into consecutive index ranges of at most that many
-    // pairs, and the lists of one range at a time are built and walked front to back (chunked_forward / chunked_backward)
-    uint64_t chunk_pairs = 1ull << 30;   // S2D_CHUNK_PAIRS overrides (tests force the path on small scenes)
-    std::vector<int> chunks;             // range k = splats [chunks[k], chunks[k+1]); empty: one set of lists
-    int chunks_used = 0;                 // ranges the last forward pass walked before every pixel was saturated
-    int chunk_built = -1;                // the range whose lists are in the buffers now
-    DevBuf<float4> d_state;              // per pixel of the slab: (r, g, b, T) carried from range to range
-    DevBuf<uint32_t> d_chunk_alive;      // != 0: some pixel is still above the throughput cut-off after this range
-    HostBuf<uint32_t> h_chunk_alive;     // ... read back between two ranges
+    PairScratch scratch;                        // the raster's hand-over and slots, sized like the lists (s2d_context.h)
+    IndexRanges ranges;                         // scenes beyond one set of lists: the cut, the carry, the progress of a pass
     bool lists_valid = false;
     bool proj_fresh = false; // d_proj and d_status->rebin_needed describe the CURRENT parameters
-    Event ev_flag;                 // recorded behind the kernel that ran the latest containment check
-    int check_seq = 1;             // its sequence number (both stamp words start at 0: nothing matches before a check): the stamp that kernel writes if a splat left its rectangle
-    HostBuf<int> h_rebin_stamp;    // host-mapped copy of that stamp (written by the kernel, read after ev_flag)
-    int rebin_interval = 1;
-    int since_rebin = 0;
-    float margin = 0.0f;
+    ListReuse reuse;         // when lists are rebuilt on schedule, and the stamped containment check (s2d_context.h)
     // images
     // image0 / imageRef (main.cpp:310, :254): the rows [row_begin, row_end) of this context's slab only -- a context
     // never touches another row, so a 1/8 slab of 8192^2 holds 2 x 134 MB instead of 2 x 1.07 GB
@@ -149,7 +118,7 @@ int use_device(s2d_ctx* c)
     return S2D_OK;
 }
 
-// The single place where pair capacity grows: the pair buffers of the lists and the raster's hand-over have one size.
+// The single place where pair capacity grows: the pair buffers of the lists and the raster's scratch have one size.
 // Every one of them is released, with the stream idle, before the first is allocated again.
 int ensure_pair_capacity(s2d_ctx* c, uint64_t need)
 {
@@ -157,39 +126,26 @@ int ensure_pair_capacity(s2d_ctx* c, uint64_t need)
     if (need >= 0xFFFF0000ull) return fail(c, S2D_E_NOMEM, "tile lists need %llu pairs (> 2^32)", (unsigned long long)need);
     uint64_t cap = std::max<uint64_t>(need + need / 4 + 4096, 1 << 16);
     if (cap > 0xFFFF0000ull) cap = 0xFFFF0000ull;
-    if (c->ref_order) { // refused before anything is released or launched
-        const uint64_t per_slot = (uint64_t)kRefTermsStride * sizeof(float);
-        if (cap * per_slot > c->ref_max_bytes) cap = std::max<uint64_t>(need, 1 << 16); // no headroom rather than no context
-        if (cap * per_slot > c->ref_max_bytes)
-            return fail(c, S2D_E_NOMEM, "the term scratch of S2D_CFG_REFERENCE_ORDER needs %llu bytes for %llu (tile, splat) pairs, "
-                        "S2D_REFERENCE_ORDER_MAX_BYTES allows %llu", (unsigned long long)(cap * per_slot), (unsigned long long)cap,
-                        (unsigned long long)c->ref_max_bytes);
-    }
+    const PairScratch::Grant grant = c->scratch.admit(need, cap); // refused before anything is released or launched
+    if (!grant.slots)
+        return fail(c, S2D_E_NOMEM, "the term scratch of S2D_CFG_REFERENCE_ORDER needs %llu bytes for %llu (tile, splat) pairs, "
+                    "S2D_REFERENCE_ORDER_MAX_BYTES allows %llu", (unsigned long long)grant.bytes, (unsigned long long)grant.refused,
+                    (unsigned long long)c->scratch.max_bytes());
+    cap = grant.slots;
     S2D_HIP(c, hipStreamSynchronize(c->stream));
     c->lists.release_pairs();
-    c->d_wave_masks.release(), c->d_exec_list.release(), c->d_det_data.release(), c->d_det_stamp.release();
-    c->d_ref_terms.release();
+    c->scratch.release();
     S2D_HIP(c, c->lists.alloc_pairs(cap));
-    const auto hand_over = [&]() -> int {
-        S2D_HIP(c, c->d_wave_masks.alloc((size_t)cap * 4));
-        S2D_HIP(c, c->d_exec_list.alloc((size_t)cap));
-        if (c->deterministic) S2D_HIP(c, c->d_det_data.alloc((size_t)cap * kDetStride));
-        if (c->ref_order) S2D_HIP(c, c->d_ref_terms.alloc((size_t)cap * kRefTermsStride));
-        if (c->deterministic || c->ref_order) { // either mode's slots carry stamps
-            S2D_HIP(c, c->d_det_stamp.alloc((size_t)cap));
-            S2D_HIP(c, hipMemsetAsync(c->d_det_stamp, 0, (size_t)cap * sizeof(uint32_t), c->stream));
-        }
-        return S2D_OK;
-    };
-    const int rc = hand_over();
-    if (rc != S2D_OK) c->lists.release_pairs(); // (capacity 0 is what is left if an allocation fails)
-    return rc;
+    const hipError_t scratch_alloc = c->scratch.alloc(cap);
+    if (scratch_alloc != hipSuccess) c->lists.release_pairs(); // (capacity 0 is what is left if an allocation fails)
+    S2D_HIP(c, scratch_alloc);
+    return S2D_OK;
 }
 
 // (Re)build the per-tile lists from the current parameters.  The projection has already been queued with mode 0.
 // first / count: the index range of the splats to list (count < 0: all of them).  A range's lists hold indices RELATIVE to
 // its first splat -- every per-splat array is handed over from that splat on -- and so do the scanned offsets.
-// *need_ranges (all splats only): their pairs exceed chunk_pairs, nothing was built.
+// *need_ranges (all splats only): their pairs exceed the budget of one set of lists, nothing was built.
 int rebuild_lists(s2d_ctx* c, int first = 0, int count = -1, bool* need_ranges = nullptr)
 {
     const int n = count < 0 ? c->n : count;
@@ -197,43 +153,40 @@ int rebuild_lists(s2d_ctx* c, int first = 0, int count = -1, bool* need_ranges =
     c->lists_valid = false; // (count() already writes into the buffers the lists lie in)
     S2D_HIP(c, c->lists.count(ListInput{c->d_rects + first, c->d_counts + first, c->d_offsets + first, first, n, c->d_scan_temp},
                               c->stream, &total));
-    if (need_ranges) *need_ranges = total > c->chunk_pairs;
+    if (need_ranges) *need_ranges = total > c->ranges.budget();
     if (need_ranges && *need_ranges) return S2D_OK;
     if (total >= 0xFFFF0000ull)
         return fail(c, S2D_E_NOMEM, "the tile lists of splats %d..%d need more than 2^32 - 65536 (tile, splat) pairs", first, first + n - 1);
     if (int rc = ensure_pair_capacity(c, total)) return rc;
     S2D_HIP(c, c->lists.finish(c->stream));
     c->lists_valid = count < 0; // a range's lists are walked once and replaced by the next range's
-    c->since_rebin = 0;
     return S2D_OK;
 }
 
-// What a raster pass of the context works on, for the lists of the splats [first, first + count) (count < 0: all of them).
-// A range's lists hold indices relative to its first splat, so every per-splat array is handed over from that splat on.
-RasterArgs raster_args(const s2d_ctx* c, int first = 0, int count = -1)
+// What a raster pass of the context works on: the lists of all splats, or (range >= 0) those of one index range.  A
+// range's lists hold indices relative to its first splat, so every per-splat array is handed over from that splat on.
+RasterArgs raster_args(const s2d_ctx* c, int range = -1)
 {
+    const int first = range < 0 ? 0 : c->ranges.first(range), count = range < 0 ? c->n : c->ranges.size(range);
     RasterArgs a;
-    a.tile_off = c->lists.tile_off(); a.list = c->lists.list(); a.wave_masks = c->d_wave_masks;
-    a.exec_list = c->d_exec_list; a.tile_exec = c->d_tile_exec; a.retire_hint = c->d_retire_hint;
+    a.tile_off = c->lists.tile_off(); a.list = c->lists.list();
     a.proj = c->d_proj + first; a.grads = c->d_grads + (size_t)first * 9;
     a.image0 = c->d_image0; a.image_ref = c->d_ref; a.tile_sqerr = c->trace.tile_sqerr();
     a.g = c->g; a.status = c->d_status; a.iteration = c->iterations; a.counters = c->d_counters;
-    a.state = c->d_state; a.any_alive = c->d_chunk_alive;
-    if (c->deterministic) // (det.now stays 0, no gather, until with_backward_walk)
-        a.det = DetGather{c->d_rects + first, c->d_offsets + first, c->d_counts + first, c->d_det_data, c->d_det_stamp,
-                          c->d_det_touched + first, 0u, count < 0 ? c->n : count};
+    c->scratch.fill(&a, c->d_rects, c->d_offsets, c->d_counts, first, count);
+    c->ranges.fill(&a, range);
     a.half_images = c->half_images; a.count = (c->cfg.flags & S2D_CFG_COUNT_PAIRS) != 0; a.exact_exp = (c->cfg.flags & S2D_CFG_EXACT_EXP) != 0;
     return a;
 }
 
-// What a projection pass works on.  mode 0: rectangles (inflated by the re-use margin), pair and row counts for a list
-// build; mode 1: the containment check against those rectangles, stamped with the check's sequence number.
-ProjectArgs project_args(const s2d_ctx* c, const float* splats, int mode)
+// What a projection pass works on.  check == nullptr (mode 0): rectangles (inflated by the re-use margin), pair and row
+// counts for a list build; otherwise (mode 1): that containment check against those rectangles.
+ProjectArgs project_args(const s2d_ctx* c, const float* splats, const ContainmentCheck* check)
 {
     ProjectArgs a;
-    a.splats = splats; a.held = c->state.held(); a.n = c->n; a.g = c->g; a.mode = mode; a.proj = c->d_proj; a.counts = c->d_counts;
-    a.check = ContainmentCheck{c->d_rects, c->d_status, mode ? c->check_seq : 0, mode ? (int*)c->h_rebin_stamp : nullptr};
-    if (mode == 0) a.margin = c->margin, a.row_counts = c->lists.row_counts();
+    a.splats = splats; a.held = c->state.held(); a.n = c->n; a.g = c->g; a.mode = check ? 1 : 0; a.proj = c->d_proj; a.counts = c->d_counts;
+    a.check = check ? *check : ContainmentCheck{c->d_rects, c->d_status};
+    if (!check) a.margin = c->reuse.margin(), a.row_counts = c->lists.row_counts();
     return a;
 }
 
@@ -248,58 +201,32 @@ AdamArgs adam_args(s2d_ctx* c, uint32_t flags, bool project)
     a.mode = ((flags & S2D_STEP_OPTIMIZE_OPACITY) ? 1 : 0) | ((c->cfg.flags & S2D_CFG_ADAM_FP32) ? 2 : 0);
     a.proj = project ? (ProjRec*)c->d_proj : nullptr;
     a.proj_current = c->proj_fresh; // (every event that replaces parameters clears it: invalidate())
-    a.check = ContainmentCheck{c->d_rects, c->d_status, c->check_seq, c->h_rebin_stamp};
+    a.check = project ? c->reuse.next_check(c->d_rects, c->d_status) : c->reuse.idle_check(c->d_rects, c->d_status);
     a.sq = c->trace.take_for_adam();
     return a;
 }
 
-// The pass has a backward walk.  Deterministic mode: a fresh stamp for its slots (those of earlier passes become invalid).
-void with_backward_walk(s2d_ctx* c, RasterArgs& a, bool need_opacity_grad)
-{
-    a.need_opacity_grad = need_opacity_grad;
-    if (c->deterministic) a.det.now = ++c->det_epoch;
-}
+// The pass has a backward walk (deterministic mode: with a fresh stamp for its slots).
+void with_backward_walk(s2d_ctx* c, RasterArgs& a, bool need_opacity_grad) { a.need_opacity_grad = need_opacity_grad, c->scratch.backward_walk(&a); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Index-range ("chunked") rendering.  The reference's loops have no limit on the number of (pixel, splat) pairs
 // (main.cpp:492-536); 32-bit list positions have one, and long before it the list and mask buffers have a price.  A scene
-// beyond chunk_pairs is rendered range by range: cut where the running pair count would pass the budget, build the
-// lists of one range, walk them, carry the per-pixel (colour, T) to the next range.  Blend order is index order
+// beyond the budget of IndexRanges is rendered range by range: cut where the running pair count would pass the budget,
+// build the lists of one range, walk them, carry the per-pixel (colour, T) to the next range.  Blend order is index order
 // (main.cpp:419), so the cut changes no operation: the framebuffer is bit for bit the unchunked one, and so is every
 // gradient term (the sums differ in the order the atomics arrive, as always).  Lists are rebuilt every pass: this is the
 // path for scenes that do not fit, not a fast one.
 // ---------------------------------------------------------------------------------------------------------------------
-int plan_chunks(s2d_ctx* c)
-{
-    std::vector<uint32_t> cnt((size_t)c->n);
-    S2D_HIP(c, hipMemcpyAsync(cnt.data(), c->d_counts, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    S2D_HIP(c, hipStreamSynchronize(c->stream));
-    c->chunks.assign(1, 0);
-    uint64_t acc = 0;
-    for (int i = 0; i < c->n; i++) {
-        if (acc > 0 && acc + cnt[(size_t)i] > c->chunk_pairs) {
-            c->chunks.push_back(i);
-            acc = 0;
-        }
-        acc += cnt[(size_t)i];
-    }
-    c->chunks.push_back(c->n);
-    if (!c->d_state) S2D_HIP(c, c->d_state.alloc((size_t)c->g.W * (size_t)(c->g.row_end - c->g.row_begin)));
-    if (!c->d_chunk_alive) S2D_HIP(c, c->d_chunk_alive.alloc(1));
-    S2D_HIP(c, c->h_chunk_alive.alloc(1, hipHostMallocDefault));
-    return S2D_OK;
-}
-
 // The lists of range k (built unless the buffers hold them already), and what a raster pass over them works on.
 int build_chunk(s2d_ctx* c, int k, RasterArgs* a)
 {
-    const int first = c->chunks[(size_t)k], count = c->chunks[(size_t)k + 1] - first;
-    if (c->chunk_built != k) {
-        c->chunk_built = -1;
-        if (int rc = rebuild_lists(c, first, count)) return rc;
-        c->chunk_built = k;
+    if (!c->ranges.built(k)) {
+        c->ranges.set_built(-1);
+        if (int rc = rebuild_lists(c, c->ranges.first(k), c->ranges.size(k))) return rc;
+        c->ranges.set_built(k);
     }
-    *a = raster_args(c, first, count); a->first = k == 0;
+    *a = raster_args(c, k);
     return S2D_OK;
 }
 
@@ -307,20 +234,16 @@ int build_chunk(s2d_ctx* c, int k, RasterArgs* a)
 // throughput cut-off any more (main.cpp:520: nothing later could change a pixel).
 int chunked_forward(s2d_ctx* c)
 {
-    const int K = (int)c->chunks.size() - 1;
-    c->chunks_used = 0;
-    c->chunk_built = -1;
+    const int K = c->ranges.count();
+    c->ranges.begin_forward();
     for (int k = 0; k < K; k++) {
         RasterArgs a;
         if (int rc = build_chunk(c, k, &a)) return rc;
-        S2D_HIP(c, hipMemsetAsync(c->d_chunk_alive, 0, sizeof(uint32_t), c->stream));
+        S2D_HIP(c, c->ranges.launching_forward(k));
         S2D_HIP(c, launch_raster(RasterPass::ForwardRange, a, c->stream));
-        c->chunks_used = k + 1;
-        if (k + 1 < K) {
-            S2D_HIP(c, hipMemcpyAsync(c->h_chunk_alive, c->d_chunk_alive, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            S2D_HIP(c, hipStreamSynchronize(c->stream));
-            if (*(volatile uint32_t*)c->h_chunk_alive == 0u) break;
-        }
+        bool alive = true;
+        if (k + 1 < K) S2D_HIP(c, c->ranges.any_alive(&alive));
+        if (!alive) break;
     }
     return S2D_OK;
 }
@@ -329,7 +252,7 @@ int chunked_forward(s2d_ctx* c)
 // upstream: as in queue_backward.
 int chunked_backward(s2d_ctx* c, bool need_opacity_grad, const float4* upstream = nullptr)
 {
-    for (int k = 0; k < c->chunks_used; k++) {
+    for (int k = 0; k < c->ranges.walked(); k++) {
         RasterArgs a;
         if (int rc = build_chunk(c, k, &a)) return rc;
         a.upstream = upstream;
@@ -350,13 +273,13 @@ struct RasterJob {
 int launch_job(s2d_ctx* c, bool optimistic, const RasterJob& job)
 {
     RasterArgs a = raster_args(c);
-    a.abort_stamp = optimistic ? c->check_seq : 0;
+    a.abort_stamp = optimistic ? c->reuse.abort_stamp() : 0;
     if (job.fused) {
         with_backward_walk(c, a, job.need_opacity_grad);
         a.write_image = job.write_image;
         if (c->trace.plan(true, true) == SqerrBy::PassItself) a.sq = c->trace.job(c->iterations);
     }
-    if (c->ref_order && a.exact_exp) // (never fused: queue_forward_backward)
+    if (c->scratch.reference_order() && a.exact_exp) // (never fused: queue_forward_backward)
         S2D_HIP(c, launch_reference_forward_exact(a, c->stream));
     else
         S2D_HIP(c, launch_raster(job.fused ? RasterPass::Fused : RasterPass::Forward, a, c->stream));
@@ -382,15 +305,18 @@ int launch_job(s2d_ctx* c, bool optimistic, const RasterJob& job)
 //   moments replaced (s2d_set_adam, s2d_rows_scatter): nothing, what is drawn depends on the parameters only; state.written().
 //   held set changed (s2d_halo_commit): Lists if splats arrived, on the first commit and on the return to holding
 //     everything (the lists hold the held splats only); departures alone leave lists that still cover every held splat.
-//   Adam step queued (queue_adam): Projection, which the step itself renews when it projects (lists in re-use).  The
-//     launch is told proj_fresh as it stands BEFORE the step: only then may it leave the record and the check of a splat
-//     it does not move as they are (adam_kernel); after any of the events above it projects and checks every splat.
+//   Adam step queued (queue_adam): Projection, which the step itself renews when it projects (ListReuse::adam_checks).
+//     The launch is told proj_fresh as it stands BEFORE the step: only then may it leave the record and the check of a
+//     splat it does not move as they are (adam_kernel); after any of the events above it projects and checks every splat.
 //   non-finite step judged (judge_status): Frames; the counters are wound back to the failing step.
 //   index-range pass finished (queue_raster): the last range's lists are no lists of the scene, lists_valid stays false.
-// Two rules are not in this table because no call site keeps them any more (s2d_state.h): the id-indexed parameter and
+// Rules that are not in this table because no call site keeps them any more.  s2d_state.h: the id-indexed parameter and
 // moment arrays are handed out by SplatState::current() only, which queues the write-back of a compact copy first; and a
 // squared-error sum still waiting for its Adam launch is queued by SqerrTrace's own read() and settle(), the latter
-// being what s2d_set_adam and s2d_init_splats call before they renumber the iterations.
+// being what s2d_set_adam and s2d_init_splats call before they renumber the iterations.  s2d_context.h: a stamp that asked
+// for new lists matches nothing once they are built, and every containment check has a sequence number of its own
+// (ListReuse); the slots of an earlier backward walk are invalid in the next (PairScratch); which range's lists are in
+// the buffers, and how far the last forward pass over ranges got (IndexRanges).
 // ---------------------------------------------------------------------------------------------------------------------
 enum class Stale { Frames, Projection, Lists };
 
@@ -422,48 +348,47 @@ int splats_replaced(s2d_ctx* c)
 // no flag has to be copied or cleared.  If the check failed the lists are rebuilt and the raster kernel is
 // launched again.  (In deterministic mode the gather pass queued behind a voided fused launch adds nothing: the
 // slots carry no stamp of that pass.)
-int queue_project(s2d_ctx* c, int mode)
+int queue_project(s2d_ctx* c, const ContainmentCheck* check = nullptr)
 {
     SplatState::Arrays now;
     S2D_HIP(c, c->state.current(&now));
-    S2D_HIP(c, launch_project(project_args(c, now.splats, mode), c->stream));
+    S2D_HIP(c, launch_project(project_args(c, now.splats, check), c->stream));
     return S2D_OK;
 }
 
 int queue_raster(s2d_ctx* c, const RasterJob& job)
 {
     if (!c->have_target) return fail(c, S2D_E_STATE, "no target image set (s2d_set_target)");
-    const bool scheduled = !c->lists_valid || c->rebin_interval <= 1 || c->since_rebin >= c->rebin_interval;
+    const bool scheduled = c->reuse.rebuild_scheduled(c->lists_valid);
     bool rebuild = scheduled;
     bool stored_image0 = !job.fused || job.write_image; // a fused launch told not to store image0 leaves an older frame there
     if (!scheduled) {
         if (!c->proj_fresh) { // parameters changed without a fused projection: project + check now
-            c->check_seq++;
-            if (int rc = queue_project(c, 1)) return rc;
-            S2D_HIP(c, hipEventRecord(c->ev_flag, c->stream));
+            const ContainmentCheck check = c->reuse.next_check(c->d_rects, c->d_status);
+            if (int rc = queue_project(c, &check)) return rc;
+            S2D_HIP(c, c->reuse.check_queued());
             c->proj_fresh = true;
         }
         if (int rc = launch_job(c, true, job)) return rc;
-        S2D_HIP(c, hipEventSynchronize(c->ev_flag)); // the checking kernel, not the raster kernel
-        rebuild = *(volatile int*)c->h_rebin_stamp == c->check_seq;
+        S2D_HIP(c, c->reuse.asked_for_lists(&rebuild)); // (waits for the checking kernel, not the raster kernel)
     }
     if (rebuild) {
-        int rc = queue_project(c, 0);
+        int rc = queue_project(c);
         if (rc != S2D_OK) return rc;
-        c->chunks.clear();
+        c->ranges.clear();
         bool need_ranges = false;
         if ((rc = rebuild_lists(c, 0, -1, &need_ranges)) != S2D_OK) return rc;
         if (need_ranges && (c->cfg.flags & S2D_CFG_COUNT_PAIRS))
             return fail(c, S2D_E_NOMEM, "pair counting (S2D_CFG_COUNT_PAIRS) is not available for scenes beyond %llu (tile, splat) pairs",
-                        (unsigned long long)c->chunk_pairs);
-        if (need_ranges && c->ref_order)
+                        (unsigned long long)c->ranges.budget());
+        if (need_ranges && c->scratch.reference_order())
             return fail(c, S2D_E_NOMEM, "reference order (S2D_CFG_REFERENCE_ORDER) is not available for scenes beyond %llu (tile, splat) pairs",
-                        (unsigned long long)c->chunk_pairs);
+                        (unsigned long long)c->ranges.budget());
         c->proj_fresh = true;
-        c->check_seq++; // the new lists cover the current parameters: a stamp that asked for them matches nothing now
+        c->reuse.lists_rebuilt();
         if (need_ranges) {
             // more pairs than one set of lists may hold: render by index ranges (every pass rebuilds: lists_valid stays false)
-            if ((rc = plan_chunks(c)) != S2D_OK) return rc;
+            S2D_HIP(c, c->ranges.plan(c->d_counts, c->n));
             if ((rc = chunked_forward(c)) != S2D_OK) return rc;
             if (job.fused && (rc = chunked_backward(c, job.need_opacity_grad)) != S2D_OK) return rc;
             stored_image0 = true; // the forward pass over the ranges always stores it
@@ -497,22 +422,27 @@ int queue_backward_reference(s2d_ctx* c, bool need_opacity_grad, const float4* u
     a.need_opacity_grad = need_opacity_grad;
     SplatState::Arrays now;
     S2D_HIP(c, c->state.current(&now));
-    RefOrder ro;
-    ro.splats = now.splats; ro.rects = c->d_rects; ro.offsets = c->d_offsets; ro.counts = c->d_counts; ro.n = c->n;
-    ro.terms = c->d_ref_terms; ro.stamp = c->d_det_stamp; ro.capacity = (uint32_t)c->lists.capacity(); ro.now = ++c->det_epoch;
-    ro.pixel_sqerr = c->d_pixel_sqerr;
+    const RefOrder ro = c->scratch.reference_walk(now.splats, c->d_rects, c->d_offsets, c->d_counts, c->n);
     S2D_HIP(c, launch_reference_backward(a, ro, c->stream));
     if (upstream) return backward_queued(c, SqerrBy::NoLoss);
-    S2D_HIP(c, launch_reference_sqerr(c->d_pixel_sqerr, (size_t)c->g.W * (size_t)(c->g.row_end - c->g.row_begin),
+    S2D_HIP(c, launch_reference_sqerr(c->scratch.pixel_sqerr(), (size_t)c->g.W * (size_t)(c->g.row_end - c->g.row_begin),
                                       c->trace.job(c->iterations).out, c->d_status, c->iterations, c->stream));
     return backward_queued(c, SqerrBy::PassItself);
 }
 
-// A context whose configuration has no density-statistics walk (the STATS kernels exist without pair counting and the
-// exact exponential; reference order has kernels of its own).
-int density_refused(s2d_ctx* c)
+// What the flags of a backward pass (S2D_BWD_*) or of a step (step: S2D_STEP_*) ask of the backward walk.  The density
+// statistics are refused here for a context whose configuration has no such walk (the STATS kernels exist without pair
+// counting and the exact exponential; reference order has kernels of its own).
+struct WalkFlags {
+    bool need_opacity_grad = true;
+    bool density = false;
+};
+
+int parse_walk_flags(s2d_ctx* c, uint32_t flags, bool step, WalkFlags* out)
 {
-    if ((c->cfg.flags & (S2D_CFG_COUNT_PAIRS | S2D_CFG_EXACT_EXP)) || c->ref_order)
+    out->need_opacity_grad = step ? (flags & S2D_STEP_OPTIMIZE_OPACITY) != 0 : !(flags & S2D_BWD_SKIP_OPACITY_GRAD);
+    out->density = (flags & (step ? S2D_STEP_DENSITY_STATS : S2D_BWD_DENSITY_STATS)) != 0;
+    if (out->density && ((c->cfg.flags & (S2D_CFG_COUNT_PAIRS | S2D_CFG_EXACT_EXP)) || c->scratch.reference_order()))
         return fail(c, S2D_E_INVALID, "density statistics are not available with S2D_CFG_COUNT_PAIRS, S2D_CFG_EXACT_EXP or "
                     "S2D_CFG_REFERENCE_ORDER");
     return S2D_OK;
@@ -521,15 +451,15 @@ int density_refused(s2d_ctx* c)
 // upstream != nullptr (s2d_backward_image_grads): the walk starts from the caller's dL/d(image0) instead of
 // image0 - imageRef.  The loss is the caller's, so no squared error is formed or queued: the trace ring and a sum still
 // waiting for the next Adam launch stay as the last s2d_backward left them (SqerrBy::NoLoss).
-// density (S2D_BWD_DENSITY_STATS; density_refused() has been asked): the walk also accumulates the density statistics.
+// density (S2D_BWD_DENSITY_STATS; parse_walk_flags() has admitted it): the walk also accumulates the density statistics.
 int queue_backward(s2d_ctx* c, bool need_opacity_grad, const float4* upstream = nullptr, bool density = false)
 {
     if (!c->have_forward) return fail(c, S2D_E_STATE, "the backward pass needs s2d_forward on the current parameters");
-    if (c->ref_order) return queue_backward_reference(c, need_opacity_grad, upstream);
-    if (density && !c->chunks.empty())
+    if (c->scratch.reference_order()) return queue_backward_reference(c, need_opacity_grad, upstream);
+    if (density && c->ranges.active())
         return fail(c, S2D_E_NOMEM, "density statistics are not available for scenes beyond %llu (tile, splat) pairs (index-range rendering)",
-                    (unsigned long long)c->chunk_pairs);
-    if (!c->chunks.empty()) { // the forward pass went over index ranges: so does this one
+                    (unsigned long long)c->ranges.budget());
+    if (c->ranges.active()) { // the forward pass went over index ranges: so does this one
         if (int rc = chunked_backward(c, need_opacity_grad, upstream)) return rc;
     } else {
         RasterArgs a = raster_args(c);
@@ -545,7 +475,7 @@ int queue_backward(s2d_ctx* c, bool need_opacity_grad, const float4* upstream = 
 // property of the separate kernels only, so a counting context takes those.
 int queue_forward_backward(s2d_ctx* c, bool need_opacity_grad, bool write_image)
 {
-    if ((c->cfg.flags & S2D_CFG_COUNT_PAIRS) || c->ref_order) { // (reference order: its backward pass is a launch of its own)
+    if ((c->cfg.flags & S2D_CFG_COUNT_PAIRS) || c->scratch.reference_order()) { // (reference order: its backward pass is a launch of its own)
         if (int rc = queue_forward(c)) return rc;
         return queue_backward(c, need_opacity_grad);
     }
@@ -554,7 +484,7 @@ int queue_forward_backward(s2d_ctx* c, bool need_opacity_grad, bool write_image)
     job.need_opacity_grad = need_opacity_grad;
     job.write_image = write_image;
     if (int rc = queue_raster(c, job)) return rc;
-    return backward_queued(c, c->trace.plan(true, c->chunks.empty())); // (launch_job asked the same plan about the fused launch)
+    return backward_queued(c, c->trace.plan(true, !c->ranges.active())); // (launch_job asked the same plan about the fused launch)
 }
 
 int queue_adam(s2d_ctx* c, uint32_t flags)
@@ -563,14 +493,13 @@ int queue_adam(s2d_ctx* c, uint32_t flags)
     c->beta2t *= kAdamBeta2;
     // With re-usable lists the Adam kernel also projects the updated splats and checks them against their binned
     // rectangles (what the next forward needs), which saves a pass over the parameters per iteration.
-    const bool fuse = c->lists_valid && c->rebin_interval > 1;
-    if (fuse) c->check_seq++;
+    const bool fuse = c->reuse.adam_checks(c->lists_valid);
     S2D_HIP(c, launch_adam(adam_args(c, flags, fuse), c->stream));
-    if (fuse) S2D_HIP(c, hipEventRecord(c->ev_flag, c->stream));
+    if (fuse) S2D_HIP(c, c->reuse.check_queued());
     invalidate(c, Stale::Projection);
     c->proj_fresh = fuse; // (then the step projected what it wrote)
     c->iterations++; // main.cpp:809
-    c->since_rebin++;
+    c->reuse.step_queued();
     return S2D_OK;
 }
 
@@ -674,6 +603,103 @@ s2d_loss_terms loss_terms_of(const s2d_ctx* c, const double* sums, const float* 
     return t;
 }
 
+// The image crosses the ABI as floats; a context with S2D_CFG_FP16_IMAGES keeps halves (round to nearest even) and
+// converts on the way, through a temporary where the other side is host memory.
+// The whole target (main.cpp:254-259) -> imageRef; a slab context uploads and keeps its own rows only.  Waits.
+int upload_target(s2d_ctx* c, const float* rgba32f)
+{
+    const size_t px = slab_pixels(c), bytes = px * sizeof(float4);
+    const float* src = rgba32f + (size_t)c->g.row_begin * c->g.W * 4;
+    if (c->half_images) {
+        DevBuf<float4> tmp;
+        S2D_HIP(c, tmp.alloc(px));
+        const IdleAtExit idle{c->stream}; // (before tmp goes)
+        S2D_HIP(c, hipMemcpyAsync(tmp, src, bytes, hipMemcpyHostToDevice, c->stream));
+        S2D_HIP(c, launch_convert_f32_to_f16(tmp, c->d_ref, px, c->stream));
+    } else {
+        S2D_HIP(c, hipMemcpyAsync(c->d_ref, src, bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    S2D_HIP(c, hipStreamSynchronize(c->stream));
+    return S2D_OK;
+}
+
+// image0 (the rows of the slab) -> dst.  to_host: waits; otherwise dst is device memory and the copy is only queued.
+int download_image0(s2d_ctx* c, float* dst, bool to_host)
+{
+    const size_t px = slab_pixels(c), bytes = px * sizeof(float4);
+    if (!c->half_images) {
+        S2D_HIP(c, hipMemcpyAsync(dst, c->d_image0, bytes, to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+    } else if (!to_host) {
+        S2D_HIP(c, launch_convert_f16_to_f32(c->d_image0, reinterpret_cast<float4*>(dst), px, c->stream));
+    } else {
+        DevBuf<float4> tmp;
+        S2D_HIP(c, tmp.alloc(px));
+        const IdleAtExit idle{c->stream}; // (before tmp goes)
+        S2D_HIP(c, launch_convert_f16_to_f32(c->d_image0, tmp, px, c->stream));
+        S2D_HIP(c, hipMemcpyAsync(dst, tmp, bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (to_host) S2D_HIP(c, hipStreamSynchronize(c->stream));
+    return S2D_OK;
+}
+
+// s2d_step (loss == nullptr) and s2d_step_loss: `iters` iterations queued in pieces of the rings' capacity, their squared
+// errors (and loss totals) read back per piece, the status word judged once at the end.
+int run_steps(s2d_ctx* c, int iters, uint32_t flags, const s2d_loss_config* loss, double* loss_out, double* mse_out)
+{
+    static_assert(LossTrace::kCapacity == SqerrTrace::kCapacity, "one piece size for both rings");
+    WalkFlags wf;
+    if (int rc = parse_walk_flags(c, flags, true, &wf)) return rc;
+    if (int rc = use_device(c)) return rc;
+    const double norm = mse_norm(c);
+    const float w[3] = {loss ? loss->w_mse : 0.0f, loss ? loss->w_l1 : 0.0f, loss ? loss->w_dssim : 0.0f};
+    const int call_first_iter = c->iterations;
+    std::vector<double> sums;
+    bool status_read = false;
+    for (int done = 0; done < iters;) {
+        const int piece = std::min<int>(iters - done, SqerrTrace::kCapacity);
+        const int first_iter = c->iterations;
+        for (int k = 0; k < piece; k++) {
+            if (loss) { // the loss kernels stand between the two walks (image0 stored every time)
+                if (int rc = queue_forward(c)) return rc;
+                if (int rc = queue_loss_backward(c, loss, wf.need_opacity_grad, wf.density)) return rc;
+            } else if (wf.density) { // the separate passes: only s2d_backward's kernel gathers the statistics (image0 stored every time)
+                if (int rc = queue_forward(c)) return rc;
+                if (int rc = queue_backward(c, wf.need_opacity_grad, nullptr, true)) return rc;
+            } else if (int rc = queue_forward_backward(c, wf.need_opacity_grad, done + k + 1 == iters)) {
+                return rc; // (image0 is stored by the last iteration of the call only: nothing else could observe the others)
+            }
+            if (int rc = queue_adam(c, flags)) return rc;
+        }
+        // The usual call (a frame, or a batch of frames, of the host loop) ends with a piece that fits the pinned buffer:
+        // trace and status word in ONE round trip.  Any other piece is read by itself, if there is something to read.
+        const bool with_status = done + piece == iters && piece <= SqerrTrace::kPinned;
+        double* const mse_dst = !mse_out ? nullptr : with_status ? c->trace.pinned() : mse_out + done;
+        if (loss_out) {
+            sums.resize((size_t)3 * piece);
+            S2D_HIP(c, c->loss.read(first_iter, piece, sums.data()));
+        }
+        if (mse_dst) S2D_HIP(c, c->trace.read(first_iter, piece, mse_dst));
+        if (with_status)
+            if (int rc = queue_status_read(c)) return rc;
+        if (with_status || loss_out || mse_out) S2D_HIP(c, hipStreamSynchronize(c->stream));
+        for (int k = 0; loss_out && k < piece; k++) loss_out[done + k] = loss_terms_of(c, &sums[(size_t)3 * k], w).total;
+        for (int k = 0; mse_out && k < piece; k++) mse_out[done + k] = mse_dst[k] / norm; // main.cpp:805
+        status_read = with_status;
+        done += piece;
+    }
+    const int rc = status_read ? judge_status(c) : check_status(c);
+    if (rc == S2D_E_NONFINITE) {
+        // The reference abort()s right after the Adam step of that iteration (main.cpp:752-785): its trace ends with
+        // that iteration's line.  The kernels of the later iterations queued here did nothing; their entries are NaN.
+        const int last_valid = c->h_status->first_nonfinite_iter - call_first_iter;
+        for (int k = std::max(last_valid + 1, 0); k < iters; k++) {
+            if (loss_out) loss_out[k] = std::nan("");
+            if (mse_out) mse_out[k] = std::nan("");
+        }
+    }
+    return rc;
+}
+
 } // namespace
 
 extern "C" {
@@ -699,8 +725,6 @@ int s2d_create(const s2d_config* cfg, s2d_ctx** out)
     c->n = cfg->n_splats;
     c->device = cfg->device;
     c->lr = cfg->training_rate > 0.0f ? cfg->training_rate : 0.05f; // main.cpp:715
-    c->rebin_interval = cfg->rebin_interval > 0 ? cfg->rebin_interval : INT_MAX; // default: rebuild on violation only
-    c->margin = c->rebin_interval > 1 ? (cfg->rebin_margin > 0.0f ? cfg->rebin_margin : 2.0f) : 0.0f;
 
     Geometry& g = c->g;
     g.W = cfg->width; g.H = cfg->height;
@@ -734,38 +758,20 @@ int s2d_create(const s2d_config* cfg, s2d_ctx** out)
     S2D_HIP(c, c->d_offsets.alloc(n));
     S2D_HIP(c, c->d_scan_temp.alloc(scan_temp_words((int64_t)n)));
     S2D_HIP(c, c->lists.create(g, n, (cfg->flags & S2D_CFG_GENERIC_BINNING) != 0));
-    if (const char* e = getenv("S2D_CHUNK_PAIRS")) { // pairs per index range (tests; default 2^30, never beyond 32-bit positions)
-        const unsigned long long v = strtoull(e, nullptr, 10);
-        if (v > 0) c->chunk_pairs = std::min<unsigned long long>(v, 0xFFFF0000ull - 1);
-    }
-    c->ref_order = (cfg->flags & S2D_CFG_REFERENCE_ORDER) != 0;
-    if (c->ref_order) {
-        if (const char* e = getenv("S2D_REFERENCE_ORDER_MAX_BYTES")) {
-            const unsigned long long v = strtoull(e, nullptr, 10);
-            if (v > 0) c->ref_max_bytes = v;
-        }
-        S2D_HIP(c, c->d_pixel_sqerr.alloc(px));
-    }
-    c->deterministic = (cfg->flags & S2D_CFG_DETERMINISTIC) != 0 && !c->ref_order; // (reference order alone decides the result)
-    if (c->deterministic) {
-        S2D_HIP(c, c->d_det_touched.alloc(n));
-        S2D_HIP(c, hipMemset(c->d_det_touched, 0, n * sizeof(uint32_t)));
-    }
+    c->ranges.create(g, c->stream);
+    const bool ref_order = (cfg->flags & S2D_CFG_REFERENCE_ORDER) != 0; // (alone decides the result: deterministic mode is off then)
+    S2D_HIP(c, c->scratch.create(ref_order ? PairScratch::Mode::ReferenceOrder : (cfg->flags & S2D_CFG_DETERMINISTIC) ? PairScratch::Mode::Deterministic
+                                           : PairScratch::Mode::Atomic, g, n, c->stream));
     c->half_images = (cfg->flags & S2D_CFG_FP16_IMAGES) != 0;
     c->pixel_bytes = c->half_images ? 8 : sizeof(float4);
     S2D_HIP(c, c->d_image0.alloc(px * c->pixel_bytes));
     S2D_HIP(c, c->d_ref.alloc(px * c->pixel_bytes));
-    S2D_HIP(c, c->d_tile_exec.alloc((size_t)g.num_tiles));
-    S2D_HIP(c, c->d_retire_hint.alloc((size_t)g.num_tiles));
-    S2D_HIP(c, hipMemset(c->d_retire_hint, 0xFF, (size_t)g.num_tiles * sizeof(uint32_t)));
     S2D_HIP(c, c->d_status.alloc(1));
     S2D_HIP(c, c->trace.create(g.num_tiles, c->n, c->d_status, c->stream));
     c->density.create(c->n, c->stream);
     S2D_HIP(c, c->d_counters.alloc(1));
-    S2D_HIP(c, c->ev_flag.create(hipEventDisableTiming));
+    S2D_HIP(c, c->reuse.create(cfg->rebin_interval, cfg->rebin_margin, c->stream));
     S2D_HIP(c, c->h_status.alloc(1, hipHostMallocDefault));
-    S2D_HIP(c, c->h_rebin_stamp.alloc(16, hipHostMallocMapped));
-    *c->h_rebin_stamp = 0;
 
     S2D_HIP(c, hipMemsetAsync(c->d_grads_own, 0, n * 9 * sizeof(float), c->stream));
     S2D_HIP(c, hipMemsetAsync(c->d_image0, 0, px * c->pixel_bytes, c->stream));
@@ -797,20 +803,7 @@ int s2d_set_target(s2d_ctx* c, const float* rgba32f)
 {
     if (!c || !rgba32f) return S2D_E_INVALID;
     if (int rc = use_device(c)) return rc;
-    // the caller hands over the whole image (main.cpp:254-259); a slab context uploads and keeps its own rows only
-    const size_t px = slab_pixels(c), bytes = px * sizeof(float4);
-    const float* src = rgba32f + (size_t)c->g.row_begin * c->g.W * 4;
-    if (c->half_images) { // floats cross the boundary; the device keeps them as fp16 (round to nearest even)
-        DevBuf<float4> tmp;
-        S2D_HIP(c, tmp.alloc(px));
-        const IdleAtExit idle{c->stream}; // (before tmp goes)
-        S2D_HIP(c, hipMemcpyAsync(tmp, src, bytes, hipMemcpyHostToDevice, c->stream));
-        S2D_HIP(c, launch_convert_f32_to_f16(tmp, c->d_ref, px, c->stream));
-        S2D_HIP(c, hipStreamSynchronize(c->stream));
-    } else {
-        S2D_HIP(c, hipMemcpyAsync(c->d_ref, src, bytes, hipMemcpyHostToDevice, c->stream));
-        S2D_HIP(c, hipStreamSynchronize(c->stream));
-    }
+    if (int rc = upload_target(c, rgba32f)) return rc;
     c->have_target = true;
     invalidate(c, Stale::Frames);
     return S2D_OK;
@@ -908,19 +901,7 @@ int s2d_get_image_rows(s2d_ctx* c, float* rgba32f_rows)
 {
     if (!c || !rgba32f_rows) return S2D_E_INVALID;
     if (int rc = use_device(c)) return rc;
-    const size_t px = slab_pixels(c), bytes = px * sizeof(float4);
-    if (c->half_images) {
-        DevBuf<float4> tmp;
-        S2D_HIP(c, tmp.alloc(px));
-        const IdleAtExit idle{c->stream}; // (before tmp goes)
-        S2D_HIP(c, launch_convert_f16_to_f32(c->d_image0, tmp, px, c->stream));
-        S2D_HIP(c, hipMemcpyAsync(rgba32f_rows, tmp, bytes, hipMemcpyDeviceToHost, c->stream));
-        S2D_HIP(c, hipStreamSynchronize(c->stream));
-        return S2D_OK;
-    }
-    S2D_HIP(c, hipMemcpyAsync(rgba32f_rows, c->d_image0, bytes, hipMemcpyDeviceToHost, c->stream));
-    S2D_HIP(c, hipStreamSynchronize(c->stream));
-    return S2D_OK;
+    return download_image0(c, rgba32f_rows, true);
 }
 
 int s2d_get_image(s2d_ctx* c, float* rgba32f)
@@ -945,11 +926,10 @@ int s2d_forward_backward(s2d_ctx* c, uint32_t flags)
 int s2d_backward(s2d_ctx* c, uint32_t flags)
 {
     if (!c) return S2D_E_INVALID;
-    const bool density = (flags & S2D_BWD_DENSITY_STATS) != 0;
-    if (density)
-        if (int rc = density_refused(c)) return rc;
+    WalkFlags wf;
+    if (int rc = parse_walk_flags(c, flags, false, &wf)) return rc;
     if (int rc = use_device(c)) return rc;
-    return queue_backward(c, !(flags & S2D_BWD_SKIP_OPACITY_GRAD), nullptr, density);
+    return queue_backward(c, wf.need_opacity_grad, nullptr, wf.density);
 }
 
 int s2d_backward_image_grads(s2d_ctx* c, const float* dimage_rows_device, uint32_t flags)
@@ -958,11 +938,10 @@ int s2d_backward_image_grads(s2d_ctx* c, const float* dimage_rows_device, uint32
     if ((uintptr_t)dimage_rows_device & 15u) return fail(c, S2D_E_INVALID, "the image gradient must be 16-byte aligned");
     if (c->cfg.flags & S2D_CFG_COUNT_PAIRS)
         return fail(c, S2D_E_INVALID, "pair counting (S2D_CFG_COUNT_PAIRS) has no backward pass from a caller's image gradient");
-    const bool density = (flags & S2D_BWD_DENSITY_STATS) != 0;
-    if (density)
-        if (int rc = density_refused(c)) return rc;
+    WalkFlags wf;
+    if (int rc = parse_walk_flags(c, flags, false, &wf)) return rc;
     if (int rc = use_device(c)) return rc;
-    return queue_backward(c, !(flags & S2D_BWD_SKIP_OPACITY_GRAD), reinterpret_cast<const float4*>(dimage_rows_device), density);
+    return queue_backward(c, wf.need_opacity_grad, reinterpret_cast<const float4*>(dimage_rows_device), wf.density);
 }
 
 int s2d_set_splats_device(s2d_ctx* c, const float* splats_device)
@@ -983,12 +962,7 @@ int s2d_get_image_rows_device(s2d_ctx* c, float* rgba32f_rows_device)
     if (!c || !rgba32f_rows_device) return S2D_E_INVALID;
     if ((uintptr_t)rgba32f_rows_device & 15u) return fail(c, S2D_E_INVALID, "the image buffer must be 16-byte aligned");
     if (int rc = use_device(c)) return rc;
-    const size_t px = slab_pixels(c);
-    if (c->half_images)
-        S2D_HIP(c, launch_convert_f16_to_f32(c->d_image0, reinterpret_cast<float4*>(rgba32f_rows_device), px, c->stream));
-    else
-        S2D_HIP(c, hipMemcpyAsync(rgba32f_rows_device, c->d_image0, px * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-    return S2D_OK;
+    return download_image0(c, rgba32f_rows_device, false);
 }
 
 int s2d_get_grads(s2d_ctx* c, s2d_splat* dsplats)
@@ -1044,7 +1018,7 @@ int s2d_relocate(s2d_ctx* c, const s2d_relocate_config* cfg, int32_t* moved)
     if (c->g.row_begin != 0 || c->g.row_end != c->g.H)
         return fail(c, S2D_E_INVALID, "s2d_relocate needs the statistics of the whole image: this context owns a row slab");
     if (c->state.held()) return fail(c, S2D_E_INVALID, "s2d_relocate: this context holds a subset of the splats (s2d_halo_commit)");
-    if (c->ref_order) return fail(c, S2D_E_INVALID, "s2d_relocate is not available with S2D_CFG_REFERENCE_ORDER");
+    if (c->scratch.reference_order()) return fail(c, S2D_E_INVALID, "s2d_relocate is not available with S2D_CFG_REFERENCE_ORDER");
     const int passes = c->density.passes();
     if (passes == 0) return fail(c, S2D_E_STATE, "s2d_relocate needs a pass with S2D_BWD_DENSITY_STATS since the last reset");
     if (int rc = use_device(c)) return rc;
@@ -1101,11 +1075,10 @@ int s2d_loss_backward(s2d_ctx* c, const s2d_loss_config* cfg, uint32_t flags)
 {
     if (!c) return S2D_E_INVALID;
     if (int rc = loss_refused(c, cfg)) return rc;
-    const bool density = (flags & S2D_BWD_DENSITY_STATS) != 0;
-    if (density)
-        if (int rc = density_refused(c)) return rc;
+    WalkFlags wf;
+    if (int rc = parse_walk_flags(c, flags, false, &wf)) return rc;
     if (int rc = use_device(c)) return rc;
-    return queue_loss_backward(c, cfg, !(flags & S2D_BWD_SKIP_OPACITY_GRAD), density);
+    return queue_loss_backward(c, cfg, wf.need_opacity_grad, wf.density);
 }
 
 int s2d_loss_get(s2d_ctx* c, s2d_loss_terms* out)
@@ -1124,41 +1097,7 @@ int s2d_step_loss(s2d_ctx* c, int32_t iters, uint32_t flags, const s2d_loss_conf
 {
     if (!c || iters < 0) return S2D_E_INVALID;
     if (int rc = loss_refused(c, cfg)) return rc;
-    const bool density = (flags & S2D_STEP_DENSITY_STATS) != 0;
-    if (density)
-        if (int rc = density_refused(c)) return rc;
-    if (int rc = use_device(c)) return rc;
-    const double norm = mse_norm(c);
-    const float w[3] = {cfg->w_mse, cfg->w_l1, cfg->w_dssim};
-    const int call_first_iter = c->iterations;
-    std::vector<double> sums;
-    for (int done = 0; done < iters;) {
-        const int chunk = std::min<int>(iters - done, LossTrace::kCapacity); // (both rings have this many slots)
-        const int first_iter = c->iterations;
-        for (int k = 0; k < chunk; k++) {
-            if (int rc = queue_forward(c)) return rc;
-            if (int rc = queue_loss_backward(c, cfg, (flags & S2D_STEP_OPTIMIZE_OPACITY) != 0, density)) return rc;
-            if (int rc = queue_adam(c, flags)) return rc;
-        }
-        if (loss_out) {
-            sums.resize((size_t)3 * chunk);
-            S2D_HIP(c, c->loss.read(first_iter, chunk, sums.data()));
-        }
-        if (mse_out) S2D_HIP(c, c->trace.read(first_iter, chunk, mse_out + done));
-        if (loss_out || mse_out) S2D_HIP(c, hipStreamSynchronize(c->stream));
-        for (int k = 0; loss_out && k < chunk; k++) loss_out[done + k] = loss_terms_of(c, &sums[(size_t)3 * k], w).total;
-        for (int k = 0; mse_out && k < chunk; k++) mse_out[done + k] /= norm; // main.cpp:805
-        done += chunk;
-    }
-    const int rc = check_status(c);
-    if (rc == S2D_E_NONFINITE) { // as s2d_step: the trace ends with the failing iteration's line
-        const int last_valid = c->h_status->first_nonfinite_iter - call_first_iter;
-        for (int k = std::max(last_valid + 1, 0); k < iters; k++) {
-            if (loss_out) loss_out[k] = std::nan("");
-            if (mse_out) mse_out[k] = std::nan("");
-        }
-    }
-    return rc;
+    return run_steps(c, iters, flags, cfg, loss_out, mse_out);
 }
 
 int s2d_adam_step(s2d_ctx* c, uint32_t flags)
@@ -1172,50 +1111,7 @@ int s2d_adam_step(s2d_ctx* c, uint32_t flags)
 int s2d_step(s2d_ctx* c, int32_t iters, uint32_t flags, double* mse_out)
 {
     if (!c || iters < 0) return S2D_E_INVALID;
-    const bool density = (flags & S2D_STEP_DENSITY_STATS) != 0;
-    if (density)
-        if (int rc = density_refused(c)) return rc;
-    if (int rc = use_device(c)) return rc;
-    const double norm = mse_norm(c);
-    const int call_first_iter = c->iterations;
-    int done = 0;
-    bool status_read = false;
-    while (done < iters) {
-        const int chunk = std::min<int>(iters - done, SqerrTrace::kCapacity);
-        const int first_iter = c->iterations;
-        for (int k = 0; k < chunk; k++) {
-            // image0 is stored by the last iteration of the call only: nothing else could observe the others
-            const bool last = done + k + 1 == iters;
-            if (density) { // the separate passes: only s2d_backward's kernel gathers the statistics (image0 stored every time)
-                if (int rc = queue_forward(c)) return rc;
-                if (int rc = queue_backward(c, (flags & S2D_STEP_OPTIMIZE_OPACITY) != 0, nullptr, true)) return rc;
-            } else if (int rc = queue_forward_backward(c, (flags & S2D_STEP_OPTIMIZE_OPACITY) != 0, last)) {
-                return rc;
-            }
-            if (int rc = queue_adam(c, flags)) return rc;
-        }
-        const bool last_chunk = done + chunk == iters;
-        if (mse_out && last_chunk && chunk <= SqerrTrace::kPinned) {
-            // the usual call (a frame, or a batch of frames, of the host loop): trace and status word in one round trip
-            S2D_HIP(c, c->trace.read(first_iter, chunk, c->trace.pinned()));
-            if (int rc = queue_status_read(c)) return rc;
-            S2D_HIP(c, hipStreamSynchronize(c->stream));
-            for (int k = 0; k < chunk; k++) mse_out[done + k] = c->trace.pinned()[k] / norm; // main.cpp:805
-            status_read = true;
-        } else if (mse_out) {
-            if (int rc = s2d_get_sqerr_trace(c, first_iter, chunk, mse_out + done)) return rc;
-            for (int k = 0; k < chunk; k++) mse_out[done + k] /= norm; // main.cpp:805
-        }
-        done += chunk;
-    }
-    const int rc = status_read ? judge_status(c) : check_status(c);
-    if (rc == S2D_E_NONFINITE && mse_out) {
-        // The reference abort()s right after the Adam step of that iteration (main.cpp:752-785): its trace ends with
-        // that iteration's line.  The kernels of the later iterations queued here did nothing; their entries are NaN.
-        const int last_valid = c->h_status->first_nonfinite_iter - call_first_iter;
-        for (int k = std::max(last_valid + 1, 0); k < iters; k++) mse_out[k] = std::nan("");
-    }
-    return rc;
+    return run_steps(c, iters, flags, nullptr, nullptr, mse_out);
 }
 
 int s2d_get_mse(s2d_ctx* c, double* mse)
@@ -1259,7 +1155,7 @@ int s2d_halo_masks(s2d_ctx* c, int32_t world, const int32_t* row_bounds, float m
 int s2d_halo_commit(s2d_ctx* c, const uint32_t* masks_device, int32_t rank, int32_t added)
 {
     if (!c || rank < 0 || rank > 31) return S2D_E_INVALID;
-    if (masks_device && c->ref_order)
+    if (masks_device && c->scratch.reference_order())
         return fail(c, S2D_E_INVALID, "reference order (S2D_CFG_REFERENCE_ORDER) has no slab ownership: the chains run over all splats");
     if (int rc = use_device(c)) return rc;
     const bool had = c->state.held() != nullptr;

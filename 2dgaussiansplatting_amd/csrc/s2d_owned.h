@@ -12,6 +12,13 @@
 
 #define S2D_LOCAL __attribute__((visibility("hidden"))) // nothing of these types is exported from the library
 
+// In a function that returns hipError_t: hand a failure on.
+#define S2D_TRY(expr)                      \
+    do {                                   \
+        const hipError_t e_ = (expr);      \
+        if (e_ != hipSuccess) return e_;   \
+    } while (0)
+
 namespace s2d {
 
 template <typename T>

@@ -6,12 +6,6 @@
 
 namespace s2d {
 
-#define S2D_TRY(expr)                      \
-    do {                                   \
-        const hipError_t e_ = (expr);      \
-        if (e_ != hipSuccess) return e_;   \
-    } while (0)
-
 hipError_t SplatState::create(int n, hipStream_t stream)
 {
     n_ = n, stream_ = stream;
