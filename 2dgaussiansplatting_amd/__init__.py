@@ -37,6 +37,9 @@ S2D_CFG_REFERENCE_ORDER = 0x40
 S2D_BWD_SKIP_OPACITY_GRAD = 0x1
 S2D_FB_SKIP_IMAGE = 0x2
 S2D_BWD_DENSITY_STATS = 0x4
+S2D_SEED_TARGET_EDGES, S2D_SEED_ERROR, S2D_SEED_CALLER = 0, 1, 2
+S2D_SEED_SQUARED = 0x1
+SEED_SOURCES = {"edges": S2D_SEED_TARGET_EDGES, "error": S2D_SEED_ERROR, "caller": S2D_SEED_CALLER}
 STATUS_NAMES = {0: "S2D_OK", 1: "S2D_E_INVALID", 2: "S2D_E_HIP", 3: "S2D_E_NONFINITE", 4: "S2D_E_NOMEM",
                 5: "S2D_E_STATE"}
 
@@ -56,6 +59,11 @@ class _Config(C.Structure):
 
 class _RelocateConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("max_moves", C.c_int32), ("min_weight", C.c_float), ("shrink", C.c_float)]
+
+
+class _SeedConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("source", C.c_uint32), ("flags", C.c_uint32), ("seed", C.c_uint32),
+                ("floor", C.c_uint32), ("scale", C.c_float), ("opacity", C.c_float), ("importance_device", C.c_void_p)]
 
 
 class _LossConfig(C.Structure):
@@ -88,6 +96,7 @@ ABI_SYMBOLS = [
     "s2d_get_image", "s2d_get_image_rows", "s2d_backward", "s2d_backward_image_grads", "s2d_set_splats_device", "s2d_get_image_rows_device", "s2d_forward_backward", "s2d_get_grads", "s2d_adam_step", "s2d_step", "s2d_get_mse",
     "s2d_bind_grads_device", "s2d_grads_device_ptr", "s2d_stream", "s2d_get_sqerr_trace", "s2d_synchronize", "s2d_get_stats",
     "s2d_get_rebuild_count", "s2d_density_get", "s2d_density_get_device", "s2d_density_reset", "s2d_relocate",
+    "s2d_importance", "s2d_seed_splats", "s2d_reseed",
     "s2d_loss_image_grads_device", "s2d_loss_backward", "s2d_loss_get", "s2d_step_loss",
     "s2d_last_error", "s2d_test_sincos", "s2d_test_sort_pairs", "s2d_test_exclusive_scan",
     "s2d_test_sort_tile_offsets", "s2d_debug_get_tile_lists",
@@ -250,6 +259,9 @@ def load_library(path=None):
     sig("s2d_density_get_device", [vp, vp, vp])
     sig("s2d_density_reset", [vp])
     sig("s2d_relocate", [vp, C.POINTER(_RelocateConfig), vp])
+    sig("s2d_importance", [vp, C.POINTER(_SeedConfig), vp, vp])
+    sig("s2d_seed_splats", [vp, C.POINTER(_SeedConfig), vp, i32, vp])
+    sig("s2d_reseed", [vp, C.POINTER(_SeedConfig), i32, C.c_float, vp])
     sig("s2d_loss_image_grads_device", [vp, C.POINTER(_LossConfig), vp])
     sig("s2d_loss_backward", [vp, C.POINTER(_LossConfig), u32])
     sig("s2d_loss_get", [vp, C.POINTER(_LossTerms)])
@@ -542,6 +554,44 @@ class Trainer:
         cfg = _RelocateConfig(C.sizeof(_RelocateConfig), int(max_moves), float(min_weight), float(shrink))
         moved = C.c_int32()
         self._ck(self.L.s2d_relocate(self._h, C.byref(cfg), C.byref(moved)))
+        return moved.value
+
+    # -- importance-sampled placement (include/splat2d.h, "importance-sampled placement")
+    @staticmethod
+    def _seed_config(source, squared, floor, scale, opacity, seed, importance_ptr):
+        src = SEED_SOURCES[source] if isinstance(source, str) else int(source)
+        return _SeedConfig(C.sizeof(_SeedConfig), src, S2D_SEED_SQUARED if squared else 0, int(seed) & 0xFFFFFFFF, int(floor),
+                           float(scale), float(opacity), C.c_void_p(importance_ptr) if importance_ptr else None)
+
+    def importance(self, source="edges", squared=False, floor=0, importance_ptr=None):
+        """The importance map of the current images: -> ((H, W) uint32 q, total).  source: "edges" (the target's central
+        differences), "error" (|image0 - target|, needs forward()) or "caller" (importance_ptr: H * W floats in device memory)."""
+        cfg = self._seed_config(source, squared, floor, 0.0, 0.0, 0, importance_ptr)
+        q = np.zeros((self.H, self.W), dtype=np.uint32)
+        total = C.c_uint64()
+        self._ck(self.L.s2d_importance(self._h, C.byref(cfg), _p(q), C.byref(total)))
+        return q, total.value
+
+    def seed(self, ids=None, source="edges", squared=False, floor=0, scale=0.0, opacity=0.0, seed=0, importance_ptr=None,
+             count=None):
+        """s2d_seed_splats: the rows `ids` (None: rows 0 .. count - 1, count None: all) drawn from the importance map and
+        written with the target's colour, moments zeroed; returns the number of rows written (0 for an all-zero map)."""
+        cfg = self._seed_config(source, squared, floor, scale, opacity, seed, importance_ptr)
+        placed = C.c_int32()
+        if ids is None:
+            self._ck(self.L.s2d_seed_splats(self._h, C.byref(cfg), None, self.n if count is None else int(count), C.byref(placed)))
+        else:
+            a = np.ascontiguousarray(ids, dtype=np.int32)
+            self._ck(self.L.s2d_seed_splats(self._h, C.byref(cfg), _p(a), len(a), C.byref(placed)))
+        return placed.value
+
+    def reseed(self, max_moves, min_weight, source="error", squared=False, floor=0, scale=0.0, opacity=0.0, seed=0,
+               importance_ptr=None):
+        """s2d_reseed: seed() over the starved rows of the density statistics (weight per pass < min_weight, the lowest
+        first, at most max_moves); returns the number of rows written.  The statistics are reset."""
+        cfg = self._seed_config(source, squared, floor, scale, opacity, seed, importance_ptr)
+        moved = C.c_int32()
+        self._ck(self.L.s2d_reseed(self._h, C.byref(cfg), int(max_moves), float(min_weight), C.byref(moved)))
         return moved.value
 
     def mse(self):

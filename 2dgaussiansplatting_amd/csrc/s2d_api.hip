@@ -27,6 +27,8 @@
 #include "s2d_lists.h"
 #include "s2d_loss.h"
 #include "s2d_owned.h"
+#include "s2d_seed.h"
+#include "s2d_seed_math.h"
 #include "s2d_state.h"
 
 using namespace s2d;
@@ -68,6 +70,7 @@ struct s2d_ctx {
     LossTrace loss;                // per-tile sums and the ring of per-iteration totals
     DevBuf<float> d_loss_maps;     // [9][pixels]: the derivative maps between the two window passes (w_dssim > 0 only)
     DevBuf<float4> d_loss_grad;    // dL/d(image0) of s2d_loss_backward / s2d_step_loss
+    SeedScratch seed;              // the importance map of s2d_importance / s2d_seed_splats / s2d_reseed (s2d_seed.h), on first use
     DevBuf<DeviceStatus> d_status;
     DevBuf<PairCounters> d_counters;
     // pinned host mirrors
@@ -296,7 +299,7 @@ int launch_job(s2d_ctx* c, bool optimistic, const RasterJob& job)
 //   all splats replaced (s2d_init_splats, s2d_set_splats): Lists; splats_replaced() = state.written() + a fresh status
 //     word.  init also zeroes the gradients and restarts the counters, and asks for the arrays with discard_all(): every
 //     record, moments included, is new.
-//   some splat rows replaced (s2d_rows_scatter): Projection; state.written().  Not Lists: a row moves a splat a little,
+//   some splat rows replaced (s2d_rows_scatter; s2d_relocate, s2d_seed_splats, s2d_reseed): Projection; state.written().  Not Lists: a row moves a splat a little,
 //     and the containment check of the projection that follows asks for new lists if it left its rectangle.
 //   all splats replaced from device memory (s2d_set_splats_device): as some rows, over all of them -- Projection;
 //     state.written().  Not Lists, and no fresh status word: this is the call of an optimisation loop outside the
@@ -700,6 +703,74 @@ int run_steps(s2d_ctx* c, int iters, uint32_t flags, const s2d_loss_config* loss
     return rc;
 }
 
+// ---- importance-sampled placement (s2d_seed.h) -----------------------------------------------------------------------
+// Everything s2d_importance / s2d_seed_splats / s2d_reseed refuse for the configuration or the context, before any device
+// work (S2D_E_INVALID), then what they refuse for the order of calls (S2D_E_STATE).
+int seed_refused(s2d_ctx* c, const s2d_seed_config* cfg)
+{
+    if (!cfg || cfg->struct_size != sizeof(s2d_seed_config)) return fail(c, S2D_E_INVALID, "s2d_seed_config: NULL or wrong struct_size");
+    if (cfg->source > S2D_SEED_CALLER) return fail(c, S2D_E_INVALID, "s2d_seed_config: unknown source %u", cfg->source);
+    if (cfg->flags & ~S2D_SEED_SQUARED) return fail(c, S2D_E_INVALID, "s2d_seed_config: unknown flags 0x%x", cfg->flags);
+    if (cfg->floor > kSeedQMax) return fail(c, S2D_E_INVALID, "s2d_seed_config: floor %u > 4095", cfg->floor);
+    if (!(cfg->scale >= 0.0f) || std::isinf(cfg->scale)) return fail(c, S2D_E_INVALID, "s2d_seed_config: scale must be finite and >= 0 (0: sqrt(W H / n))");
+    if (!(cfg->opacity >= 0.0f && cfg->opacity <= 1.0f)) return fail(c, S2D_E_INVALID, "s2d_seed_config: opacity must be 0 (meaning 1) or in (0, 1]");
+    if ((cfg->source == S2D_SEED_CALLER) != (cfg->importance_device != nullptr))
+        return fail(c, S2D_E_INVALID, "s2d_seed_config: importance_device goes with S2D_SEED_CALLER, and only with it");
+    if (c->g.row_begin != 0 || c->g.row_end != c->g.H)
+        return fail(c, S2D_E_INVALID, "the importance map covers the whole image: this context owns a row slab");
+    if (c->state.held()) return fail(c, S2D_E_INVALID, "placement needs every splat: this context holds a subset (s2d_halo_commit)");
+    return S2D_OK;
+}
+
+int seed_state_refused(s2d_ctx* c, const s2d_seed_config* cfg)
+{
+    if (!c->have_target) return fail(c, S2D_E_STATE, "no target image set (s2d_set_target)");
+    if (cfg->source == S2D_SEED_ERROR && !c->have_forward)
+        return fail(c, S2D_E_STATE, "S2D_SEED_ERROR needs s2d_forward on the current parameters");
+    return S2D_OK;
+}
+
+// The map of the current images (queued) and its total (waits).
+int seed_map(s2d_ctx* c, const s2d_seed_config* cfg, SeedMap* map, uint64_t* total)
+{
+    S2D_HIP(c, c->seed.ensure(slab_pixels(c), map));
+    SeedMapArgs a;
+    a.source = (SeedSource)cfg->source; a.image0 = c->d_image0; a.image_ref = c->d_ref; a.caller = cfg->importance_device;
+    a.half_images = c->half_images; a.W = c->g.W; a.H = c->g.H; a.squared = (cfg->flags & S2D_SEED_SQUARED) != 0; a.floor_q = cfg->floor;
+    a.map = *map;
+    S2D_HIP(c, launch_seed_map(a, c->stream));
+    S2D_HIP(c, hipMemcpyAsync(total, map->share_prefix + (map->shares - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    S2D_HIP(c, hipStreamSynchronize(c->stream));
+    return S2D_OK;
+}
+
+// The rows `ids` (distinct, in range; null: 0 .. count - 1) drawn from the map of the current images and written; what
+// follows a write of some rows (the table above invalidate()).  *placed: count, or 0 for a map whose total is 0.
+int seed_rows(s2d_ctx* c, const s2d_seed_config* cfg, const int32_t* ids, int count, int32_t* placed)
+{
+    *placed = 0;
+    SeedMap map;
+    uint64_t total = 0;
+    if (int rc = seed_map(c, cfg, &map, &total)) return rc;
+    if (total == 0 || count == 0) return S2D_OK;
+    DevBuf<int32_t> d_ids;
+    if (ids) S2D_HIP(c, d_ids.alloc((size_t)count));
+    const IdleAtExit idle{c->stream}; // (before d_ids goes, and while `ids` is read)
+    if (ids) S2D_HIP(c, hipMemcpyAsync(d_ids, ids, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    SplatState::Arrays now;
+    S2D_HIP(c, c->state.current(&now));
+    SeedPlaceArgs p;
+    p.map = map; p.total = total; p.ids = ids ? (const int32_t*)d_ids : nullptr; p.count = count; p.seed = cfg->seed;
+    p.image_ref = c->d_ref; p.half_images = c->half_images; p.W = c->g.W; p.H = c->g.H;
+    p.scale = seed_scale(cfg->scale, c->g.W, c->g.H, c->n); p.opacity = seed_opacity(cfg->opacity);
+    p.splats = now.splats; p.adams = now.adams;
+    S2D_HIP(c, launch_seed_place(p, c->stream));
+    S2D_HIP(c, c->state.written(false));
+    invalidate(c, Stale::Projection); // (as s2d_rows_scatter: the containment check asks for new lists where a row left its rectangle)
+    *placed = count;
+    return S2D_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1059,6 +1130,70 @@ int s2d_relocate(s2d_ctx* c, const s2d_relocate_config* cfg, int32_t* moved)
     }
     S2D_HIP(c, c->density.reset());
     if (moved) *moved = moves;
+    return S2D_OK;
+}
+
+int s2d_importance(s2d_ctx* c, const s2d_seed_config* cfg, uint32_t* q_host, uint64_t* total)
+{
+    if (!c) return S2D_E_INVALID;
+    if (int rc = seed_refused(c, cfg)) return rc;
+    if (int rc = seed_state_refused(c, cfg)) return rc;
+    if (int rc = use_device(c)) return rc;
+    SeedMap map;
+    uint64_t sum = 0;
+    if (int rc = seed_map(c, cfg, &map, &sum)) return rc;
+    if (q_host) {
+        S2D_HIP(c, hipMemcpyAsync(q_host, map.q, map.pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        S2D_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    if (total) *total = sum;
+    return S2D_OK;
+}
+
+int s2d_seed_splats(s2d_ctx* c, const s2d_seed_config* cfg, const int32_t* ids_host, int32_t count, int32_t* placed)
+{
+    if (!c) return S2D_E_INVALID;
+    if (placed) *placed = 0;
+    if (int rc = seed_refused(c, cfg)) return rc;
+    if (count < 0 || count > c->n) return fail(c, S2D_E_INVALID, "s2d_seed_splats: count %d outside 0 .. n_splats", count);
+    if (ids_host) {
+        std::vector<bool> seen((size_t)c->n, false);
+        for (int j = 0; j < count; j++) {
+            const int32_t i = ids_host[j];
+            if (i < 0 || i >= c->n || seen[(size_t)i]) return fail(c, S2D_E_INVALID, "s2d_seed_splats: ids[%d] = %d is out of range or repeated", j, i);
+            seen[(size_t)i] = true;
+        }
+    }
+    if (int rc = seed_state_refused(c, cfg)) return rc;
+    if (int rc = use_device(c)) return rc;
+    int32_t done = 0;
+    if (int rc = seed_rows(c, cfg, ids_host, count, &done)) return rc;
+    if (placed) *placed = done;
+    return S2D_OK;
+}
+
+int s2d_reseed(s2d_ctx* c, const s2d_seed_config* cfg, int32_t max_moves, float min_weight, int32_t* moved)
+{
+    if (!c) return S2D_E_INVALID;
+    if (moved) *moved = 0;
+    if (int rc = seed_refused(c, cfg)) return rc;
+    if (max_moves < 0 || std::isnan(min_weight)) return fail(c, S2D_E_INVALID, "s2d_reseed: max_moves >= 0 and a min_weight that is a number");
+    if (c->scratch.reference_order()) return fail(c, S2D_E_INVALID, "s2d_reseed is not available with S2D_CFG_REFERENCE_ORDER");
+    if (int rc = seed_state_refused(c, cfg)) return rc;
+    const int passes = c->density.passes();
+    if (passes == 0) return fail(c, S2D_E_STATE, "s2d_reseed needs a pass with S2D_BWD_DENSITY_STATS since the last reset");
+    if (int rc = use_device(c)) return rc;
+    const size_t n = (size_t)c->n;
+    std::vector<float> stats(n * 3);
+    std::vector<int32_t> ids(std::min<size_t>((size_t)max_moves, n));
+    if (n > 0) S2D_HIP(c, hipMemcpyAsync(stats.data(), c->density.data(), n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    S2D_HIP(c, hipStreamSynchronize(c->stream));
+    const int starved = density_starved(c->n, stats.data(), passes, max_moves, min_weight, ids.data());
+    int32_t done = 0;
+    if (starved > 0)
+        if (int rc = seed_rows(c, cfg, ids.data(), starved, &done)) return rc;
+    S2D_HIP(c, c->density.reset());
+    if (moved) *moved = done;
     return S2D_OK;
 }
 

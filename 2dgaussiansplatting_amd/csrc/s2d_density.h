@@ -72,4 +72,25 @@ static inline int density_plan(int n, const float* stats, int passes, int max_mo
     return (int)moves;
 }
 
+// Rules 1-2 alone, for s2d_reseed, which needs no donors: the starved splats -- w < min_weight --
+// ordered by (w ascending, index ascending), the first max_moves of them -> ids (room for min(max_moves, n) entries).
+// Returns their number.  Where donors are plentiful these are the starved rows of density_plan, in its order.
+static inline int density_starved(int n, const float* stats, int passes, int max_moves, float min_weight, int32_t* ids)
+{
+    if (n <= 0 || passes <= 0 || max_moves <= 0) return 0;
+    struct Key {
+        double v;
+        int i;
+    };
+    std::vector<Key> starved;
+    for (int i = 0; i < n; i++) {
+        const double w = (double)stats[3 * (size_t)i + 2] / (double)passes;
+        if (w < (double)min_weight) starved.push_back(Key{w, i});
+    }
+    std::sort(starved.begin(), starved.end(), [](const Key& x, const Key& y) { return x.v < y.v || (x.v == y.v && x.i < y.i); });
+    const size_t kept = std::min(starved.size(), (size_t)max_moves);
+    for (size_t j = 0; j < kept; j++) ids[j] = starved[j].i;
+    return (int)kept;
+}
+
 } // namespace s2d

@@ -61,6 +61,18 @@ struct Options {
     int relocate_window = 10;        // --relocate-window S: the last S iterations before each relocation gather the statistics
     float relocate_max_fraction = 0.05f; // --relocate-max-fraction f: at most f * splats moved per relocation
     float relocate_min_weight = 0.5f;    // --relocate-min-weight w: a splat whose sum of T * alpha per pass is below w is starved
+    // Importance-sampled placement (include/splat2d.h "importance-sampled placement"; one context only).
+    std::string seed_init;           // --seed-init edges|uniform: init() followed by s2d_seed_splats over all rows -- positions drawn
+                                     // from the target's edge map (edges) or from that map under the full uniform share, floor 4095,
+                                     // where no pixel is more than twice as likely as another (uniform); colours from the target
+    // --reseed-every K: s2d_reseed before iteration K, 2K, ...: the starved splats are drawn again from the squared error map.
+    // Shaped like the relocation options, and like theirs the defaults are PROVISIONAL until someone sweeps them (DESIGN.md
+    // section 14): they are the one configuration that section measured.
+    int reseed_every = 0;
+    int reseed_window = 10;              // --reseed-window S: the last S iterations before each pass gather the statistics
+    float reseed_max_fraction = 0.1f;    // --reseed-max-fraction f: at most f * splats written per pass
+    float reseed_min_weight = 5.0f;      // --reseed-min-weight w: a splat whose sum of T * alpha per pass is below w is starved
+    float reseed_scale = 3.0f;           // --reseed-scale x: sx = sy of the rows written (0: sqrt(W H / splats))
     // --loss-weights M,L,D: train with L = sum of M * d^2 / 2 + L * |d| + D * (1 - SSIM) (include/splat2d.h "image losses"; one
     // context only) instead of the reference's squared error; the trace line gains ", loss %.6f"
     bool have_loss = false;
@@ -88,12 +100,19 @@ int usage()
                  "                     [--lr RATE] [--deterministic] [--reference-order] [--device D] [--gpus N [--exchange halo|dense] [--share-gpu]\n"
                  "                     [--stall-timeout-ms MS]] [--rebin-interval R] [--quiet]\n"
                  "                     [--relocate-every K [--relocate-window S] [--relocate-max-fraction F] [--relocate-min-weight W]]\n"
-                 "                     [--loss-weights M,L,D]\n"
+                 "                     [--loss-weights M,L,D] [--seed-init edges|uniform]\n"
+                 "                     [--reseed-every K [--reseed-window S] [--reseed-max-fraction F] [--reseed-min-weight W] [--reseed-scale X]]\n"
                  "  --loss-weights M,L,D: train with the sum over pixels and channels of M * d^2 / 2 + L * |d| + D * (1 - SSIM), e.g.\n"
                  "    0,0.8,0.2, instead of the reference's squared error (one GPU only); every line ends with the loss's mean.\n"
                  "  --relocate-every K: before iteration K, 2K, ... move the starved splats (summed T * alpha per pass below W) onto\n"
                  "    halves of the splats with the largest summed |dL/dpos|, from statistics of the S iterations before, at most\n"
                  "    F * splats at a time (one GPU only).  Defaults S = 10, F = 0.05, W = 0.5 are provisional: not measured yet.\n");
+    std::fprintf(stderr,
+                 "  --seed-init edges|uniform: after init(), draw every splat's position from the target's edge map (uniform: under\n"
+                 "    the full uniform share) and take its colour from the target there (one GPU only).\n"
+                 "  --reseed-every K: before iteration K, 2K, ... draw the starved splats (summed T * alpha per pass below W) again from\n"
+                 "    the squared error map at scale X, from statistics of the S iterations before, at most F * splats at a time (one\n"
+                 "    GPU only; not together with --relocate-every).  Defaults S = 10, F = 0.1, W = 5, X = 3 are provisional.\n");
     return 2;
 }
 
@@ -230,6 +249,12 @@ int main(int argc, char** argv)
         else if (a == "--relocate-window") o.relocate_window = std::atoi(next("--relocate-window"));
         else if (a == "--relocate-max-fraction") o.relocate_max_fraction = (float)std::atof(next("--relocate-max-fraction"));
         else if (a == "--relocate-min-weight") o.relocate_min_weight = (float)std::atof(next("--relocate-min-weight"));
+        else if (a == "--seed-init") o.seed_init = next("--seed-init");
+        else if (a == "--reseed-every") o.reseed_every = std::atoi(next("--reseed-every"));
+        else if (a == "--reseed-window") o.reseed_window = std::atoi(next("--reseed-window"));
+        else if (a == "--reseed-max-fraction") o.reseed_max_fraction = (float)std::atof(next("--reseed-max-fraction"));
+        else if (a == "--reseed-min-weight") o.reseed_min_weight = (float)std::atof(next("--reseed-min-weight"));
+        else if (a == "--reseed-scale") o.reseed_scale = (float)std::atof(next("--reseed-scale"));
         else return usage();
     }
     if (!o.convert_in.empty()) { // file conversion between .s2di / .ppm / .png; touches no GPU
@@ -269,6 +294,17 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "--relocate-every works on one context: the multi-device handle has no relocation\n");
         return 2;
     }
+    if (!o.seed_init.empty() && o.seed_init != "edges" && o.seed_init != "uniform") return usage();
+    if (o.reseed_every < 0 || o.reseed_window < 1 || !(o.reseed_max_fraction >= 0.0f) || !(o.reseed_min_weight >= 0.0f) || !(o.reseed_scale >= 0.0f))
+        return usage();
+    if ((o.reseed_every > 0 || !o.seed_init.empty()) && (o.gpus > 1 || std::getenv("S2D_TRAIN_FORCE_MULTI"))) {
+        std::fprintf(stderr, "--seed-init and --reseed-every work on one context: the multi-device handle has no placement\n");
+        return 2;
+    }
+    if (o.reseed_every > 0 && o.relocate_every > 0) {
+        std::fprintf(stderr, "--reseed-every and --relocate-every both own the statistics window: choose one\n");
+        return 2;
+    }
     Session S;
     CK(S.create(o, W, H));
     if (S.is_multi && o.stall_ms >= 0) CK(s2d_multi_set_stall_timeout(S.multi, o.stall_ms));
@@ -281,7 +317,21 @@ int main(int argc, char** argv)
         }
     }
     CK(S.set_target(imageRef)); // (empty: the synthetic target is generated on the device)
+    // init(), and with --seed-init every row drawn again from the target (the moments init() zeroed stay zero)
+    auto seed_all = [&]() -> int {
+        if (o.seed_init.empty()) return S2D_OK;
+        s2d_seed_config sc;
+        std::memset(&sc, 0, sizeof(sc));
+        sc.struct_size = sizeof(sc);
+        sc.source = S2D_SEED_TARGET_EDGES;
+        sc.floor = o.seed_init == "uniform" ? 4095u : 0u;
+        int32_t placed = 0;
+        const int rc = s2d_seed_splats(S.ctx, &sc, nullptr, o.n_splats, &placed);
+        if (rc == S2D_OK) std::fprintf(stderr, "seeded %d splats from the target (%s)\n", (int)placed, o.seed_init.c_str());
+        return rc;
+    };
     CK(S.init());               // init(); main.cpp:307
+    CK(seed_all());
 
     int iterations = 0; // main.cpp:278
     if (!o.load_ckpt.empty()) {
@@ -310,6 +360,7 @@ int main(int argc, char** argv)
     while (iterations < o.iters) { // while (pr::NextFrame() == false), main.cpp:334
         if (iterations == o.restart_at) { // ImGui::Button("Restart"), main.cpp:828-831: init() also sets
             CK(S.init());                 // iterations = 0 (main.cpp:281), so the trace restarts at "0 itr"
+            CK(seed_all());
             o.iters -= iterations;        // --iters is the number of frames to run in total
             iterations = 0;
             o.restart_at = -1;
@@ -320,12 +371,26 @@ int main(int argc, char** argv)
         if (o.restart_at > iterations && iterations + k > o.restart_at) k = o.restart_at - iterations;
         const bool opacity_now = o.optimize_opacity && iterations >= o.opacity_from; // bool optimizeOpacity, main.cpp:317
         uint32_t density = 0u;
-        if (o.relocate_every > 0) {
-            // iterations [mK - S, mK) gather the statistics; the relocation runs in front of iteration mK
-            const int K = o.relocate_every, S_ = o.relocate_window < K ? o.relocate_window : K;
+        if (o.relocate_every > 0 || o.reseed_every > 0) {
+            // iterations [mK - S, mK) gather the statistics; the relocation (or the reseeding) runs in front of iteration mK
+            const bool reseed = o.reseed_every > 0; // (never both: refused above)
+            const int K = reseed ? o.reseed_every : o.relocate_every, window = reseed ? o.reseed_window : o.relocate_window;
+            const int S_ = window < K ? window : K;
             int32_t passes = 0;
             if (iterations > 0 && iterations % K == 0) CK(s2d_density_get(S.ctx, nullptr, &passes));
-            if (passes > 0) { // (none: the run began here, from a checkpoint or a Restart)
+            if (passes > 0 && reseed) {
+                s2d_seed_config sc;
+                std::memset(&sc, 0, sizeof(sc));
+                sc.struct_size = sizeof(sc);
+                sc.source = S2D_SEED_ERROR;
+                sc.flags = S2D_SEED_SQUARED;
+                sc.seed = (uint32_t)(iterations / K);
+                sc.scale = o.reseed_scale;
+                int32_t moved = 0;
+                CK(s2d_forward(S.ctx)); // the error map is that of the current parameters
+                CK(s2d_reseed(S.ctx, &sc, (int32_t)(o.reseed_max_fraction * (float)o.n_splats), o.reseed_min_weight, &moved));
+                std::fprintf(stderr, "reseeded %d splats before iteration %d\n", (int)moved, iterations);
+            } else if (passes > 0) { // (none: the run began here, from a checkpoint or a Restart)
                 s2d_relocate_config rc;
                 rc.struct_size = sizeof(rc);
                 rc.max_moves = (int32_t)(o.relocate_max_fraction * (float)o.n_splats);

@@ -272,6 +272,61 @@ typedef struct s2d_relocate_config {
 } s2d_relocate_config;
 int s2d_relocate(s2d_ctx* ctx, const s2d_relocate_config* cfg, int32_t* moved);
 
+/* ---- importance-sampled placement (no counterpart in the reference, whose init() draws uniform positions and grey colours,
+ * main.cpp:280-305).  Rows are drawn from a per-pixel importance map and written with the target's
+ * colour there: a start that carries the picture (s2d_seed_splats over all rows), and a way to send unused splats to where
+ * the picture is still wrong (s2d_reseed with S2D_SEED_ERROR).  Everything below is exact: two calls, or a NumPy restatement,
+ * give the same bytes.  Pixels are numbered row-major, p = y * W + x; images are read as the context holds them (with
+ * S2D_CFG_FP16_IMAGES: the fp16 values converted to fp32); all float arithmetic is fp32, one operation at a time.
+ *
+ * Importance q(p), a uint32, from a measure s in [0, 1]:
+ *   S2D_SEED_TARGET_EDGES  y = imageRef; per channel e_c = |y_c(x+1,.) - y_c(x-1,.)| + |y_c(.,y+1) - y_c(.,y-1)|, indices
+ *                          clamped to the image; m = (e_r + e_g) + e_b; s = min(1, m * 0.5f)
+ *   S2D_SEED_ERROR         x = image0; d_c = |x_c - y_c|; m = (d_r + d_g) + d_b; s = min(1, m * (1.0f / 3.0f))
+ *   S2D_SEED_CALLER        importance_device: H * W floats in DEVICE memory; s = the value clamped to [0, 1], NaN -> 0
+ *   q0 = (uint32)(s * 4095.0f + 0.5f); with S2D_SEED_SQUARED q0 = (q0 * q0) >> 12; q = q0 + floor, floor in [0, 4095] being the
+ *   uniform share; total = sum of q in 64 bits.
+ * Draw of row i under `seed`, pcg3d as in init() (main.cpp:285-292), words mod 2^32:
+ *   (ax, ay, az) = pcg3d(i, 2 * seed, 0x5EED5EED), (bx, by, bz) = pcg3d(i, 2 * seed + 1, 0x5EED5EED);
+ *   u = floor(((ax * 2^32 + ay) * total) / 2^64); the pixel is the smallest p whose inclusive prefix sum of q exceeds u.
+ * The row: pos = (clamp((float)x + (float)bx / 2^32, 0, W - 1), clamp((float)y + (float)by / 2^32, 0, H - 1)) -- the rasteriser's
+ * pixel centre is x + 0.5; sx = sy = clamp(scale, 1, 1024), scale == 0 meaning sqrtf((float)W * (float)H / (float)n_splats);
+ * rot = pi * ((float)az / 2^32); color = imageRef's rgb at the pixel clamped to [0, 1]; opacity as given, 0 meaning 1; all 18
+ * Adam moments +0.  The draw depends on (i, seed) only: seeding a subset of rows writes exactly those rows of seeding all.
+ *
+ * S2D_E_INVALID, before any device work: a NULL config or wrong struct_size; an unknown source or flag; floor > 4095; a
+ * negative or non-finite scale; opacity outside {0} and (0, 1]; S2D_SEED_CALLER with a NULL importance_device, another source
+ * with a non-NULL one; ids out of range or repeated; a slab context (row_begin / row_end) or one with a held set
+ * (s2d_halo_commit).  S2D_E_STATE: no target; S2D_SEED_ERROR without s2d_forward on the current parameters.  The multi-device
+ * handle (s2d_multi) has no placement: out of scope here. */
+#define S2D_SEED_TARGET_EDGES 0u
+#define S2D_SEED_ERROR 1u
+#define S2D_SEED_CALLER 2u
+#define S2D_SEED_SQUARED 0x1u /* s2d_seed_config.flags */
+typedef struct s2d_seed_config {
+    uint32_t struct_size; /* = sizeof(s2d_seed_config) */
+    uint32_t source;      /* S2D_SEED_TARGET_EDGES, _ERROR, _CALLER */
+    uint32_t flags;       /* S2D_SEED_SQUARED */
+    uint32_t seed;
+    uint32_t floor;       /* 0 .. 4095 */
+    float scale;          /* 0 -> sqrt(W * H / n_splats); otherwise finite and > 0, clamped to [1, 1024] */
+    float opacity;        /* 0 -> 1; otherwise in (0, 1] */
+    const float* importance_device; /* S2D_SEED_CALLER only */
+} s2d_seed_config;
+/* The map alone: q of every pixel (q_host: H * W words, may be NULL) and its total (may be NULL).  scale, opacity and seed
+ * are checked but not used. */
+int s2d_importance(s2d_ctx* ctx, const s2d_seed_config* cfg, uint32_t* q_host, uint64_t* total);
+/* Writes the rows ids_host[0 .. count) (distinct; NULL: rows 0 .. count - 1, count <= n_splats) and zeroes their moments;
+ * projection and lists follow as after s2d_rows_scatter.  beta1t / beta2t / iterations, the gradient buffer and the density
+ * statistics are untouched: a caller who wants a fresh run calls s2d_init_splats first.  *placed (may be NULL): rows
+ * written -- count, or 0 when the map's total is 0 (nothing is written then). */
+int s2d_seed_splats(s2d_ctx* ctx, const s2d_seed_config* cfg, const int32_t* ids_host, int32_t count, int32_t* placed);
+/* s2d_seed_splats over the STARVED rows of the density statistics: weight / passes < min_weight, ordered by (weight, index),
+ * the first max_moves (rules 1-2 of csrc/s2d_density.h; no donors are involved).  Resets the statistics.  *moved (may be
+ * NULL): rows written.  Additionally S2D_E_INVALID wherever s2d_relocate refuses (max_moves < 0, a NaN min_weight,
+ * S2D_CFG_REFERENCE_ORDER) and S2D_E_STATE without a statistics pass since the last reset. */
+int s2d_reseed(s2d_ctx* ctx, const s2d_seed_config* cfg, int32_t max_moves, float min_weight, int32_t* moved);
+
 /* ---- image losses formed by the library (no counterpart in the reference, whose only loss is the squared error of
  * main.cpp:616).  With x = image0, y = imageRef, d = x - y, over all pixels p and channels c of .rgb:
  *
