@@ -1,0 +1,106 @@
+// s2d_api_loss.hip -- the loss passes of the C ABI (s2d_loss_*, s2d_step_loss; the kernels are s2d_loss.hip's).
+#include "s2d_ctx.h"
+
+#include <cmath>
+
+namespace {
+
+// Everything s2d_loss_* refuses for the configuration or the context, before any device work.
+int loss_refused(s2d_ctx* c, const s2d_loss_config* cfg)
+{
+    if (!cfg || cfg->struct_size != sizeof(s2d_loss_config)) return fail(c, S2D_E_INVALID, "s2d_loss_config: NULL or wrong struct_size");
+    const float w[3] = {cfg->w_mse, cfg->w_l1, cfg->w_dssim};
+    for (float v : w)
+        if (!(v >= 0.0f) || std::isinf(v)) return fail(c, S2D_E_INVALID, "loss weights must be finite and >= 0");
+    if (w[0] == 0.0f && w[1] == 0.0f && w[2] == 0.0f) return fail(c, S2D_E_INVALID, "all loss weights are zero");
+    if (int rc = whole_scene_refused(c, "the loss passes", true)) return rc; // (the window crosses slab rows)
+    if (c->cfg.flags & S2D_CFG_COUNT_PAIRS)
+        return fail(c, S2D_E_INVALID, "pair counting (S2D_CFG_COUNT_PAIRS) has no backward pass from an image gradient");
+    return S2D_OK;
+}
+
+// The loss kernels of the current frame: dL/d(image0) -> dimage, the totals -> `slot` of the loss ring, the squared error
+// also -> sqerr_out (the iteration's slot of the squared-error ring, or null).
+int queue_loss(s2d_ctx* c, const s2d_loss_config* cfg, float4* dimage, int slot, double* sqerr_out)
+{
+    if (!c->fresh.forward()) return fail(c, S2D_E_STATE, "the loss needs s2d_forward on the current parameters");
+    S2D_HIP(c, c->loss.ensure(c->g.W, c->g.H, c->stream));
+    if (cfg->w_dssim > 0.0f && !c->d_loss_maps) S2D_HIP(c, c->d_loss_maps.alloc((size_t)kLossMapPlanes * slab_pixels(c)));
+    LossArgs a;
+    a.image0 = c->d_image0; a.image_ref = c->d_ref; a.half_images = c->half_images; a.W = c->g.W; a.H = c->g.H;
+    a.w_mse = cfg->w_mse; a.w_l1 = cfg->w_l1; a.w_dssim = cfg->w_dssim;
+    a.maps = c->d_loss_maps; a.dimage = dimage; a.partial = c->loss.partial(); a.out3 = c->loss.slot(slot); a.sqerr_out = sqerr_out;
+    a.status = c->d_status; a.iteration = c->iterations;
+    S2D_HIP(c, launch_loss(a, c->stream));
+    c->loss.record(slot, cfg->w_mse, cfg->w_l1, cfg->w_dssim);
+    return S2D_OK;
+}
+
+} // namespace
+
+// s2d_backward for the loss: the loss kernels into the context's gradient image, the backward walk from it, and the
+// squared error of the iteration in the ring as the loss finalize left it (SqerrBy::LossPass).
+int queue_loss_backward(s2d_ctx* c, const s2d_loss_config* cfg, bool need_opacity_grad, bool density)
+{
+    if (!c->fresh.forward()) return fail(c, S2D_E_STATE, "the backward pass needs s2d_forward on the current parameters");
+    if (!c->d_loss_grad) S2D_HIP(c, c->d_loss_grad.alloc(slab_pixels(c)));
+    if (int rc = queue_loss(c, cfg, c->d_loss_grad, LossTrace::slot_of(c->iterations), c->trace.job(c->iterations).out)) return rc;
+    if (int rc = queue_backward(c, need_opacity_grad, c->d_loss_grad, density)) return rc;
+    return backward_queued(c, SqerrBy::LossPass);
+}
+
+// Sums of a loss pass (squared error on the 255 scale, |d|, 1 - s) -> the means and the total; a term with weight 0 was not formed.
+s2d_loss_terms loss_terms_of(const s2d_ctx* c, const double* sums, const float* w)
+{
+    const double n3 = mse_norm(c);
+    s2d_loss_terms t;
+    t.mse = sums[0] / (255.0 * 255.0) / n3;
+    t.l1 = w[1] > 0.0f ? sums[1] / n3 : std::nan("");
+    t.dssim = w[2] > 0.0f ? sums[2] / n3 : std::nan("");
+    t.total = 0.0;
+    if (w[0] > 0.0f) t.total += (double)w[0] * 0.5 * t.mse;
+    if (w[1] > 0.0f) t.total += (double)w[1] * t.l1;
+    if (w[2] > 0.0f) t.total += (double)w[2] * t.dssim;
+    return t;
+}
+
+extern "C" {
+
+int s2d_loss_image_grads_device(s2d_ctx* c, const s2d_loss_config* cfg, float* dimage_rows_device)
+{
+    if (!c || !dimage_rows_device) return S2D_E_INVALID;
+    if (int rc = loss_refused(c, cfg)) return rc;
+    if ((uintptr_t)dimage_rows_device & 15u) return fail(c, S2D_E_INVALID, "the image gradient must be 16-byte aligned");
+    if (int rc = use_device(c)) return rc;
+    return queue_loss(c, cfg, reinterpret_cast<float4*>(dimage_rows_device), LossTrace::kEvalSlot, nullptr);
+}
+
+int s2d_loss_backward(s2d_ctx* c, const s2d_loss_config* cfg, uint32_t flags)
+{
+    if (!c) return S2D_E_INVALID;
+    if (int rc = loss_refused(c, cfg)) return rc;
+    WalkFlags wf;
+    if (int rc = parse_walk_flags(c, flags, false, &wf)) return rc;
+    if (int rc = use_device(c)) return rc;
+    return queue_loss_backward(c, cfg, wf.need_opacity_grad, wf.density);
+}
+
+int s2d_loss_get(s2d_ctx* c, s2d_loss_terms* out)
+{
+    if (!c || !out) return S2D_E_INVALID;
+    if (c->loss.last_slot() < 0) return fail(c, S2D_E_STATE, "no loss pass has run yet");
+    if (int rc = use_device(c)) return rc;
+    double sums[3];
+    if (int rc = read_back(c, sums, c->loss.slot(c->loss.last_slot()), sizeof(sums))) return rc;
+    *out = loss_terms_of(c, sums, c->loss.last_weights());
+    return S2D_OK;
+}
+
+int s2d_step_loss(s2d_ctx* c, int32_t iters, uint32_t flags, const s2d_loss_config* cfg, double* loss_out, double* mse_out)
+{
+    if (!c || iters < 0) return S2D_E_INVALID;
+    if (int rc = loss_refused(c, cfg)) return rc;
+    return run_steps(c, iters, flags, cfg, loss_out, mse_out);
+}
+
+} // extern "C"

@@ -1,4 +1,4 @@
-// s2d_context.h -- three owners of context state whose rules used to be kept by hand across s2d_api.hip: the raster's
+// s2d_context.h -- three owners of context state whose rules used to be kept by hand across the API file (now s2d_sequence.hip): the raster's
 // scratch that is sized like the tile lists (PairScratch), the cut and the progress of a pass over index ranges
 // (IndexRanges), and the schedule and the stamps of list re-use (ListReuse).
 // Host code only (s2d_context.hip holds no kernel); each works on the context's stream, handed over once.

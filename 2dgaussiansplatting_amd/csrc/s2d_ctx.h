@@ -1,0 +1,123 @@
+// s2d_ctx.h -- the context behind the C ABI's handle, and the few helpers every unit that takes one needs.  Internal:
+// s2d_sequence.hip and the entry-point units s2d_api*.hip include it; nothing of it is exported.
+#pragma once
+
+#include "../../include/splat2d.h"
+
+#include <cstdarg>
+#include <cstdio>
+
+#include "s2d_device.h"
+#include "s2d_context.h"
+#include "s2d_lists.h"
+#include "s2d_loss.h"
+#include "s2d_owned.h"
+#include "s2d_seed.h"
+#include "s2d_sequence.h"
+#include "s2d_state.h"
+
+using namespace s2d;
+
+struct s2d_ctx {
+    s2d_config cfg{};
+    Geometry g{};
+    int n = 0;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    float lr = 0.05f;
+
+    SplatState state;            // parameters, optimiser state, the held set of slab ownership (s2d_state.h)
+    DevBuf<float> d_grads_own;   // gradients (AoS, the reference's layout)
+    float* d_grads = nullptr;    // buffer in use (own or bound)
+    // projection + binning
+    DevBuf<ProjRec> d_proj;
+    DevBuf<TileRect> d_rects;
+    DevBuf<uint32_t> d_counts;
+    DevBuf<uint32_t> d_offsets;
+    DevBuf<uint32_t> d_scan_temp;               // lent to the list builds and to s2d_halo_commit
+    TileLists lists;                            // the per-tile lists and everything only their builds use
+    PairScratch scratch;                        // the raster's hand-over and slots, sized like the lists (s2d_context.h)
+    IndexRanges ranges;                         // scenes beyond one set of lists: the cut, the carry, the progress of a pass
+    Freshness fresh;         // which of target, frames, projection and lists are current (s2d_sequence.h)
+    ListReuse reuse;         // when lists are rebuilt on schedule, and the stamped containment check (s2d_context.h)
+    // images
+    // image0 / imageRef (main.cpp:310, :254): the rows [row_begin, row_end) of this context's slab only -- a context
+    // never touches another row, so a 1/8 slab of 8192^2 holds 2 x 134 MB instead of 2 x 1.07 GB
+    DevBuf<uint8_t> d_image0;  // bytes: RGBA32F, or 4 x fp16 per pixel with S2D_CFG_FP16_IMAGES
+    DevBuf<uint8_t> d_ref;
+    bool half_images = false;
+    size_t pixel_bytes = sizeof(float4);
+    SqerrTrace trace;          // the tile errors of a backward pass and the ring of per-iteration sums (s2d_state.h)
+    DensityStats density;      // what the passes with S2D_BWD_DENSITY_STATS accumulated (s2d_state.h)
+    // loss passes (s2d_loss_*, s2d_loss.h): everything here is allocated by the first call that needs it
+    LossTrace loss;                // per-tile sums and the ring of per-iteration totals
+    DevBuf<float> d_loss_maps;     // [9][pixels]: the derivative maps between the two window passes (w_dssim > 0 only)
+    DevBuf<float4> d_loss_grad;    // dL/d(image0) of s2d_loss_backward / s2d_step_loss
+    SeedScratch seed;              // the importance map of s2d_importance / s2d_seed_splats / s2d_reseed (s2d_seed.h), on first use
+    DevBuf<DeviceStatus> d_status;
+    DevBuf<PairCounters> d_counters;
+    // pinned host mirrors
+    HostBuf<DeviceStatus> h_status;
+
+    // host-side state of the reference's main()
+    float beta1t = 1.0f, beta2t = 1.0f; // main.cpp:274-275
+    int iterations = 0;                 // main.cpp:278
+    float good_beta1t = 1.0f, good_beta2t = 1.0f; // the three above at the last point known to be finite
+    int good_iterations = 0;
+    char err[512] = {0};
+    S2D_LOCAL ~s2d_ctx() = default; // (named only to keep it out of the library's exports, like the owners it runs)
+};
+
+S2D_LOCAL inline int fail(s2d_ctx* c, int code, const char* fmt, ...)
+{
+    if (c) {
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(c->err, sizeof(c->err), fmt, ap);
+        va_end(ap);
+    }
+    return code;
+}
+
+#define S2D_HIP(c, expr)                                                                              \
+    do {                                                                                              \
+        hipError_t e_ = (expr);                                                                       \
+        if (e_ != hipSuccess)                                                                         \
+            return fail((c), S2D_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+
+// Declared behind a temporary device buffer that work queued on `stream` uses: the stream is idle before the buffer
+// is freed, on whichever way the function is left.
+struct S2D_LOCAL IdleAtExit {
+    hipStream_t stream;
+    ~IdleAtExit() { (void)hipStreamSynchronize(stream); }
+};
+
+S2D_LOCAL inline int use_device(s2d_ctx* c)
+{
+    S2D_HIP(c, hipSetDevice(c->device));
+    return S2D_OK;
+}
+
+// Device memory -> host memory behind everything queued on the context's stream.  Waits.
+S2D_LOCAL inline int read_back(s2d_ctx* c, void* dst, const void* src, size_t bytes)
+{
+    S2D_HIP(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    S2D_HIP(c, hipStreamSynchronize(c->stream));
+    return S2D_OK;
+}
+
+S2D_LOCAL inline double mse_norm(const s2d_ctx* c) { return (double)((long long)c->g.H * c->g.W * 3); }
+
+S2D_LOCAL inline size_t slab_pixels(const s2d_ctx* c) { return (size_t)c->g.W * (size_t)(c->g.row_end - c->g.row_begin); }
+
+// `who` (a call's name) works on the whole image and on every splat, and has_reference_order == false: has no
+// reference-order variant.  S2D_E_INVALID, before any device work.
+S2D_LOCAL inline int whole_scene_refused(s2d_ctx* c, const char* who, bool has_reference_order)
+{
+    if (c->g.row_begin != 0 || c->g.row_end != c->g.H) return fail(c, S2D_E_INVALID, "%s: the whole image is needed, this context owns a row slab", who);
+    if (c->state.held()) return fail(c, S2D_E_INVALID, "%s: every splat is needed, this context holds a subset (s2d_halo_commit)", who);
+    if (!has_reference_order && c->scratch.reference_order()) return fail(c, S2D_E_INVALID, "%s: not available with S2D_CFG_REFERENCE_ORDER", who);
+    return S2D_OK;
+}

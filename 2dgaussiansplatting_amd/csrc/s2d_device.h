@@ -219,7 +219,7 @@ enum class RasterPass {
     Forward,
     Backward,
     Fused,         // forward + backward walk of every tile in one launch (same results as the two launches above)
-    ForwardRange,  // index-range rendering (scenes beyond one set of lists; s2d_raster.hip "chunked", s2d_api.hip
+    ForwardRange,  // index-range rendering (scenes beyond one set of lists; s2d_raster.hip "chunked", s2d_sequence.hip
     BackwardRange, // chunked_forward / chunked_backward): the lists are those of ONE index range of the splats
 };
 // What a raster pass works on; a member left at its default is not used.

@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256) void grads_combine_kernel(float* __restrict__ 
     if (!first) grads[(size_t)i * 9 + k] = acc;
 }
 
-// Compact copies of the held splats' records (s2d_api.hip "compact held state"): out[h] = base[ids[h]] and back, for
+// Compact copies of the held splats' records (SplatState, s2d_state.h): out[h] = base[ids[h]] and back, for
 // h < *count (the launch covers n, the upper bound known to the host).
 __global__ __launch_bounds__(256) void compact_gather_kernel(const float* __restrict__ base, int w, const uint32_t* __restrict__ ids,
                                                              const uint32_t* __restrict__ count, float* __restrict__ out)

@@ -1292,7 +1292,7 @@ int s2d_multi_step(s2d_multi* m, int32_t iters, uint32_t flags, double* mse_out)
     run_command(m, CMD_STEP);
     if (int rc = first_failure(m, "s2d_multi_step")) {
         // Where the run stands now: a non-finite stop winds the counters of the rank that holds the splat back to the
-        // failing iteration (s2d_api.hip judge_status); with slab ownership the other ranks did not see it and are ahead.
+        // failing iteration (s2d_sequence.hip judge_status); with slab ownership the other ranks did not see it and are ahead.
         // The earliest count is the iteration at which the reference abort()ed; the state is for inspection only, and
         // s2d_multi_set_adam (which sets every rank's counters alike) comes before any further step.
         int32_t earliest = INT32_MAX;

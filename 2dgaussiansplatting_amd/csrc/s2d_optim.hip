@@ -261,7 +261,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ splats, f
     // (main.cpp:550), so neither may be skipped over.  Such a splat is INERT in this launch: nothing of it is read beyond
     // the gradients just looked at and its dormant byte, nothing is written, and its projection record and containment
     // check stand as they are -- PROVIDED the record was made from these very parameters and the check was passed, which is
-    // the context's proj_fresh (s2d_api.hip, invalidate()) handed over as proj_current, with one addition the host cannot
+    // the context's Freshness::projection() (s2d_sequence.h) handed over as proj_current, with one addition the host cannot
     // see without waiting: the check before this one must not be a failed one that no list rebuild has answered yet
     // (rebuilds and checks share one sequence, so that is the stamp before ours), or a splat that failed it and went inert
     // would not fail this one.  Where the record is not known current every splat runs the step, which changes nothing

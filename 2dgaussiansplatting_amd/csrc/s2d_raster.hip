@@ -276,7 +276,7 @@ __device__ __forceinline__ bool block_any_alive_exec(int4* flags, unsigned long 
 // tile's first list position; their number is returned.  Compacted positions never run ahead of list positions and
 // [beg, end) belongs to this tile alone.  A counting walk (COUNT, whose statistics are defined on staged entries) hands
 // over every staged entry at its list position instead, and the backward walk reads the list.
-// CHUNK (scenes whose (tile, splat) pairs do not fit one set of lists, s2d_api.hip chunked_forward / chunked_backward): the
+// CHUNK (scenes whose (tile, splat) pairs do not fit one set of lists, s2d_sequence.hip chunked_forward / chunked_backward): the
 // list holds the
 // splats of one INDEX RANGE only; the walk continues from the pixel's state after the ranges before it -- (crg, cb) and
 // *T_io on entry -- and leaves the state for the range after it.  The reference's loop is front to back in index order
@@ -961,7 +961,7 @@ __global__ __launch_bounds__(256, 8) void raster_fused_kernel(const uint32_t* __
 
 // ---------------------------------------------------------------------------------------------------
 // Index-range ("chunked") rendering, for scenes with more (tile, splat) pairs than one set of lists may hold
-// (s2d_api.hip chunked_forward / chunked_backward).  The splats are cut into consecutive index ranges; the lists of one range at a time are
+// (s2d_sequence.hip chunked_forward / chunked_backward).  The splats are cut into consecutive index ranges; the lists of one range at a time are
 // built and walked, front to back like the reference's loops (main.cpp:419, :552), and the per-pixel state is carried
 // from range to range in `state` (fp32 whatever the image format): (r, g, b, T).
 //   forward pass : raster_forward_chunk_kernel per range; each stores the state and image0 (.w = 1, main.cpp:543-546),
@@ -1143,7 +1143,7 @@ __global__ __launch_bounds__(256) void gather_stats_kernel(const uint32_t* __res
 // Sum of the per-tile squared errors in a fixed order (deterministic MSE trace), two stages in one launch:
 // kSqerrChunks blocks each reduce a contiguous chunk to partial[b] (sqerr_reduce, s2d_device.h); the block that finishes last (ticket counter)
 // adds the partials, again in a fixed order, and re-arms the counter.  scratch = kSqerrChunks doubles + one
-// 64-bit counter, zero before the first launch (s2d_api.hip allocates it behind tile_sqerr).
+// 64-bit counter, zero before the first launch (SqerrTrace, s2d_state.hip, allocates it behind tile_sqerr).
 __global__ __launch_bounds__(256) void sqerr_finalize_kernel(const double* __restrict__ tile_sqerr, int num_tiles,
                                                              double* __restrict__ out, double* scratch,
                                                              const DeviceStatus* __restrict__ status, int iteration)

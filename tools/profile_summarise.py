@@ -8,7 +8,7 @@
   working      : profile_summarise.py working <dir> <out.csv>
                  per kernel, from the kernel TRACE: all launches, and the launches that did work -- the first raster kernel of
                  an iteration is launched optimistically and returns at once (~22 us) when the tile lists turn out stale
-                 (csrc/s2d_api.hip queue_raster), so the stats file's AverageNs mixes in one void launch per list rebuild
+                 (csrc/s2d_sequence.hip queue_raster), so the stats file's AverageNs mixes in one void launch per list rebuild
   traffic      : profile_summarise.py traffic <pmc_traffic.csv> [<pmc_sq.csv>] <traffic.json>
                  HBM bytes per launch of the dominant raster kernel for bench.py's roofline.traffic, corrected as
                  /opt/skills/guides/MI355X_MICROARCH.md (HBM section) prescribes for gfx950, and tied to the kernel sources
