@@ -70,6 +70,14 @@ class _LossConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("w_mse", C.c_float), ("w_l1", C.c_float), ("w_dssim", C.c_float)]
 
 
+class _OptimConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("rate", C.c_float * 5), ("final_ratio", C.c_float * 5),
+                ("decay_iterations", C.c_int32)]
+
+
+OPTIM_GROUPS = ("pos", "scale", "rot", "color", "opacity")  # the groups of s2d_optim_config, in its order
+
+
 class _LossTerms(C.Structure):
     _fields_ = [("mse", C.c_double), ("l1", C.c_double), ("dssim", C.c_double), ("total", C.c_double)]
 
@@ -98,6 +106,7 @@ ABI_SYMBOLS = [
     "s2d_get_rebuild_count", "s2d_density_get", "s2d_density_get_device", "s2d_density_reset", "s2d_relocate",
     "s2d_importance", "s2d_seed_splats", "s2d_reseed",
     "s2d_loss_image_grads_device", "s2d_loss_backward", "s2d_loss_get", "s2d_step_loss",
+    "s2d_set_optim", "s2d_optim_rates_at", "s2d_set_frozen", "s2d_set_frozen_device",
     "s2d_last_error", "s2d_test_sincos", "s2d_test_sort_pairs", "s2d_test_exclusive_scan",
     "s2d_test_sort_tile_offsets", "s2d_debug_get_tile_lists",
     "s2d_halo_masks", "s2d_halo_commit", "s2d_rows_gather", "s2d_rows_scatter", "s2d_grads_combine",
@@ -266,6 +275,10 @@ def load_library(path=None):
     sig("s2d_loss_backward", [vp, C.POINTER(_LossConfig), u32])
     sig("s2d_loss_get", [vp, C.POINTER(_LossTerms)])
     sig("s2d_step_loss", [vp, i32, u32, C.POINTER(_LossConfig), vp, vp])
+    sig("s2d_set_optim", [vp, C.POINTER(_OptimConfig)])
+    sig("s2d_optim_rates_at", [vp, i32, vp])
+    sig("s2d_set_frozen", [vp, vp])
+    sig("s2d_set_frozen_device", [vp, vp])
     sig("s2d_step", [vp, i32, u32, vp])
     sig("s2d_get_mse", [vp, vp])
     sig("s2d_bind_grads_device", [vp, vp])
@@ -364,6 +377,7 @@ class Trainer:
                 self.L.s2d_destroy(h)
             self._h = None
             raise S2DError(rc, msg)
+        self.training_rate = float(training_rate) if training_rate > 0 else 0.05  # main.cpp:715
         self.optimize_opacity = False  # main.cpp:317
         self.lean_backward = False     # backward() may skip the opacity gradient while optimize_opacity is off
 
@@ -530,6 +544,48 @@ class Trainer:
         self._ck(self.L.s2d_step_loss(self._h, int(iters), flags, C.byref(cfg), _p(loss) if want else None,
                                       _p(mse) if want else None))
         return loss, mse
+
+    # -- optimiser controls (include/splat2d.h, "optimiser controls"): they act in the Adam launch of adam_step(), step() and
+    # step_loss() alike
+    _UNSET = object()
+
+    def set_optim(self, pos=_UNSET, scale=None, rot=None, color=None, opacity=None, final_ratio=None, decay_iterations=0):
+        """s2d_set_optim: a rate per parameter group (an omitted one: the context's training_rate), optionally decaying
+        log-linearly to rate * final_ratio[g] over decay_iterations (final_ratio: five numbers in the order pos, scale, rot,
+        color, opacity, 0 or 1 meaning no decay; or one number for all).  set_optim(None): back to the single training_rate."""
+        if pos is None:
+            self._ck(self.L.s2d_set_optim(self._h, None))
+            return
+        cfg = _OptimConfig()
+        cfg.struct_size = C.sizeof(_OptimConfig)
+        for g, r in enumerate((None if pos is Trainer._UNSET else pos, scale, rot, color, opacity)):
+            cfg.rate[g] = self.training_rate if r is None else float(r)
+        if final_ratio is not None:
+            ratios = [float(final_ratio)] * 5 if np.isscalar(final_ratio) else [float(x) for x in final_ratio]
+            assert len(ratios) == 5, ratios
+            for g in range(5):
+                cfg.final_ratio[g] = ratios[g]
+        cfg.decay_iterations = int(decay_iterations)
+        self._ck(self.L.s2d_set_optim(self._h, C.byref(cfg)))
+
+    def rates_at(self, iteration):
+        """-> five float32: the rates (pos, scale, rot, color, opacity) of the step taken while `iterations == iteration`."""
+        out = np.zeros(5, dtype=np.float32)
+        self._ck(self.L.s2d_optim_rates_at(self._h, int(iteration), _p(out)))
+        return out
+
+    def set_frozen(self, mask):
+        """s2d_set_frozen: n booleans / bytes, non-zero = the Adam step does not exist for that splat; None: no mask."""
+        if mask is None:
+            self._ck(self.L.s2d_set_frozen(self._h, None))
+            return
+        a = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        assert a.shape == (self.n,), a.shape
+        self._ck(self.L.s2d_set_frozen(self._h, _p(a)))
+
+    def set_frozen_device(self, ptr):
+        """The same from n bytes of device memory, copied on the context's stream (0 / None: no mask)."""
+        self._ck(self.L.s2d_set_frozen_device(self._h, C.c_void_p(ptr) if ptr else None))
 
     # -- density control (include/splat2d.h, "density control")
     def density(self):

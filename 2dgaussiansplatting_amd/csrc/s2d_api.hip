@@ -177,6 +177,7 @@ int s2d_init_splats(s2d_ctx* c)
     if (int rc = splats_replaced(c)) return rc;
     if (c->n > 0) S2D_HIP(c, hipMemsetAsync(c->d_grads, 0, (size_t)c->n * 9 * sizeof(float), c->stream));
     S2D_HIP(c, c->density.reset()); // (statistics of splats that no longer exist)
+    c->has_frozen = false;          // (a mask of splats that no longer exist; the rates of s2d_set_optim stay)
     c->beta1t = c->good_beta1t = 1.0f; // main.cpp:283-284
     c->beta2t = c->good_beta2t = 1.0f;
     c->iterations = c->good_iterations = 0; // main.cpp:281

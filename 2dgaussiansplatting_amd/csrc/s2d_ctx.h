@@ -11,6 +11,7 @@
 #include "s2d_context.h"
 #include "s2d_lists.h"
 #include "s2d_loss.h"
+#include "s2d_optim_rates.h"
 #include "s2d_owned.h"
 #include "s2d_seed.h"
 #include "s2d_sequence.h"
@@ -54,6 +55,12 @@ struct s2d_ctx {
     LossTrace loss;                // per-tile sums and the ring of per-iteration totals
     DevBuf<float> d_loss_maps;     // [9][pixels]: the derivative maps between the two window passes (w_dssim > 0 only)
     DevBuf<float4> d_loss_grad;    // dL/d(image0) of s2d_loss_backward / s2d_step_loss
+    // optimiser controls (s2d_set_optim / s2d_set_frozen, s2d_optim_rates.h): with either set the step launches the second
+    // instantiation of the Adam kernel (adam_args)
+    bool has_optim = false;
+    s2d_optim_config optim{};
+    bool has_frozen = false;
+    DevBuf<uint8_t> d_frozen;      // n bytes, non-zero = frozen; allocated by the first mask
     SeedScratch seed;              // the importance map of s2d_importance / s2d_seed_splats / s2d_reseed (s2d_seed.h), on first use
     DevBuf<DeviceStatus> d_status;
     DevBuf<PairCounters> d_counters;

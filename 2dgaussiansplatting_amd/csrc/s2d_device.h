@@ -397,7 +397,16 @@ hipError_t launch_init_splats(float* splats, float* adams, int n, int W, int H, 
 // a skipped splat's record and check stand; otherwise no splat is skipped.
 // compact (only with held_ids): splats / adams are the COMPACT arrays of the held splats, record h = splat held_ids[h]:
 // whole lines instead of one gathered record per splat; gradients, projection and `dormant` stay indexed by splat id.
+// controls (s2d_set_optim / s2d_set_frozen): the launch is the second instantiation of the kernel -- rates[k] is the rate of
+// scalar k of a splat instead of the one `lr`; frozen (n bytes indexed by splat id, or nullptr): a splat with a non-zero byte
+// is left as it is, parameters, moments and dormant byte, and only its gradient record is re-zeroed.
+struct AdamRates {
+    float r[9];
+};
 struct AdamArgs {
+    bool controls = false;
+    AdamRates rates{};
+    const uint8_t* frozen = nullptr;
     float* splats = nullptr;
     float* adams = nullptr;
     float* grads = nullptr;
@@ -415,7 +424,8 @@ struct AdamArgs {
     SqerrJob sq{};                         // the launch's first workgroups also add up the tile errors
     bool compact = false;
 };
-hipError_t launch_adam(const AdamArgs& a, hipStream_t stream);
+hipError_t launch_adam(const AdamArgs& a, hipStream_t stream); // (a.controls: hands over to launch_adam_controls)
+hipError_t launch_adam_controls(const AdamArgs& a, hipStream_t stream);
 // image_ref: rows [row_begin, row_end) of the W x H target
 hipError_t launch_synthetic_target(void* image_ref, bool half_images, int W, int H, int row_begin, int row_end, hipStream_t stream);
 // RGBA32F <-> 4 x fp16 (round to nearest even) for images that cross the boundary as floats

@@ -102,6 +102,13 @@ AdamArgs adam_args(s2d_ctx* c, uint32_t flags, bool project)
     a.proj_current = c->fresh.projection(); // (every event that replaces parameters clears it)
     a.check = project ? c->reuse.next_check(c->d_rects, c->d_status) : c->reuse.idle_check(c->d_rects, c->d_status);
     a.sq = c->trace.take_for_adam();
+    if (c->has_optim || c->has_frozen) { // the second instantiation: the nine per-field rates of this iteration, the mask
+        float group[kOptimGroups];
+        optim_rates_at(c->has_optim ? &c->optim : nullptr, c->lr, c->iterations, group);
+        a.controls = true;
+        for (int k = 0; k < 9; k++) a.rates.r[k] = group[kOptimGroupOf[k]];
+        a.frozen = c->has_frozen ? (const uint8_t*)c->d_frozen : nullptr;
+    }
     return a;
 }
 

@@ -77,6 +77,15 @@ struct Options {
     // context only) instead of the reference's squared error; the trace line gains ", loss %.6f"
     bool have_loss = false;
     s2d_loss_config loss{};
+    // Optimiser controls (include/splat2d.h "optimiser controls"; one context only).  All defaults leave the plain launch.
+    bool have_lr_groups = false;     // --lr-groups P,S,R,C,O: a rate per parameter group (pos, scale, rot, colour, opacity)
+    float lr_groups[5] = {0, 0, 0, 0, 0};
+    bool have_lr_ratio = false;      // --lr-final-ratio P,S,R,C,O: each rate decays log-linearly to rate * ratio (0 or 1: not) ...
+    float lr_ratio[5] = {0, 0, 0, 0, 0};
+    int lr_decay_iters = 0;          // --lr-decay-iters T: ... over the first T iterations (groups not named by --lr-groups: --lr)
+    float rebin_margin = 0.0f;       // --rebin-margin PX: s2d_config.rebin_margin (0: the library's 2 pixels)
+    bool freeze_unmoved = false;     // --freeze-unmoved: after each --reseed-every / --relocate-every event only the rows it wrote
+                                     // are trained until the next event (s2d_set_frozen)
     bool replicated = false;    // --exchange dense: replicated state + RCCL all-reduce of all gradients (default: slab ownership)
                                 // (RCCL takes one rank per GPU): a rehearsal of the N-rank host logic on a box with fewer GPUs
 };
@@ -102,6 +111,7 @@ int usage()
                  "                     [--relocate-every K [--relocate-window S] [--relocate-max-fraction F] [--relocate-min-weight W]]\n"
                  "                     [--loss-weights M,L,D] [--seed-init edges|uniform]\n"
                  "                     [--reseed-every K [--reseed-window S] [--reseed-max-fraction F] [--reseed-min-weight W] [--reseed-scale X]]\n"
+                 "                     [--lr-groups P,S,R,C,O [--lr-final-ratio P,S,R,C,O --lr-decay-iters T]] [--rebin-margin PX] [--freeze-unmoved]\n"
                  "  --loss-weights M,L,D: train with the sum over pixels and channels of M * d^2 / 2 + L * |d| + D * (1 - SSIM), e.g.\n"
                  "    0,0.8,0.2, instead of the reference's squared error (one GPU only); every line ends with the loss's mean.\n"
                  "  --relocate-every K: before iteration K, 2K, ... move the starved splats (summed T * alpha per pass below W) onto\n"
@@ -113,6 +123,11 @@ int usage()
                  "  --reseed-every K: before iteration K, 2K, ... draw the starved splats (summed T * alpha per pass below W) again from\n"
                  "    the squared error map at scale X, from statistics of the S iterations before, at most F * splats at a time (one\n"
                  "    GPU only; not together with --relocate-every).  Defaults S = 10, F = 0.1, W = 5, X = 3 are provisional.\n");
+    std::fprintf(stderr,
+                 "  --lr-groups P,S,R,C,O: Adam rates of position, scale, rotation, colour and opacity instead of the one --lr, e.g.\n"
+                 "    0.5,0.2,0.1,0.05,0.05; with --lr-final-ratio and --lr-decay-iters T each decays log-linearly to rate * ratio over\n"
+                 "    the first T iterations (one GPU only).  --rebin-margin PX: the margin of the re-used tile lists (default 2 pixels).\n"
+                 "  --freeze-unmoved: after each reseeding / relocation only the rows it wrote are trained until the next one.\n");
     return 2;
 }
 
@@ -133,6 +148,7 @@ struct Session {
         cfg.n_splats = o.n_splats; // int NSplat = 1024; main.cpp:271
         cfg.rebin_interval = o.rebin_interval;
         cfg.training_rate = o.lr;
+        cfg.rebin_margin = o.rebin_margin;
         if (o.deterministic) cfg.flags |= S2D_CFG_DETERMINISTIC;
         if (o.reference_order) cfg.flags |= S2D_CFG_REFERENCE_ORDER;
         is_multi = o.gpus > 1 || std::getenv("S2D_TRAIN_FORCE_MULTI"); // (the variable sends --gpus 1 through the handle)
@@ -245,6 +261,14 @@ int main(int argc, char** argv)
             if (std::sscanf(next("--loss-weights"), "%f,%f,%f", &o.loss.w_mse, &o.loss.w_l1, &o.loss.w_dssim) != 3) return usage();
             o.have_loss = true;
         }
+        else if (a == "--lr-groups" || a == "--lr-final-ratio") {
+            float* v = a == "--lr-groups" ? o.lr_groups : o.lr_ratio;
+            if (std::sscanf(next(a.c_str()), "%f,%f,%f,%f,%f", &v[0], &v[1], &v[2], &v[3], &v[4]) != 5) return usage();
+            (a == "--lr-groups" ? o.have_lr_groups : o.have_lr_ratio) = true;
+        }
+        else if (a == "--lr-decay-iters") o.lr_decay_iters = std::atoi(next("--lr-decay-iters"));
+        else if (a == "--rebin-margin") o.rebin_margin = (float)std::atof(next("--rebin-margin"));
+        else if (a == "--freeze-unmoved") o.freeze_unmoved = true;
         else if (a == "--relocate-every") o.relocate_every = std::atoi(next("--relocate-every"));
         else if (a == "--relocate-window") o.relocate_window = std::atoi(next("--relocate-window"));
         else if (a == "--relocate-max-fraction") o.relocate_max_fraction = (float)std::atof(next("--relocate-max-fraction"));
@@ -305,8 +329,54 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "--reseed-every and --relocate-every both own the statistics window: choose one\n");
         return 2;
     }
+    const bool have_optim = o.have_lr_groups || o.have_lr_ratio || o.lr_decay_iters != 0;
+    if (!(o.rebin_margin >= 0.0f) || o.lr_decay_iters < 0) return usage();
+    if ((have_optim || o.freeze_unmoved) && (o.gpus > 1 || std::getenv("S2D_TRAIN_FORCE_MULTI"))) {
+        std::fprintf(stderr, "--lr-groups, --lr-final-ratio, --lr-decay-iters and --freeze-unmoved work on one context: the multi-device handle has no optimiser controls\n");
+        return 2;
+    }
+    if (o.freeze_unmoved && o.reseed_every == 0 && o.relocate_every == 0) {
+        std::fprintf(stderr, "--freeze-unmoved needs --reseed-every or --relocate-every: it freezes what their events did not write\n");
+        return 2;
+    }
     Session S;
     CK(S.create(o, W, H));
+    if (have_optim) { // (groups without a rate of their own: the one --lr)
+        s2d_optim_config oc;
+        std::memset(&oc, 0, sizeof(oc));
+        oc.struct_size = sizeof(oc);
+        for (int g = 0; g < 5; g++) {
+            oc.rate[g] = o.have_lr_groups ? o.lr_groups[g] : (o.lr > 0.0f ? o.lr : 0.05f);
+            oc.final_ratio[g] = o.have_lr_ratio ? o.lr_ratio[g] : 0.0f;
+        }
+        oc.decay_iterations = o.lr_decay_iters;
+        CK(s2d_set_optim(S.ctx, &oc));
+    }
+    // --freeze-unmoved: the state in front of an event, to tell afterwards which rows it wrote
+    std::vector<s2d_splat> before_sp;
+    std::vector<s2d_splat_adam> before_ad;
+    auto remember_rows = [&]() -> int {
+        if (!o.freeze_unmoved) return S2D_OK;
+        before_sp.resize((size_t)o.n_splats);
+        before_ad.resize((size_t)o.n_splats);
+        if (int rc = s2d_get_splats(S.ctx, before_sp.data())) return rc;
+        return s2d_get_adam(S.ctx, before_ad.data(), nullptr, nullptr, nullptr);
+    };
+    auto freeze_unwritten_rows = [&]() -> int {
+        if (!o.freeze_unmoved) return S2D_OK;
+        std::vector<s2d_splat> sp((size_t)o.n_splats);
+        std::vector<s2d_splat_adam> ad((size_t)o.n_splats);
+        if (int rc = s2d_get_splats(S.ctx, sp.data())) return rc;
+        if (int rc = s2d_get_adam(S.ctx, ad.data(), nullptr, nullptr, nullptr)) return rc;
+        std::vector<uint8_t> frozen((size_t)o.n_splats);
+        int trained = 0;
+        for (size_t i = 0; i < frozen.size(); i++) {
+            frozen[i] = std::memcmp(&sp[i], &before_sp[i], sizeof(s2d_splat)) == 0 && std::memcmp(&ad[i], &before_ad[i], sizeof(s2d_splat_adam)) == 0;
+            trained += frozen[i] ? 0 : 1;
+        }
+        std::fprintf(stderr, "froze %d splats, %d stay trained\n", o.n_splats - trained, trained);
+        return s2d_set_frozen(S.ctx, frozen.data());
+    };
     if (S.is_multi && o.stall_ms >= 0) CK(s2d_multi_set_stall_timeout(S.multi, o.stall_ms));
     if (S.is_multi) { // which GPU runs which rows (stderr: stdout is the reference's trace)
         for (int r = 0; r < s2d_multi_device_count(S.multi); r++) {
@@ -388,8 +458,10 @@ int main(int argc, char** argv)
                 sc.scale = o.reseed_scale;
                 int32_t moved = 0;
                 CK(s2d_forward(S.ctx)); // the error map is that of the current parameters
+                CK(remember_rows());
                 CK(s2d_reseed(S.ctx, &sc, (int32_t)(o.reseed_max_fraction * (float)o.n_splats), o.reseed_min_weight, &moved));
                 std::fprintf(stderr, "reseeded %d splats before iteration %d\n", (int)moved, iterations);
+                CK(freeze_unwritten_rows());
             } else if (passes > 0) { // (none: the run began here, from a checkpoint or a Restart)
                 s2d_relocate_config rc;
                 rc.struct_size = sizeof(rc);
@@ -397,8 +469,10 @@ int main(int argc, char** argv)
                 rc.min_weight = o.relocate_min_weight;
                 rc.shrink = 0.0f;
                 int32_t moved = 0;
+                CK(remember_rows());
                 CK(s2d_relocate(S.ctx, &rc, &moved));
                 std::fprintf(stderr, "relocated %d splats before iteration %d\n", (int)moved, iterations);
+                CK(freeze_unwritten_rows());
             }
             const int next_reloc = (iterations / K + 1) * K, window_begin = next_reloc - S_;
             if (iterations >= window_begin) density = S2D_STEP_DENSITY_STATS;

@@ -376,6 +376,42 @@ int s2d_step_loss(s2d_ctx* ctx, int32_t iters, uint32_t flags, const s2d_loss_co
 /* Adam + constraints + finite guard, main.cpp:714-785, on the current gradient buffer; then iterations++ (809). */
 int s2d_adam_step(s2d_ctx* ctx, uint32_t flags);
 
+/* ---- optimiser controls (no counterpart in the reference, whose one trainingRate, main.cpp:715, drives all nine scalars of
+ * a splat).  They act in the Adam launch, so s2d_adam_step, s2d_step (fused or with
+ * S2D_STEP_DENSITY_STATS) and s2d_step_loss all follow them.
+ *
+ * Rates per parameter GROUP, with an optional log-linear decay.  The rate of group g for the step taken while the context's
+ * `iterations` counter is t (the counter s2d_set_adam restores, so a resumed run continues its schedule):
+ *   T == 0 or final_ratio[g] == 1 (0 means 1):  rate[g], exactly;
+ *   otherwise:  (float)((double)rate[g] * pow((double)final_ratio[g], (double)min(t, T) / T)) -- constant from T on.
+ * Every scalar of the group is then Adam::optimize (main.cpp:144-156) at that alpha, bit for bit.  The opacity rate matters
+ * only under S2D_STEP_OPTIMIZE_OPACITY, as ever.
+ *
+ * FROZEN splats: the Adam step does not exist for them.  The 9 parameters, the 18 moments and the finite guard leave a frozen
+ * splat alone (byte for byte); its gradient record is re-zeroed like everyone's (main.cpp:550).  The raster passes, the density
+ * statistics, s2d_relocate and s2d_reseed do not know about the mask.  s2d_init_splats clears the mask (and keeps the rates);
+ * s2d_set_splats, s2d_set_adam and the row calls keep both.  Setting either invalidates nothing.
+ *
+ * While a configuration or a mask is set -- even one that equals the defaults -- the step runs a second instantiation of the
+ * Adam kernel; s2d_set_optim(NULL) with no mask returns to the plain one.
+ * S2D_E_INVALID, before any device work, for all four calls: a slab context (row_begin / row_end) or one with a held set
+ * (s2d_halo_commit; and s2d_halo_commit with masks refuses a context that has a configuration or a mask) -- the hold margins
+ * of slab ownership are derived from the one training_rate; for s2d_set_optim also a wrong struct_size, a rate that is <= 0 or
+ * not finite, a final_ratio that is negative or not finite, decay_iterations < 0; for s2d_optim_rates_at a negative iteration.
+ * The multi-device handle (s2d_multi) has no such controls: out of scope here. */
+/* groups: 0 pos (pos.x, pos.y), 1 scale (sx, sy), 2 rot, 3 colour (r, g, b), 4 opacity */
+typedef struct s2d_optim_config {
+    uint32_t struct_size;     /* = sizeof(s2d_optim_config) */
+    float rate[5];            /* each finite and > 0 */
+    float final_ratio[5];     /* 0 -> 1 (no decay); otherwise finite and > 0 */
+    int32_t decay_iterations; /* T >= 0; 0 -> no decay, the ratios are not looked at beyond validation */
+} s2d_optim_config;
+int s2d_set_optim(s2d_ctx* ctx, const s2d_optim_config* cfg);        /* NULL: back to the single training_rate */
+/* What the step taken at `iterations == iteration` uses (without a configuration: training_rate five times). */
+int s2d_optim_rates_at(s2d_ctx* ctx, int32_t iteration, float rates[5]);
+int s2d_set_frozen(s2d_ctx* ctx, const uint8_t* frozen_host);        /* n_splats bytes, non-zero = frozen; NULL: none */
+int s2d_set_frozen_device(s2d_ctx* ctx, const uint8_t* frozen_device); /* copied on the context's stream; NULL: none */
+
 /* `iters` whole iterations (main.cpp:414-809): forward, backward, Adam, MSE.  mse_out (may be NULL) receives
  * iters doubles: the value the reference prints for each iteration (main.cpp:796-807).  For a slab context the
  * values are this slab's sum of squared errors divided by (H*W*3), i.e. partial MSEs that add up over slabs.
