@@ -66,6 +66,10 @@ class _SeedConfig(C.Structure):
                 ("floor", C.c_uint32), ("scale", C.c_float), ("opacity", C.c_float), ("importance_device", C.c_void_p)]
 
 
+class _PruneConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_weight", C.c_float), ("min_opacity", C.c_float)]
+
+
 class _LossConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("w_mse", C.c_float), ("w_l1", C.c_float), ("w_dssim", C.c_float)]
 
@@ -107,6 +111,7 @@ ABI_SYMBOLS = [
     "s2d_importance", "s2d_seed_splats", "s2d_reseed",
     "s2d_loss_image_grads_device", "s2d_loss_backward", "s2d_loss_get", "s2d_step_loss",
     "s2d_set_optim", "s2d_optim_rates_at", "s2d_set_frozen", "s2d_set_frozen_device",
+    "s2d_set_alive", "s2d_set_alive_device", "s2d_get_alive", "s2d_prune", "s2d_grow",
     "s2d_last_error", "s2d_test_sincos", "s2d_test_sort_pairs", "s2d_test_exclusive_scan",
     "s2d_test_sort_tile_offsets", "s2d_debug_get_tile_lists",
     "s2d_halo_masks", "s2d_halo_commit", "s2d_rows_gather", "s2d_rows_scatter", "s2d_grads_combine",
@@ -279,6 +284,11 @@ def load_library(path=None):
     sig("s2d_optim_rates_at", [vp, i32, vp])
     sig("s2d_set_frozen", [vp, vp])
     sig("s2d_set_frozen_device", [vp, vp])
+    sig("s2d_set_alive", [vp, vp])
+    sig("s2d_set_alive_device", [vp, vp])
+    sig("s2d_get_alive", [vp, vp, vp])
+    sig("s2d_prune", [vp, C.POINTER(_PruneConfig), vp])
+    sig("s2d_grow", [vp, C.POINTER(_SeedConfig), vp, i32, vp])
     sig("s2d_step", [vp, i32, u32, vp])
     sig("s2d_get_mse", [vp, vp])
     sig("s2d_bind_grads_device", [vp, vp])
@@ -586,6 +596,48 @@ class Trainer:
     def set_frozen_device(self, ptr):
         """The same from n bytes of device memory, copied on the context's stream (0 / None: no mask)."""
         self._ck(self.L.s2d_set_frozen_device(self._h, C.c_void_p(ptr) if ptr else None))
+
+    # -- the alive set (include/splat2d.h, "the alive set")
+    def set_alive(self, mask):
+        """s2d_set_alive: n booleans / bytes, non-zero = the row takes part; None: every row again.  A dead row is not drawn,
+        listed or stepped and keeps its index (its place in the blend order)."""
+        if mask is None:
+            self._ck(self.L.s2d_set_alive(self._h, None))
+            return
+        a = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        assert a.shape == (self.n,), a.shape
+        self._ck(self.L.s2d_set_alive(self._h, _p(a)))
+
+    def set_alive_device(self, ptr):
+        """The same from n bytes of device memory, copied on the context's stream (0 / None: every row again)."""
+        self._ck(self.L.s2d_set_alive_device(self._h, C.c_void_p(ptr) if ptr else None))
+
+    def alive(self):
+        """-> (n booleans, the number of alive rows); all True without a set."""
+        a = np.zeros(self.n, dtype=np.uint8)
+        count = C.c_int32()
+        self._ck(self.L.s2d_get_alive(self._h, _p(a), C.byref(count)))
+        return a != 0, count.value
+
+    def prune(self, min_weight=0.0, min_opacity=0.0):
+        """s2d_prune: alive rows with weight per statistics pass < min_weight or opacity < min_opacity die (a threshold of 0
+        is off); returns their number.  With min_weight the statistics are reset."""
+        cfg = _PruneConfig(C.sizeof(_PruneConfig), float(min_weight), float(min_opacity))
+        pruned = C.c_int32()
+        self._ck(self.L.s2d_prune(self._h, C.byref(cfg), C.byref(pruned)))
+        return pruned.value
+
+    def grow(self, count, ids=None, source="edges", squared=False, floor=0, scale=0.0, opacity=0.0, seed=0, importance_ptr=None):
+        """s2d_grow: the rows `ids` (each dead), or with None the `count` dead rows of lowest index, are seeded as seed()
+        seeds them and come alive; returns the number of rows written (0 for an all-zero map or without a dead row)."""
+        cfg = self._seed_config(source, squared, floor, scale, opacity, seed, importance_ptr)
+        grown = C.c_int32()
+        if ids is None:
+            self._ck(self.L.s2d_grow(self._h, C.byref(cfg), None, min(int(count), 2**31 - 1), C.byref(grown)))
+        else:
+            a = np.ascontiguousarray(ids, dtype=np.int32)
+            self._ck(self.L.s2d_grow(self._h, C.byref(cfg), _p(a), len(a), C.byref(grown)))
+        return grown.value
 
     # -- density control (include/splat2d.h, "density control")
     def density(self):

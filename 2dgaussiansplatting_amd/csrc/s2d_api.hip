@@ -172,6 +172,10 @@ int s2d_init_splats(s2d_ctx* c)
     if (!c) return S2D_E_INVALID;
     if (int rc = use_device(c)) return rc;
     S2D_HIP(c, c->trace.settle()); // (the iteration count is about to restart)
+    if (c->state.kind() == SplatState::Subset::Alive) { // (a set of splats that no longer exist, like the frozen mask)
+        S2D_HIP(c, c->state.clear_alive());
+        alive_set_changed(c);
+    }
     const SplatState::Arrays all = c->state.discard_all(); // every record is new
     S2D_HIP(c, launch_init_splats(all.splats, all.adams, c->n, c->g.W, c->g.H, c->stream));
     if (int rc = splats_replaced(c)) return rc;

@@ -61,10 +61,10 @@ int density_get(s2d_ctx* c, void* out, bool to_host, int32_t* passes)
     return S2D_OK;
 }
 
-// ---- importance-sampled placement (s2d_seed.h) -----------------------------------------------------------------------
-// Everything s2d_importance / s2d_seed_splats / s2d_reseed (`who`) refuse for the configuration or the context, before
-// any device work (S2D_E_INVALID), then what they refuse for the order of calls (S2D_E_STATE).
-int seed_refused(s2d_ctx* c, const s2d_seed_config* cfg, const char* who, bool has_reference_order = true)
+} // namespace
+
+// ---- importance-sampled placement (s2d_seed.h; declared in s2d_ctx.h) --------------------------------------------------
+int seed_refused(s2d_ctx* c, const s2d_seed_config* cfg, const char* who, bool has_reference_order)
 {
     if (!cfg || cfg->struct_size != sizeof(s2d_seed_config)) return fail(c, S2D_E_INVALID, "s2d_seed_config: NULL or wrong struct_size");
     if (cfg->source > S2D_SEED_CALLER) return fail(c, S2D_E_INVALID, "s2d_seed_config: unknown source %u", cfg->source);
@@ -85,7 +85,6 @@ int seed_state_refused(s2d_ctx* c, const s2d_seed_config* cfg)
     return S2D_OK;
 }
 
-// The map of the current images (queued) and its total (waits).
 int seed_map(s2d_ctx* c, const s2d_seed_config* cfg, SeedMap* map, uint64_t* total)
 {
     S2D_HIP(c, c->seed.ensure(slab_pixels(c), map));
@@ -96,6 +95,31 @@ int seed_map(s2d_ctx* c, const s2d_seed_config* cfg, SeedMap* map, uint64_t* tot
     S2D_HIP(c, launch_seed_map(a, c->stream));
     return read_back(c, total, map->share_prefix + (map->shares - 1), sizeof(uint64_t));
 }
+
+int seed_place(s2d_ctx* c, const s2d_seed_config* cfg, const SeedMap& map, uint64_t total, const int32_t* ids_device, int count)
+{
+    SplatState::Arrays now;
+    S2D_HIP(c, c->state.current(&now));
+    SeedPlaceArgs p;
+    p.map = map; p.total = total; p.ids = ids_device; p.count = count; p.seed = cfg->seed;
+    p.image_ref = c->d_ref; p.half_images = c->half_images; p.W = c->g.W; p.H = c->g.H;
+    p.scale = seed_scale(cfg->scale, c->g.W, c->g.H, c->n); p.opacity = seed_opacity(cfg->opacity);
+    p.splats = now.splats; p.adams = now.adams;
+    S2D_HIP(c, launch_seed_place(p, c->stream));
+    return rows_replaced(c, S2D_ROWS_SPLATS);
+}
+
+int mask_dead_stats(s2d_ctx* c, float* stats)
+{
+    if (c->state.kind() != SplatState::Subset::Alive || c->n == 0) return S2D_OK;
+    std::vector<uint8_t> alive((size_t)c->n);
+    if (int rc = read_back(c, alive.data(), c->state.held(), alive.size())) return rc;
+    for (size_t i = 0; i < alive.size(); i++)
+        if (!alive[i]) stats[3 * i] = stats[3 * i + 1] = stats[3 * i + 2] = std::nanf("");
+    return S2D_OK;
+}
+
+namespace {
 
 // The rows `ids` (distinct, in range; null: 0 .. count - 1) drawn from the map of the current images and written
 // (rows_replaced).  *placed: count, or 0 for a map whose total is 0.
@@ -109,15 +133,7 @@ int seed_rows(s2d_ctx* c, const s2d_seed_config* cfg, const int32_t* ids, int co
     StreamTemps tmp(c->stream);
     const int32_t* d_ids = nullptr;
     if (ids) S2D_HIP(c, tmp.upload(ids, (size_t)count, &d_ids));
-    SplatState::Arrays now;
-    S2D_HIP(c, c->state.current(&now));
-    SeedPlaceArgs p;
-    p.map = map; p.total = total; p.ids = d_ids; p.count = count; p.seed = cfg->seed;
-    p.image_ref = c->d_ref; p.half_images = c->half_images; p.W = c->g.W; p.H = c->g.H;
-    p.scale = seed_scale(cfg->scale, c->g.W, c->g.H, c->n); p.opacity = seed_opacity(cfg->opacity);
-    p.splats = now.splats; p.adams = now.adams;
-    S2D_HIP(c, launch_seed_place(p, c->stream));
-    if (int rc = rows_replaced(c, S2D_ROWS_SPLATS)) return rc;
+    if (int rc = seed_place(c, cfg, map, total, d_ids, count)) return rc;
     *placed = count;
     return S2D_OK;
 }
@@ -166,6 +182,7 @@ int s2d_relocate(s2d_ctx* c, const s2d_relocate_config* cfg, int32_t* moved)
         S2D_HIP(c, hipMemcpyAsync(adams.data(), now.adams, n * 18 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     }
     S2D_HIP(c, hipStreamSynchronize(c->stream)); // (one wait for the three arrays)
+    if (int rc = mask_dead_stats(c, stats.data())) return rc; // (dead rows: neither starved nor donors)
     const int moves = density_plan(c->n, stats.data(), passes, cfg->max_moves, cfg->min_weight, shrink, c->g.W, c->g.H, splats.data(),
                                    adams.data(), ids.data());
     if (moves > 0) { // the changed rows, through the row calls' scatter
@@ -239,6 +256,7 @@ int s2d_reseed(s2d_ctx* c, const s2d_seed_config* cfg, int32_t max_moves, float 
     std::vector<float> stats((size_t)c->n * 3);
     if (int rc = density_to_host(c, "s2d_reseed", stats.data(), &passes)) return rc;
     S2D_HIP(c, hipStreamSynchronize(c->stream));
+    if (int rc = mask_dead_stats(c, stats.data())) return rc; // (dead rows are not starved)
     std::vector<int32_t> ids(std::min<size_t>((size_t)max_moves, (size_t)c->n));
     const int starved = density_starved(c->n, stats.data(), passes, max_moves, min_weight, ids.data());
     int32_t done = 0;

@@ -9,6 +9,8 @@ int s2d_halo_masks(s2d_ctx* c, int32_t world, const int32_t* row_bounds, float m
     if (!c || !row_bounds || !masks_device || world < 1 || world > 32 || !(margin_rows >= 0.0f)) return S2D_E_INVALID;
     for (int q = 0; q < world; q++)
         if (row_bounds[q] > row_bounds[q + 1]) return S2D_E_INVALID;
+    if (c->state.kind() == SplatState::Subset::Alive) // (its flags are no hold set: the two kinds of subset exclude each other)
+        return fail(c, S2D_E_INVALID, "s2d_halo_masks: this context has an alive set (s2d_set_alive(NULL) first)");
     if (int rc = use_device(c)) return rc;
     SplatState::Arrays now;
     S2D_HIP(c, c->state.current(&now));
@@ -23,6 +25,10 @@ int s2d_halo_commit(s2d_ctx* c, const uint32_t* masks_device, int32_t rank, int3
         return fail(c, S2D_E_INVALID, "reference order (S2D_CFG_REFERENCE_ORDER) has no slab ownership: the chains run over all splats");
     if (masks_device && (c->has_optim || c->has_frozen))
         return fail(c, S2D_E_INVALID, "slab ownership derives its hold margins from the one training_rate: clear s2d_set_optim / s2d_set_frozen first");
+    if (c->state.kind() == SplatState::Subset::Alive) { // the two kinds of subset exclude each other
+        if (masks_device) return fail(c, S2D_E_INVALID, "s2d_halo_commit: this context has an alive set (s2d_set_alive(NULL) first)");
+        return S2D_OK; // (it holds every row it has already)
+    }
     if (int rc = use_device(c)) return rc;
     const bool had = c->state.held() != nullptr;
     S2D_HIP(c, c->state.commit(masks_device, rank, c->d_scan_temp));

@@ -28,7 +28,7 @@ struct s2d_ctx {
     bool own_stream = false;
     float lr = 0.05f;
 
-    SplatState state;            // parameters, optimiser state, the held set of slab ownership (s2d_state.h)
+    SplatState state;            // parameters, optimiser state, the held set of slab ownership or the alive set (s2d_state.h)
     DevBuf<float> d_grads_own;   // gradients (AoS, the reference's layout)
     float* d_grads = nullptr;    // buffer in use (own or bound)
     // projection + binning
@@ -124,7 +124,22 @@ S2D_LOCAL inline size_t slab_pixels(const s2d_ctx* c) { return (size_t)c->g.W * 
 S2D_LOCAL inline int whole_scene_refused(s2d_ctx* c, const char* who, bool has_reference_order)
 {
     if (c->g.row_begin != 0 || c->g.row_end != c->g.H) return fail(c, S2D_E_INVALID, "%s: the whole image is needed, this context owns a row slab", who);
-    if (c->state.held()) return fail(c, S2D_E_INVALID, "%s: every splat is needed, this context holds a subset (s2d_halo_commit)", who);
+    if (c->state.kind() == SplatState::Subset::Slab) // (an alive set is no obstacle: a dead row does not exist for the passes)
+        return fail(c, S2D_E_INVALID, "%s: every splat is needed, this context holds a subset (s2d_halo_commit)", who);
     if (!has_reference_order && c->scratch.reference_order()) return fail(c, S2D_E_INVALID, "%s: not available with S2D_CFG_REFERENCE_ORDER", who);
     return S2D_OK;
 }
+
+// ---- what s2d_api_placement.hip shares with s2d_api_alive.hip (s2d_grow seeds the rows it brings to life) ---------------
+// Everything the seeding calls (`who`) refuse for the configuration or the context, before any device work (S2D_E_INVALID),
+// then what they refuse for the order of calls (S2D_E_STATE).
+S2D_LOCAL int seed_refused(s2d_ctx* c, const s2d_seed_config* cfg, const char* who, bool has_reference_order = true);
+S2D_LOCAL int seed_state_refused(s2d_ctx* c, const s2d_seed_config* cfg);
+// The map of the current images (queued) and its total (waits).
+S2D_LOCAL int seed_map(s2d_ctx* c, const s2d_seed_config* cfg, SeedMap* map, uint64_t* total);
+// The rows ids_device[0 .. count) (distinct, in range; null: 0 .. count - 1) drawn from `map` (total > 0) and written (queued;
+// rows_replaced).
+S2D_LOCAL int seed_place(s2d_ctx* c, const s2d_seed_config* cfg, const SeedMap& map, uint64_t total, const int32_t* ids_device, int count);
+// The host copy of the density statistics (n x 3) with the rows that are not alive set to NaN, which makes a row neither
+// starved nor a donor for the planners of s2d_density.h.  Waits; nothing to do without an alive set.
+S2D_LOCAL int mask_dead_stats(s2d_ctx* c, float* stats);

@@ -166,6 +166,14 @@ hipError_t launch_halo_commit(const uint32_t* masks, int n, int rank, uint8_t* h
     return hipGetLastError();
 }
 
+// (declared in s2d_alive.h: the alive set builds its list with the same kernel)
+hipError_t launch_held_ids(const uint8_t* held, const uint32_t* pos, int n, uint32_t* ids, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(held_ids_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, held, pos, n, ids);
+    return hipGetLastError();
+}
+
 hipError_t launch_rows_gather(const float* base, int w, const int* ids, int count, int n, float* out, hipStream_t stream)
 {
     if (count <= 0) return hipSuccess;

@@ -81,3 +81,4 @@ S2D_LOCAL int splats_replaced_from_device(s2d_ctx* c);      // s2d_set_splats_de
 S2D_LOCAL int rows_replaced(s2d_ctx* c, int32_t what);      // S2D_ROWS_*: s2d_rows_scatter; s2d_relocate and the seeding write S2D_ROWS_SPLATS (with their moments)
 S2D_LOCAL int moments_replaced(s2d_ctx* c);                 // s2d_set_adam
 S2D_LOCAL void held_set_changed(s2d_ctx* c, bool had, bool has, bool added); // s2d_halo_commit
+S2D_LOCAL void alive_set_changed(s2d_ctx* c);               // s2d_set_alive, s2d_prune, s2d_grow, s2d_init_splats over a set

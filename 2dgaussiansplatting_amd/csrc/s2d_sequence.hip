@@ -510,3 +510,8 @@ void held_set_changed(s2d_ctx* c, bool had, bool has, bool added)
 {
     if (has ? (added || !had) : had) c->fresh.invalidate(Stale::Lists);
 }
+
+// The alive set changed, in either direction: always the lists, and the projection with them.  Unlike a splat that left a
+// rank's hold set -- which moved out of reach of the slab, so its old list entries cover nothing -- a row that died still
+// covers its pixels through the entries it has, and would be drawn from them.
+void alive_set_changed(s2d_ctx* c) { c->fresh.invalidate(Stale::Lists); }

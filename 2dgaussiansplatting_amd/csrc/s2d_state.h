@@ -8,7 +8,10 @@
 
 namespace s2d {
 
-// Parameters, Adam moments and the held set of slab ownership.  With a held set the Adam step touches only the splats the
+// Parameters, Adam moments and the subset of the splats that takes part: the held set of slab ownership (s2d_halo_commit), or
+// the alive set of a single context (s2d_set_alive, s2d_prune, s2d_grow).  One context has one kind at a
+// time, kind() says which.  Both are the same machinery: flags that project_kernel reads, an ascending id list and compact
+// record copies for the Adam kernels.  With a held set the Adam step touches only the splats the
 // rank holds -- a seventh of them at eight ranks, scattered through the id-indexed arrays (36- and 72-byte records, a cache
 // line or two each).  Their records are therefore kept in compact arrays in the order of held_ids, which the Adam kernel
 // reads and writes in whole lines, and which run ahead of the id-indexed arrays between two readers of those.  Nobody
@@ -38,13 +41,29 @@ public:
     hipError_t written(bool all_rows);
     // s2d_halo_commit: the held set becomes bit `rank` of masks[] (nullptr: every splat again, the buffers go).
     hipError_t commit(const uint32_t* masks, int rank, uint32_t* scan_temp);
-    const uint8_t* held() const { return held_; } // [n]: 1 = this rank holds (updates) the splat; nullptr: all
+    const uint8_t* held() const { return held_; } // [n]: 1 = this rank holds (updates) the splat, or the row is alive; nullptr: all
+    enum class Subset { None, Slab, Alive };
+    Subset kind() const { return kind_; } // whose set held() is
+    // The alive set, the second way to a subset.  An edit is three steps on the stream: begin_alive() -- the id-indexed arrays
+    // take over, the flag bytes exist (all ones when there was no set) and are handed out to be written, each 0 or 1 or, with
+    // finish_alive(normalise), any byte with non-zero = alive; the caller's kernels; finish_alive() -- id list, count and compact
+    // copies follow the flags.  grads != nullptr: the gradient records of the dead rows become +0.  A set that begin_alive()
+    // creates has its list and count (every row) queued at once: a caller that fails between the two steps leaves a context
+    // whose Adam launch walks a valid list.
+    hipError_t begin_alive(uint8_t** flags, uint32_t* scan_temp);
+    hipError_t finish_alive(float* grads, uint32_t* scan_temp);
+    hipError_t clear_alive(); // every row alive again, the buffers go (waits for the stream); nothing to do without an alive set
+    uint32_t* alive_scan_work() const { return held_work_; } // n words, free between begin_alive() and finish_alive()
+    // The number of alive rows: known to the host after a call that told it (alive_count_is), read back (waits) otherwise.
+    hipError_t alive_count(int* out);
+    void alive_count_is(int count) { alive_count_ = count; }
     // What the Adam launch about to be queued updates.  (A compact copy is ahead of the id-indexed arrays from here on.)
     AdamStep adam_step();
 
 private:
     hipError_t flush();
     hipError_t load();
+    hipError_t list_alive(float* grads, uint32_t* scan_temp); // flags -> 0 / 1, id list, count (queued)
 
     int n_ = 0;
     hipStream_t stream_ = nullptr;
@@ -55,6 +74,8 @@ private:
     bool compact_enabled_ = true;
     bool live_ = false;  // the compact arrays mirror the held splats
     bool dirty_ = false; // ... and are ahead of the id-indexed arrays (Adam steps since the last flush)
+    Subset kind_ = Subset::None;
+    int alive_count_ = -1; // -1: not known to the host
 };
 
 // The squared error of every iteration (main.cpp:796-805): the per-tile sums a backward pass leaves, and the ring of

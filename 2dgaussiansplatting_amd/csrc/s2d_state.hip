@@ -4,6 +4,8 @@
 
 #include <cstdlib>
 
+#include "s2d_alive.h"
+
 namespace s2d {
 
 hipError_t SplatState::create(int n, hipStream_t stream)
@@ -63,8 +65,10 @@ hipError_t SplatState::commit(const uint32_t* masks, int rank, uint32_t* scan_te
     if (!masks) { // (the caller has made this context's copy complete again)
         if (held_) S2D_TRY(hipStreamSynchronize(stream_));
         held_.release(), held_ids_.release(), held_work_.release(), held_count_.release();
+        kind_ = Subset::None;
         return hipSuccess;
     }
+    kind_ = Subset::Slab;
     if (!held_) {
         S2D_TRY(held_.alloc((size_t)n_));
         S2D_TRY(held_ids_.alloc((size_t)n_));
@@ -73,6 +77,66 @@ hipError_t SplatState::commit(const uint32_t* masks, int rank, uint32_t* scan_te
     }
     S2D_TRY(launch_halo_commit(masks, n_, rank, held_, held_ids_, held_count_, held_work_, scan_temp, stream_));
     return load();
+}
+
+hipError_t SplatState::list_alive(float* grads, uint32_t* scan_temp)
+{
+    if (n_ <= 0) return hipMemsetAsync(held_count_, 0, sizeof(uint32_t), stream_);
+    S2D_TRY(launch_alive_flags(held_, 0, n_, held_, held_work_, grads, stream_));
+    S2D_TRY(exclusive_scan_u32(held_work_, held_work_, n_, scan_temp, held_count_, stream_)); // held_count_ = number of alive rows
+    return launch_held_ids(held_, held_work_, n_, held_ids_, stream_);
+}
+
+hipError_t SplatState::begin_alive(uint8_t** flags, uint32_t* scan_temp)
+{
+    S2D_TRY(flush()); // the id-indexed arrays take over while the set changes
+    live_ = false;
+    alive_count_ = -1;
+    if (!held_) {
+        S2D_TRY(held_.alloc((size_t)n_));
+        S2D_TRY(held_ids_.alloc((size_t)n_));
+        S2D_TRY(held_work_.alloc((size_t)n_));
+        S2D_TRY(held_count_.alloc(4));
+        if (n_ > 0) S2D_TRY(hipMemsetAsync(held_, 1, (size_t)n_, stream_)); // without a set every row is alive
+        S2D_TRY(list_alive(nullptr, scan_temp)); // (valid from here on, whatever becomes of the edit)
+    }
+    kind_ = Subset::Alive;
+    *flags = held_;
+    return hipSuccess;
+}
+
+hipError_t SplatState::finish_alive(float* grads, uint32_t* scan_temp)
+{
+    S2D_TRY(list_alive(grads, scan_temp));
+    return load();
+}
+
+hipError_t SplatState::clear_alive()
+{
+    if (kind_ != Subset::Alive) return hipSuccess;
+    S2D_TRY(flush());
+    live_ = false;
+    S2D_TRY(hipStreamSynchronize(stream_));
+    held_.release(), held_ids_.release(), held_work_.release(), held_count_.release();
+    kind_ = Subset::None;
+    alive_count_ = -1;
+    return hipSuccess;
+}
+
+hipError_t SplatState::alive_count(int* out)
+{
+    if (kind_ != Subset::Alive) {
+        *out = n_;
+        return hipSuccess;
+    }
+    if (alive_count_ < 0) {
+        uint32_t count = 0;
+        S2D_TRY(hipMemcpyAsync(&count, held_count_, sizeof(count), hipMemcpyDeviceToHost, stream_));
+        S2D_TRY(hipStreamSynchronize(stream_));
+        alive_count_ = (int)std::min<uint32_t>(count, (uint32_t)n_);
+    }
+    *out = alive_count_;
+    return hipSuccess;
 }
 
 SplatState::AdamStep SplatState::adam_step()

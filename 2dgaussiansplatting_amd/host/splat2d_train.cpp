@@ -73,6 +73,15 @@ struct Options {
     float reseed_max_fraction = 0.1f;    // --reseed-max-fraction f: at most f * splats written per pass
     float reseed_min_weight = 5.0f;      // --reseed-min-weight w: a splat whose sum of T * alpha per pass is below w is starved
     float reseed_scale = 3.0f;           // --reseed-scale x: sx = sy of the rows written (0: sqrt(W H / splats))
+    // The alive set (include/splat2d.h "the alive set"; one context only): --splats is the capacity.  The defaults of the
+    // count, the scale, the window and the weight are PROVISIONAL: nobody has measured them yet.
+    int alive_from = -1;             // --alive-from K0: after init() / --seed-init only the LAST K0 rows are alive (-1: all)
+    int grow_every = 0;              // --grow-every M: s2d_grow before iteration M, 2M, ... from the squared error map, while a row is dead
+    int grow_count = 0;              // --grow-count C: rows brought to life per event
+    float grow_scale = 3.0f;         // --grow-scale X: sx = sy of the rows written (0: sqrt(W H / splats))
+    int prune_every = 0;             // --prune-every K: s2d_prune before iteration K, 2K, ...
+    float prune_min_weight = 0.5f;   // --prune-min-weight W: an alive row whose sum of T * alpha per pass is below W dies
+    int prune_window = 10;           // --prune-window S: the last S iterations before each pruning gather the statistics
     // --loss-weights M,L,D: train with L = sum of M * d^2 / 2 + L * |d| + D * (1 - SSIM) (include/splat2d.h "image losses"; one
     // context only) instead of the reference's squared error; the trace line gains ", loss %.6f"
     bool have_loss = false;
@@ -112,6 +121,8 @@ int usage()
                  "                     [--loss-weights M,L,D] [--seed-init edges|uniform]\n"
                  "                     [--reseed-every K [--reseed-window S] [--reseed-max-fraction F] [--reseed-min-weight W] [--reseed-scale X]]\n"
                  "                     [--lr-groups P,S,R,C,O [--lr-final-ratio P,S,R,C,O --lr-decay-iters T]] [--rebin-margin PX] [--freeze-unmoved]\n"
+                 "                     [--alive-from K0] [--grow-every M --grow-count C [--grow-scale X]]\n"
+                 "                     [--prune-every K [--prune-min-weight W] [--prune-window S]]\n"
                  "  --loss-weights M,L,D: train with the sum over pixels and channels of M * d^2 / 2 + L * |d| + D * (1 - SSIM), e.g.\n"
                  "    0,0.8,0.2, instead of the reference's squared error (one GPU only); every line ends with the loss's mean.\n"
                  "  --relocate-every K: before iteration K, 2K, ... move the starved splats (summed T * alpha per pass below W) onto\n"
@@ -128,6 +139,14 @@ int usage()
                  "    0.5,0.2,0.1,0.05,0.05; with --lr-final-ratio and --lr-decay-iters T each decays log-linearly to rate * ratio over\n"
                  "    the first T iterations (one GPU only).  --rebin-margin PX: the margin of the re-used tile lists (default 2 pixels).\n"
                  "  --freeze-unmoved: after each reseeding / relocation only the rows it wrote are trained until the next one.\n");
+    std::fprintf(stderr,
+                 "  --alive-from K0: --splats is the capacity; after init() (or --seed-init, which then seeds only those) the last K0\n"
+                 "    rows are alive.  --grow-every M --grow-count C: before iteration M, 2M, ... bring the C dead rows of lowest index\n"
+                 "    to life, drawn from the squared error map at scale X, until no row is dead.  --prune-every K: before iteration\n"
+                 "    K, 2K, ... alive rows whose summed T * alpha per pass is below W die, from statistics of the S iterations before\n"
+                 "    (not together with --relocate-every / --reseed-every).  One GPU only, not with --reference-order, and not with\n"
+                 "    --save-checkpoint / --load-checkpoint: the checkpoint format does not carry the set.  Defaults X = 3, W = 0.5,\n"
+                 "    S = 10 are provisional: not measured yet.\n");
     return 2;
 }
 
@@ -220,6 +239,7 @@ struct Session {
 int main(int argc, char** argv)
 {
     Options o;
+    bool have_alive_from = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&](const char* what) -> const char* {
@@ -279,6 +299,13 @@ int main(int argc, char** argv)
         else if (a == "--reseed-max-fraction") o.reseed_max_fraction = (float)std::atof(next("--reseed-max-fraction"));
         else if (a == "--reseed-min-weight") o.reseed_min_weight = (float)std::atof(next("--reseed-min-weight"));
         else if (a == "--reseed-scale") o.reseed_scale = (float)std::atof(next("--reseed-scale"));
+        else if (a == "--alive-from") { o.alive_from = std::atoi(next("--alive-from")); have_alive_from = true; }
+        else if (a == "--grow-every") o.grow_every = std::atoi(next("--grow-every"));
+        else if (a == "--grow-count") o.grow_count = std::atoi(next("--grow-count"));
+        else if (a == "--grow-scale") o.grow_scale = (float)std::atof(next("--grow-scale"));
+        else if (a == "--prune-every") o.prune_every = std::atoi(next("--prune-every"));
+        else if (a == "--prune-min-weight") o.prune_min_weight = (float)std::atof(next("--prune-min-weight"));
+        else if (a == "--prune-window") o.prune_window = std::atoi(next("--prune-window"));
         else return usage();
     }
     if (!o.convert_in.empty()) { // file conversion between .s2di / .ppm / .png; touches no GPU
@@ -339,6 +366,32 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "--freeze-unmoved needs --reseed-every or --relocate-every: it freezes what their events did not write\n");
         return 2;
     }
+    const bool alive_options = have_alive_from || o.grow_every != 0 || o.grow_count != 0 || o.prune_every != 0;
+    if (alive_options) { // (all of it before the device is touched)
+        if ((have_alive_from && (o.alive_from < 0 || o.alive_from > o.n_splats)) || o.grow_every < 0 || o.grow_count < 0 || !(o.grow_scale >= 0.0f) ||
+            o.prune_every < 0 || o.prune_window < 1 || !(o.prune_min_weight > 0.0f))
+            return usage();
+        if ((o.grow_every > 0) != (o.grow_count > 0)) {
+            std::fprintf(stderr, "--grow-every and --grow-count go together\n");
+            return 2;
+        }
+        if (o.gpus > 1 || std::getenv("S2D_TRAIN_FORCE_MULTI")) {
+            std::fprintf(stderr, "--alive-from, --grow-every and --prune-every work on one context: the multi-device handle has no alive set\n");
+            return 2;
+        }
+        if (o.reference_order) {
+            std::fprintf(stderr, "--alive-from, --grow-every and --prune-every are not available with --reference-order\n");
+            return 2;
+        }
+        if (!o.save_ckpt.empty() || !o.load_ckpt.empty()) {
+            std::fprintf(stderr, "--alive-from, --grow-every and --prune-every: the checkpoint format does not carry the alive set\n");
+            return 2;
+        }
+        if (o.prune_every > 0 && (o.relocate_every > 0 || o.reseed_every > 0)) {
+            std::fprintf(stderr, "--prune-every owns the statistics window: not together with --relocate-every / --reseed-every\n");
+            return 2;
+        }
+    }
     Session S;
     CK(S.create(o, W, H));
     if (have_optim) { // (groups without a rate of their own: the one --lr)
@@ -389,19 +442,32 @@ int main(int argc, char** argv)
     CK(S.set_target(imageRef)); // (empty: the synthetic target is generated on the device)
     // init(), and with --seed-init every row drawn again from the target (the moments init() zeroed stay zero)
     auto seed_all = [&]() -> int {
-        if (o.seed_init.empty()) return S2D_OK;
+        if (o.seed_init.empty() || (have_alive_from && o.alive_from == 0)) return S2D_OK; // (no row alive: none to seed)
         s2d_seed_config sc;
         std::memset(&sc, 0, sizeof(sc));
         sc.struct_size = sizeof(sc);
         sc.source = S2D_SEED_TARGET_EDGES;
         sc.floor = o.seed_init == "uniform" ? 4095u : 0u;
         int32_t placed = 0;
-        const int rc = s2d_seed_splats(S.ctx, &sc, nullptr, o.n_splats, &placed);
+        std::vector<int32_t> last; // --alive-from: only the rows that will be alive
+        for (int i = o.n_splats - o.alive_from; have_alive_from && i < o.n_splats; i++) last.push_back(i);
+        const int rc = have_alive_from ? s2d_seed_splats(S.ctx, &sc, last.data(), (int32_t)last.size(), &placed)
+                                       : s2d_seed_splats(S.ctx, &sc, nullptr, o.n_splats, &placed);
         if (rc == S2D_OK) std::fprintf(stderr, "seeded %d splats from the target (%s)\n", (int)placed, o.seed_init.c_str());
+        return rc;
+    };
+    // --alive-from: the last K0 rows -- the back of the blend order, so that what --grow-every adds lies in front of them
+    auto alive_from_start = [&]() -> int {
+        if (!have_alive_from) return S2D_OK;
+        std::vector<uint8_t> mask((size_t)o.n_splats, 0);
+        for (int i = o.n_splats - o.alive_from; i < o.n_splats; i++) mask[(size_t)i] = 1;
+        const int rc = s2d_set_alive(S.ctx, mask.data());
+        if (rc == S2D_OK) std::fprintf(stderr, "%d of %d splats alive at the start\n", o.alive_from, o.n_splats);
         return rc;
     };
     CK(S.init());               // init(); main.cpp:307
     CK(seed_all());
+    CK(alive_from_start());
 
     int iterations = 0; // main.cpp:278
     if (!o.load_ckpt.empty()) {
@@ -431,6 +497,7 @@ int main(int argc, char** argv)
         if (iterations == o.restart_at) { // ImGui::Button("Restart"), main.cpp:828-831: init() also sets
             CK(S.init());                 // iterations = 0 (main.cpp:281), so the trace restarts at "0 itr"
             CK(seed_all());
+            CK(alive_from_start());
             o.iters -= iterations;        // --iters is the number of frames to run in total
             iterations = 0;
             o.restart_at = -1;
@@ -441,14 +508,25 @@ int main(int argc, char** argv)
         if (o.restart_at > iterations && iterations + k > o.restart_at) k = o.restart_at - iterations;
         const bool opacity_now = o.optimize_opacity && iterations >= o.opacity_from; // bool optimizeOpacity, main.cpp:317
         uint32_t density = 0u;
-        if (o.relocate_every > 0 || o.reseed_every > 0) {
+        if (o.relocate_every > 0 || o.reseed_every > 0 || o.prune_every > 0) {
             // iterations [mK - S, mK) gather the statistics; the relocation (or the reseeding) runs in front of iteration mK
             const bool reseed = o.reseed_every > 0; // (never both: refused above)
-            const int K = reseed ? o.reseed_every : o.relocate_every, window = reseed ? o.reseed_window : o.relocate_window;
+            const bool prune = o.prune_every > 0;   // (alone: refused above)
+            const int K = prune ? o.prune_every : reseed ? o.reseed_every : o.relocate_every;
+            const int window = prune ? o.prune_window : reseed ? o.reseed_window : o.relocate_window;
             const int S_ = window < K ? window : K;
             int32_t passes = 0;
             if (iterations > 0 && iterations % K == 0) CK(s2d_density_get(S.ctx, nullptr, &passes));
-            if (passes > 0 && reseed) {
+            if (passes > 0 && prune) {
+                s2d_prune_config pc;
+                pc.struct_size = sizeof(pc);
+                pc.min_weight = o.prune_min_weight;
+                pc.min_opacity = 0.0f;
+                int32_t pruned = 0, alive = 0;
+                CK(s2d_prune(S.ctx, &pc, &pruned));
+                CK(s2d_get_alive(S.ctx, nullptr, &alive));
+                std::fprintf(stderr, "pruned %d splats before iteration %d, %d alive\n", (int)pruned, iterations, (int)alive);
+            } else if (passes > 0 && reseed) {
                 s2d_seed_config sc;
                 std::memset(&sc, 0, sizeof(sc));
                 sc.struct_size = sizeof(sc);
@@ -479,6 +557,25 @@ int main(int argc, char** argv)
             else if (iterations + k > window_begin) k = window_begin - iterations;
             if (iterations + k > next_reloc) k = next_reloc - iterations;
         }
+        if (o.grow_every > 0) { // before iteration M, 2M, ...: while a row is dead
+            int32_t alive = o.n_splats;
+            if (iterations > 0 && iterations % o.grow_every == 0) CK(s2d_get_alive(S.ctx, nullptr, &alive));
+            if (alive < o.n_splats) {
+                s2d_seed_config sc;
+                std::memset(&sc, 0, sizeof(sc));
+                sc.struct_size = sizeof(sc);
+                sc.source = S2D_SEED_ERROR;
+                sc.flags = S2D_SEED_SQUARED;
+                sc.seed = (uint32_t)(iterations / o.grow_every);
+                sc.scale = o.grow_scale;
+                int32_t grown = 0;
+                CK(s2d_forward(S.ctx)); // the error map is that of the current parameters
+                CK(s2d_grow(S.ctx, &sc, nullptr, o.grow_count, &grown));
+                std::fprintf(stderr, "grew %d splats before iteration %d, %d alive\n", (int)grown, iterations, (int)(alive + grown));
+            }
+            const int next_grow = (iterations / o.grow_every + 1) * o.grow_every;
+            if (iterations + k > next_grow) k = next_grow - iterations;
+        }
         const uint32_t step_flags = (opacity_now ? S2D_STEP_OPTIMIZE_OPACITY : 0u) | density;
         if (o.have_loss) CK(s2d_step_loss(S.ctx, k, step_flags, &o.loss, loss.data(), mse.data()));
         else CK(S.step(k, step_flags, mse.data()));
@@ -494,6 +591,11 @@ int main(int argc, char** argv)
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::fprintf(stderr, "%d iterations in %.3f s = %.2f it/s (%dx%d, %d splats%s)\n", frames, secs,
                  secs > 0 ? frames / secs : 0.0, W, H, o.n_splats, S.exchange_summary(o).c_str());
+    if (alive_options) {
+        int32_t alive = 0;
+        CK(s2d_get_alive(S.ctx, nullptr, &alive));
+        std::fprintf(stderr, "%d of %d splats alive at the end\n", (int)alive, o.n_splats);
+    }
     int exit_code = 0; // an output file that cannot be written is an error, reported after everything else was tried
 
     if (!o.save_ckpt.empty()) {

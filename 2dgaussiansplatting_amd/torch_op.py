@@ -66,6 +66,15 @@ class SplatRenderer:
     def set_target(self, rgba32f):
         self.trainer.set_target(rgba32f)
 
+    def set_alive(self, mask):
+        """Trainer.set_alive: n booleans, False = the row is not drawn and its gradient row comes back as zeros; None: every
+        row again.  A frame rendered before the call is drawn again by its backward()."""
+        self.trainer.set_alive(mask)
+        self.generation += 1
+
+    def alive(self):
+        return self.trainer.alive()
+
     def _check_stream(self):
         if torch.cuda.current_stream(self.device).cuda_stream != self.stream:
             raise RuntimeError("SplatRenderer was created on stream %#x and is called with another stream current: its "

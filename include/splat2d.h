@@ -412,6 +412,54 @@ int s2d_optim_rates_at(s2d_ctx* ctx, int32_t iteration, float rates[5]);
 int s2d_set_frozen(s2d_ctx* ctx, const uint8_t* frozen_host);        /* n_splats bytes, non-zero = frozen; NULL: none */
 int s2d_set_frozen_device(s2d_ctx* ctx, const uint8_t* frozen_device); /* copied on the context's stream; NULL: none */
 
+/* ---- the alive set: how many splats take part (no counterpart in the reference, whose NSplat is fixed at init(),
+ * main.cpp:271).  n_splats of s2d_config is the CAPACITY; a context may keep any subset of its rows
+ * alive.  A dead row does not exist for the passes:
+ *   raster      no footprint: empty tile rectangle, no list entry, no colour contribution; its gradient record stays +0;
+ *   Adam        the step skips it: 9 parameters, 18 moments and the dormant byte stay byte for byte, the finite guard does
+ *               not see it;
+ *   statistics  its density statistics stay as they were (0 after a reset);
+ *   blend order the row keeps its INDEX, which is its place in the blend order (main.cpp:419): a row that comes alive again
+ *               is blended where its index says.
+ * A context with an alive set draws exactly the image of a context that holds only the alive rows, in index order.
+ * s2d_init_splats clears the set, as it clears the frozen mask; s2d_set_splats[_device], s2d_set_adam, the row calls,
+ * s2d_set_optim and s2d_set_frozen keep it.  ANY change of the set -- departures too: a row that died would still cover its
+ * pixels through its old list entries -- invalidates the tile lists, and the projection with them, before the next raster pass.
+ * Everything works on a context with a set: s2d_forward, s2d_backward, s2d_forward_backward, s2d_step (fused and with
+ * S2D_STEP_DENSITY_STATS), s2d_adam_step, s2d_backward_image_grads, the loss entry points, s2d_set_optim / s2d_set_frozen (a
+ * row trains only when it is alive and not frozen), s2d_importance and s2d_seed_splats (seeding writes rows and does not
+ * change which are alive), s2d_relocate and s2d_reseed (dead rows are neither starved nor donors), index-range rendering,
+ * fp16 images, generic binning, counting and exact-exp contexts.
+ * S2D_E_INVALID, before any device work, for the five calls below on a slab context (row_begin / row_end), a context with a
+ * held set from s2d_halo_commit, or a S2D_CFG_REFERENCE_ORDER context; and s2d_halo_masks, and s2d_halo_commit with masks,
+ * refuse a context that has an alive set.  The multi-device handle (s2d_multi) has no alive set: out of scope here. */
+/* n_splats bytes, non-zero = alive; NULL: every row alive again (the buffers go). */
+int s2d_set_alive(s2d_ctx* ctx, const uint8_t* alive_host);
+int s2d_set_alive_device(s2d_ctx* ctx, const uint8_t* alive_device);   /* copied on the context's stream */
+/* alive_host: n_splats bytes, each 0 or 1 (all 1 without a set); count: alive rows.  Either may be NULL. */
+int s2d_get_alive(s2d_ctx* ctx, uint8_t* alive_host, int32_t* count);
+/* alive' = alive AND NOT (criterion 1 OR criterion 2), decided on the device, one thread per row; a context without a set
+ * starts from all ones.  *pruned (may be NULL): rows that died, from one read-back of the new count (one more, of the old
+ * count, where the host does not know it: after s2d_set_alive_device).  With min_weight > 0 the
+ * call needs a statistics pass since the last reset (S2D_E_STATE otherwise) and resets the statistics afterwards, as
+ * s2d_relocate does.  No parameter or moment of any row is touched.  S2D_E_INVALID for a negative or NaN threshold, for both
+ * thresholds 0, or for a wrong struct_size. */
+typedef struct s2d_prune_config {
+    uint32_t struct_size; /* = sizeof(s2d_prune_config) */
+    float min_weight;     /* > 0: prune alive rows with (double)weight / (double)passes < (double)min_weight; 0: criterion off */
+    float min_opacity;    /* > 0: prune alive rows with opacity < min_opacity; 0: off */
+} s2d_prune_config;
+int s2d_prune(s2d_ctx* ctx, const s2d_prune_config* cfg, int32_t* pruned);
+/* Brings dead rows to life and seeds them.  ids_host: the rows -- distinct, in range, each currently dead, else
+ * S2D_E_INVALID; NULL: the min(count, dead) dead rows of LOWEST index, the front-most free places in the blend order (so
+ * that what is grown is not buried under what is there), chosen on the device from a scan over the dead flags.  The chosen
+ * rows are written exactly as s2d_seed_splats writes those ids under the same config (same map, same draw per (i, seed),
+ * moments +0; scale == 0 still means sqrt(W * H / n_splats) with n_splats the capacity), and all refusals and state rules of
+ * s2d_seed_splats apply.  Then the rows are alive and the lists invalid; statistics, frozen mask and iteration counters are
+ * untouched.  *grown (may be NULL): rows written -- 0 when the map's total is 0 (nothing changes then); no dead row, or
+ * count == 0, gives S2D_OK with 0. */
+int s2d_grow(s2d_ctx* ctx, const s2d_seed_config* cfg, const int32_t* ids_host, int32_t count, int32_t* grown);
+
 /* `iters` whole iterations (main.cpp:414-809): forward, backward, Adam, MSE.  mse_out (may be NULL) receives
  * iters doubles: the value the reference prints for each iteration (main.cpp:796-807).  For a slab context the
  * values are this slab's sum of squared errors divided by (H*W*3), i.e. partial MSEs that add up over slabs.
