@@ -288,8 +288,6 @@ struct RefOrder {
 // uses of `a`: tile_off, exec_list, wave_masks, tile_exec, proj, image0, image_ref / upstream, grads, g, status, iteration,
 // exact_exp, need_opacity_grad (false: the opacity component of a.grads is left as it is)
 hipError_t launch_reference_backward(const RasterArgs& a, const RefOrder& ro, hipStream_t stream);
-// RasterPass::Forward for such a context with exact_exp: expf with the bits of the oracle's libm (s2d_math.h expf_ref)
-hipError_t launch_reference_forward_exact(const RasterArgs& a, hipStream_t stream);
 // *out = the slab's squared error as main.cpp:796-805 adds it: one double chain over pixel_sqerr[0 .. pixels), in order
 hipError_t launch_reference_sqerr(const float* pixel_sqerr, size_t pixels, double* out, const DeviceStatus* status, int iteration,
                                   hipStream_t stream);

@@ -159,8 +159,8 @@ S2D_HD float gauss_pow8(float d2, bool* nonzero)
 // optimized routines -- x*32/ln2 = k + r, 2^(k/32) from a 32-entry table, a cubic in r, all in double, rounded to float
 // once -- compiled with FMA contraction).  A restatement of that published algorithm with the contractions written out,
 // like sincos_f32 above; it returns the same bits as this container's libm for 2.6e8 arguments spread over [-104.5, 89.5]
-// (every 7th / 11th float), 0 mismatches.  S2D_CFG_REFERENCE_ORDER with S2D_CFG_EXACT_EXP uses it in both walks: the
-// device library's own expf is accurate to 1 ulp, not equal to libm's.
+// (every 7th / 11th float), 0 mismatches.  Every S2D_CFG_EXACT_EXP kernel uses it, in both walks: the device library's
+// own expf is accurate to 1 ulp, not equal to libm's.
 S2D_HD float expf_ref(float x)
 {
     const uint64_t tab[32] = {

@@ -184,14 +184,15 @@ __device__ __forceinline__ int stage_masks(uint32_t* s_mask32, int se, int sub, 
 // EXACT (S2D_CFG_EXACT_EXP): G = expf(-d2/2) instead of exp_approx -- the switch the reference keeps at main.cpp:51
 // "for numerical varidation": the analytic gradients are those of the TRUE exponential, so only in this mode is the
 // backward pass the derivative of the forward pass (tests/test_fd_end_to_end.py checks exactly that by finite differences).
-// REFEXP (the forward kernel of S2D_CFG_REFERENCE_ORDER contexts only): expf with the bits of the oracle's libm
-// (s2d_math.h expf_ref) instead of the device library's, which is accurate to 1 ulp but not equal to it.
-template <bool EXACT, bool REFEXP = false>
+// The expf is the one with the bits of the oracle's libm (s2d_math.h expf_ref), in every kernel of the mode: the device
+// library's is accurate to 1 ulp but not equal to it, and a framebuffer that is an ulp off the reference's cannot be held
+// to it on bits (tests/test_gpu_raster_variants.py does, for every exact variant).
+template <bool EXACT>
 __device__ __forceinline__ float gauss_of(float d2, bool* nonzero)
 {
     if (EXACT) {
         *nonzero = true;
-        return REFEXP ? expf_ref(-0.5f * d2) : expf(-0.5f * d2); // main.cpp:51, :527
+        return expf_ref(-0.5f * d2); // main.cpp:51, :527
     }
     return gauss_pow8(d2, nonzero);
 }
@@ -281,7 +282,7 @@ __device__ __forceinline__ bool block_any_alive_exec(int4* flags, unsigned long 
 // splats of one INDEX RANGE only; the walk continues from the pixel's state after the ranges before it -- (crg, cb) and
 // *T_io on entry -- and leaves the state for the range after it.  The reference's loop is front to back in index order
 // (main.cpp:419), so cutting it at any index and carrying (colour, T) across the cut changes no operation.
-template <bool COUNT, bool EXACT, bool CHUNK = false, bool REFEXP = false>
+template <bool COUNT, bool EXACT, bool CHUNK = false>
 __device__ __forceinline__ uint32_t forward_tile(FwdShared& s, const TileCtx& c, const uint32_t* __restrict__ tile_off,
                                              const uint32_t* __restrict__ list, const ProjRec* __restrict__ proj,
                                              unsigned long long* __restrict__ wave_masks, uint32_t* __restrict__ exec_list,
@@ -370,7 +371,7 @@ __device__ __forceinline__ uint32_t forward_tile(FwdShared& s, const TileCtx& c,
                 const f2 m = mk2(q0.z, q0.w) * v.x + mk2(q1.x, q1.y) * v.y;  // inv_cov * v: (a vx + b vy, b vx + d vy)
                 const f2 vm = v * m;
                 bool nonzero;
-                const float G = gauss_of<EXACT, REFEXP>(vm.x + vm.y, &nonzero); // main.cpp:526-527
+                const float G = gauss_of<EXACT>(vm.x + vm.y, &nonzero);         // main.cpp:526-527
                 const unsigned long long on = act & __ballot(nonzero);
                 const float alpha = __builtin_amdgcn_inverse_ballot_w64(on) ? G * q2.y : 0.0f;
                 crg += (T * mk2(q1.z, q1.w)) * alpha;                        // main.cpp:529-530: (T*c)*alpha
@@ -423,7 +424,7 @@ __device__ __forceinline__ bool launch_is_void(const DeviceStatus* status, int a
     return (abort_stamp != 0 && status->rebin_needed == abort_stamp) || status->first_nonfinite_iter < iteration;
 }
 
-template <bool COUNT, bool HALF, bool EXACT, bool REFEXP = false>
+template <bool COUNT, bool HALF, bool EXACT>
 __global__ __launch_bounds__(256) void raster_forward_kernel(const uint32_t* __restrict__ tile_off,
                                                              const uint32_t* __restrict__ list,
                                                              const ProjRec* __restrict__ proj,
@@ -441,7 +442,7 @@ __global__ __launch_bounds__(256) void raster_forward_kernel(const uint32_t* __r
     const TileCtx c = tile_ctx(tile, g);
     f2 crg;
     float cb;
-    const uint32_t n_exec = forward_tile<COUNT, EXACT, false, REFEXP>(s, c, tile_off, list, proj, wave_masks, exec_list, retire_hint, g, counters, crg, cb);
+    const uint32_t n_exec = forward_tile<COUNT, EXACT>(s, c, tile_off, list, proj, wave_masks, exec_list, retire_hint, g, counters, crg, cb);
     if (!COUNT && c.tid == 0) tile_exec[tile] = n_exec; // the backward walk is another launch
     if (c.inside) store_pixel<HALF>(image0, pixel_index(c, g), make_float4(crg.x, crg.y, cb, 1.0f)); // .w reset, main.cpp:543-546
 }
@@ -1396,17 +1397,6 @@ __global__ __launch_bounds__(64) void reference_sqerr_kernel(const float* __rest
         }
     }
     if (lane == 0) *out = acc;
-}
-
-// The forward pass of a reference-order context with S2D_CFG_EXACT_EXP: raster_forward_kernel with the libm-equal expf
-// (every other such context takes launch_raster's forward kernel, whose arithmetic is the reference's already).
-hipError_t launch_reference_forward_exact(const RasterArgs& a, hipStream_t stream)
-{
-    if (a.g.num_tiles <= 0) return hipSuccess;
-    hipLaunchKernelGGL((raster_forward_kernel<false, false, true, true>), dim3(raster_grid(a.g.num_tiles)), dim3(256), 0, stream,
-                       a.tile_off, a.list, a.proj, a.image0, a.wave_masks, a.exec_list, a.tile_exec, a.retire_hint, a.g, a.status,
-                       a.abort_stamp, a.iteration, a.counters);
-    return hipGetLastError();
 }
 
 hipError_t launch_reference_backward(const RasterArgs& a, const RefOrder& ro, hipStream_t stream)

@@ -185,10 +185,7 @@ int launch_job(s2d_ctx* c, bool optimistic, const RasterJob& job)
         a.write_image = job.write_image;
         if (c->trace.plan(true, true) == SqerrBy::PassItself) a.sq = c->trace.job(c->iterations);
     }
-    if (c->scratch.reference_order() && a.exact_exp) // (never fused: queue_forward_backward)
-        S2D_HIP(c, launch_reference_forward_exact(a, c->stream));
-    else
-        S2D_HIP(c, launch_raster(job.fused ? RasterPass::Fused : RasterPass::Forward, a, c->stream));
+    S2D_HIP(c, launch_raster(job.fused ? RasterPass::Fused : RasterPass::Forward, a, c->stream));
     return S2D_OK;
 }
 

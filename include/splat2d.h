@@ -108,8 +108,9 @@ typedef enum s2d_status {
                                     * main.cpp:51 "for numerical varidation".  The analytic gradients (main.cpp:639-704)
                                     * are those of the true exponential, so in this mode the backward pass is the
                                     * derivative of the forward pass and a finite-difference check closes
-                                    * (tests/test_fd_end_to_end.py).  Not combinable with S2D_CFG_COUNT_PAIRS /
-                                    * S2D_CFG_FP16_IMAGES. */
+                                    * (tests/test_fd_end_to_end.py).  The expf has the bits of glibc's (the reference built
+                                    * with g++ on x86-64), so image0 is the reference's byte for byte in this mode too.
+                                    * Not combinable with S2D_CFG_COUNT_PAIRS / S2D_CFG_FP16_IMAGES. */
 #define S2D_CFG_ADAM_FP32 0x10u    /* Adam::optimize (main.cpp:155) with the quotient and subtraction in fp32, as the
                                     * reference's own MSVC build evaluates the unqualified `sqrt` (float overload).
                                     * Default: the double-precision quotient of a g++/clang++ build, which is what the

@@ -93,6 +93,20 @@ def synthetic_target(W, H):
     return out
 
 
+def random_splats(n, W, H, seed):
+    """Adversarial splats: thin, huge, rotated, off-centre, low opacities (what the parity and variant tests draw from)."""
+    rng = np.random.default_rng(seed)
+    s = np.zeros(n, dtype=SPLAT_DTYPE)
+    s["pos"][:, 0] = rng.uniform(0, W - 1, n)
+    s["pos"][:, 1] = rng.uniform(0, H - 1, n)
+    s["sx"] = rng.choice([1.0, 1.5, 3.0, 8.0, 40.0, 300.0, 1024.0], n, p=[.15, .15, .3, .3, .06, .03, .01])
+    s["sy"] = rng.choice([1.0, 2.0, 6.0, 25.0, 1024.0], n, p=[.2, .3, .4, .09, .01])
+    s["rot"] = rng.uniform(-7, 7, n)
+    s["color"] = rng.uniform(0, 1, (n, 3))
+    s["opacity"] = rng.uniform(0.1, 1.0, n)
+    return s
+
+
 class OracleTrainer:
     """Holds the locals of the reference's main() that the three passes own (main.cpp:272-278, 310-314)."""
 

@@ -25,7 +25,8 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from test_gpu_parity import REL, _lists, random_splats
+from oracle_lib import random_splats
+from test_gpu_parity import REL, _lists
 from test_gpu_reference_order import same32, same64
 
 pytestmark = pytest.mark.gpu

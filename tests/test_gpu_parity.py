@@ -32,6 +32,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from oracle_lib import random_splats
 
 pytestmark = pytest.mark.gpu
 
@@ -63,19 +64,6 @@ def grad_check(got, oracle):
     """Asserts the three gradient bars of the module docstring; `oracle` has just run forward()."""
     w32, dsum, dabs = oracle.backward_stats()
     return O.grad_bars(got.view(np.float32), w32.view(np.float32), dsum, dabs, REL)["c_gpu_vs_oracle"]
-
-
-def random_splats(n, W, H, seed):
-    rng = np.random.default_rng(seed)
-    s = np.zeros(n, dtype=O.SPLAT_DTYPE)
-    s["pos"][:, 0] = rng.uniform(0, W - 1, n)
-    s["pos"][:, 1] = rng.uniform(0, H - 1, n)
-    s["sx"] = rng.choice([1.0, 1.5, 3.0, 8.0, 40.0, 300.0, 1024.0], n, p=[.15, .15, .3, .3, .06, .03, .01])
-    s["sy"] = rng.choice([1.0, 2.0, 6.0, 25.0, 1024.0], n, p=[.2, .3, .4, .09, .01])
-    s["rot"] = rng.uniform(-7, 7, n)
-    s["color"] = rng.uniform(0, 1, (n, 3))
-    s["opacity"] = rng.uniform(0.1, 1.0, n)
-    return s
 
 
 # ---------------------------------------------------------------------------------------------

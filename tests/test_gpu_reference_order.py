@@ -19,7 +19,8 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from test_gpu_parity import make_pair, mini_target, random_splats
+from oracle_lib import random_splats
+from test_gpu_parity import make_pair, mini_target
 
 pytestmark = pytest.mark.gpu
 

@@ -39,7 +39,7 @@ def p(a):
 
 
 def draw(rng, n):
-    """Parameters as random_splats of tests/test_gpu_parity.py draws them; the positions lie around the one pixel instead
+    """Parameters as random_splats of tests/oracle_lib.py draws them; the positions lie around the one pixel instead
     of inside a 1 x 1 image (which would put every splat at the origin)."""
     s = np.zeros(n, dtype=O.SPLAT_DTYPE)
     s["pos"] = rng.uniform(-3.0, 4.0, (n, 2))

@@ -60,6 +60,43 @@ def test_working_launch_durations(tmp_path):
     assert row[1:5] == ["12", "1505", "3", "9"] and float(row[5]) == 2000.0
 
 
+def test_variant_coverage_names_the_rows_a_trace_never_dispatched(tmp_path):
+    """tools/gpu_variant_coverage.py on a synthetic kernel trace: names as rocprofv3 writes them (`void`, the argument list, a
+    mangled one, a `.kd` suffix), spread over two files; every row of tests/raster_variants.py but two is dispatched."""
+    import raster_variants as RV
+    tool = os.path.join(O.ROOT, "tools", "gpu_variant_coverage.py")
+    left_out = [RV.NAMES[3], RV.NAMES[-1]]
+    stats = [n for n in RV.NAMES if n.endswith(", float*>")]
+    assert stats and stats[0] not in left_out
+    rows = [["void %s(unsigned int const*, float*)" % n, 10 * k, 10 * k + 5] for k, n in enumerate(RV.NAMES) if n not in left_out]
+    rows.append(["void %s(int)" % RV.NAMES[0], 1, 2])                                   # a second dispatch of the first row
+    rows.append(["void s2d::raster_backward_kernel<false , false,false, false, false, false, true, float *>(int)", 3, 4])
+    rows.append(["_ZN3s2d19gather_grads_kernelEPKjS1_jPKfS1_PjjPf.kd", 5, 6])           # mangled, not a row: information only
+    rows.append(["void s2d::adam_kernel<true>(int)", 7, 8])                             # another unit's kernel
+    for k, part in enumerate((rows[:40], rows[40:])):
+        p = str(tmp_path / "t" / ("p%d" % k) / ("%d_kernel_trace.csv" % k))
+        os.makedirs(os.path.dirname(p))
+        with open(p, "w") as f:
+            w = csv.writer(f)
+            w.writerow(["Kernel_Name", "Start_Timestamp", "End_Timestamp"])
+            w.writerows(part)
+    r = subprocess.run([sys.executable, tool, str(tmp_path / "t")], stdout=subprocess.PIPE, universal_newlines=True)
+    assert r.returncode == 1
+    lines = r.stdout.splitlines()
+    assert lines[0].startswith("# raster kernel variants dispatched: %d of %d " % (len(RV.NAMES) - 2, len(RV.NAMES)))
+    got = {l.split(None, 2)[2]: l.split(None, 2)[:2] for l in lines if not l.startswith("#")}
+    assert [n for n, v in got.items() if v[0] == "MISSING"] == left_out
+    assert got[RV.NAMES[0]] == ["dispatched", "2"]
+    assert got["s2d::raster_backward_kernel<false, false, false, false, false, false, true, float*>"] == ["dispatched", "2"]
+    assert got["s2d::gather_grads_kernel"] == ["other", "1"] and not any("adam" in n for n in got)
+    # ... and with the two rows dispatched as well, every row is there and the exit status says so
+    with open(p, "a") as f:
+        csv.writer(f).writerows([["void %s()" % n, 0, 1] for n in left_out])
+    r = subprocess.run([sys.executable, tool, str(tmp_path / "t")], stdout=subprocess.PIPE, universal_newlines=True)
+    assert r.returncode == 0 and "MISSING" not in r.stdout
+    assert r.stdout.startswith("# raster kernel variants dispatched: %d of %d " % (len(RV.NAMES), len(RV.NAMES)))
+
+
 def test_one_residual_correction_gives_the_ieee_quotient():
     """csrc/s2d_raster.hip::div_by_recip: q = S*r; q += (S - den*q)*r with r a 1-ulp reciprocal.  What its comment claims, on
     three operand populations of the backward blend's range incl. den = 1e-15 and quotients placed next to rounding midpoints

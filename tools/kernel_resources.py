@@ -7,8 +7,9 @@
 
 compare: every kernel instantiation of `old` must be in `new` with the same SGPRs, VGPRs, AGPRs, scratch, LDS and occupancy
 (exit status 1 otherwise); instantiations only `new` has are listed.  A kernel that gained a trailing template flag is
-matched with its `false` instantiation (`k<a, b>` of old == `k<a, b, false>` of new): adding a defaulted flag renames the
-symbol and must change nothing else.  The order in which variants are instantiated has moved the register allocation of
+matched with its `false` instantiation (`k<a, b>` of old == `k<a, b, false>` of new), and one that lost a trailing flag
+with the old `false` instantiation (`k<a, b, false>` of old == `k<a, b>` of new): adding or dropping a defaulted flag renames
+the symbol and must change nothing else.  The order in which variants are instantiated has moved the register allocation of
 unrelated kernels before (s2d_raster.hip, with_variant), which is what this is run for.
 asm: the device assembly (--offload-device-only -S) of every kernel of the old tree against the same kernel of the new one,
 comments dropped and local labels unnumbered: which are instruction for instruction the same (exit status 1 if one is not).
@@ -39,6 +40,17 @@ def _plain(names):
     return [re.sub(r"\(.*$", "", p).replace("void ", "") for p in out.splitlines()]
 
 
+def _renamed(new, name):
+    """The kernel of `new` that `name` of the old tree became when a trailing template flag was added (its `false`
+    instantiation) or a trailing flag that was `false` was dropped."""
+    if not name.endswith(">"):
+        return None
+    got = new.get(name[:-1] + ", false>")
+    if got is None and name.endswith(", false>"):
+        got = new.get(name[:-len(", false>")] + ">")
+    return got
+
+
 def assembly(csrc, source="s2d_raster.hip"):
     """{kernel: its instructions as text} of one translation unit."""
     build, flags = _build_flags()
@@ -61,7 +73,7 @@ def assembly(csrc, source="s2d_raster.hip"):
 def compare_assembly(old, new, label=""):
     same, changed = 0, []
     for name, want in sorted(old.items()):
-        got = new.get(name, new.get(name[:-1] + ", false>") if name.endswith(">") else None)
+        got = new.get(name, _renamed(new, name))
         if got == want:
             same += 1
         else:
@@ -95,16 +107,14 @@ def report(csrc, source="s2d_raster.hip"):
 def compare(old, new):
     bad, matched = [], 0
     for name, want in sorted(old.items()):
-        got = new.get(name)
-        if got is None and name.endswith(">"):
-            got = new.get(name[:-1] + ", false>")
+        got = new.get(name, _renamed(new, name))
         if got is None:
             bad.append("%s: gone" % name)
         elif got != want:
             bad.append("%s: %s -> %s" % (name, want, got))
         else:
             matched += 1
-    known = set(old) | {n[:-1] + ", false>" for n in old if n.endswith(">")}
+    known = set(old) | {n[:-1] + ", false>" for n in old if n.endswith(">")} | {n[:-len(", false>")] + ">" for n in old if n.endswith(", false>")}
     added = sorted(n for n in new if n not in known)
     print("%d of %d kernels of the old tree unchanged, %d new" % (matched, len(old), len(added)))
     for n in added:
