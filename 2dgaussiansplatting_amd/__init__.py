@@ -74,6 +74,15 @@ class _LossConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("w_mse", C.c_float), ("w_l1", C.c_float), ("w_dssim", C.c_float)]
 
 
+class _ViewConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("out_width", C.c_int32), ("out_height", C.c_int32), ("origin_x", C.c_float),
+                ("origin_y", C.c_float), ("zoom", C.c_float), ("filter_var", C.c_float), ("samples", C.c_int32),
+                ("format", C.c_uint32)]
+
+
+S2D_VIEW_RGBA32F, S2D_VIEW_RGBA8 = 0, 1
+
+
 class _OptimConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("rate", C.c_float * 5), ("final_ratio", C.c_float * 5),
                 ("decay_iterations", C.c_int32)]
@@ -112,8 +121,9 @@ ABI_SYMBOLS = [
     "s2d_loss_image_grads_device", "s2d_loss_backward", "s2d_loss_get", "s2d_step_loss",
     "s2d_set_optim", "s2d_optim_rates_at", "s2d_set_frozen", "s2d_set_frozen_device",
     "s2d_set_alive", "s2d_set_alive_device", "s2d_get_alive", "s2d_prune", "s2d_grow",
+    "s2d_view_splats", "s2d_render_view", "s2d_render_view_device", "s2d_view_release",
     "s2d_last_error", "s2d_test_sincos", "s2d_test_sort_pairs", "s2d_test_exclusive_scan",
-    "s2d_test_sort_tile_offsets", "s2d_debug_get_tile_lists",
+    "s2d_test_sort_tile_offsets", "s2d_debug_get_tile_lists", "s2d_debug_view_raster",
     "s2d_halo_masks", "s2d_halo_commit", "s2d_rows_gather", "s2d_rows_scatter", "s2d_grads_combine",
     "s2d_multi_create", "s2d_multi_destroy", "s2d_multi_last_error", "s2d_multi_device_count", "s2d_multi_set_target",
     "s2d_multi_set_target_synthetic", "s2d_multi_init_splats", "s2d_multi_set_splats", "s2d_multi_get_splats",
@@ -289,6 +299,11 @@ def load_library(path=None):
     sig("s2d_get_alive", [vp, vp, vp])
     sig("s2d_prune", [vp, C.POINTER(_PruneConfig), vp])
     sig("s2d_grow", [vp, C.POINTER(_SeedConfig), vp, i32, vp])
+    sig("s2d_view_splats", [vp, C.POINTER(_ViewConfig), vp])
+    sig("s2d_render_view", [vp, C.POINTER(_ViewConfig), vp])
+    sig("s2d_render_view_device", [vp, C.POINTER(_ViewConfig), vp])
+    sig("s2d_view_release", [vp])
+    sig("s2d_debug_view_raster", [vp, C.POINTER(_ViewConfig), vp])
     sig("s2d_step", [vp, i32, u32, vp])
     sig("s2d_get_mse", [vp, vp])
     sig("s2d_bind_grads_device", [vp, vp])
@@ -701,6 +716,43 @@ class Trainer:
         moved = C.c_int32()
         self._ck(self.L.s2d_reseed(self._h, C.byref(cfg), int(max_moves), float(min_weight), C.byref(moved)))
         return moved.value
+
+    # -- view rendering (s2d_view_config, include/splat2d.h): the current splats at any zoom, crop and output size; read-only
+    # with respect to training
+    @staticmethod
+    def _view_config(out_width, out_height, origin=(0.0, 0.0), zoom=1.0, filter_var=0.0, samples=1, rgba8=False):
+        cfg = _ViewConfig()
+        cfg.struct_size = C.sizeof(_ViewConfig)
+        cfg.out_width, cfg.out_height = int(out_width), int(out_height)
+        cfg.origin_x, cfg.origin_y = float(origin[0]), float(origin[1])
+        cfg.zoom, cfg.filter_var, cfg.samples = float(zoom), float(filter_var), int(samples)
+        cfg.format = S2D_VIEW_RGBA8 if rgba8 else S2D_VIEW_RGBA32F
+        return cfg
+
+    def view_splats(self, out_width, out_height, origin=(0.0, 0.0), zoom=1.0, filter_var=0.0, samples=1, rgba8=False):
+        """The n records the view rasterises (the transform of include/splat2d.h; dead rows like live ones)."""
+        cfg = self._view_config(out_width, out_height, origin, zoom, filter_var, samples, rgba8)
+        a = np.zeros(self.n, dtype=SPLAT_DTYPE)
+        self._ck(self.L.s2d_view_splats(self._h, C.byref(cfg), _p(a)))
+        return a
+
+    def render_view(self, out_width, out_height, origin=(0.0, 0.0), zoom=1.0, filter_var=0.0, samples=1, rgba8=False):
+        """The window of the source plane that starts at `origin`, at `zoom` output pixels per source pixel, as an
+        (out_height, out_width, 4) array: float32 with .w = 1, or uint8 with alpha 255 (rgba8).  samples: 1, 2 or 4 per axis;
+        filter_var: variance, in output pixels^2, of a low-pass on the footprints."""
+        cfg = self._view_config(out_width, out_height, origin, zoom, filter_var, samples, rgba8)
+        a = np.zeros((int(out_height), int(out_width), 4), dtype=np.uint8 if rgba8 else np.float32)
+        self._ck(self.L.s2d_render_view(self._h, C.byref(cfg), _p(a)))
+        return a
+
+    def render_view_device(self, ptr, out_width, out_height, origin=(0.0, 0.0), zoom=1.0, filter_var=0.0, samples=1, rgba8=False):
+        """render_view into device memory (16-byte aligned for float32, 4-byte for rgba8), queued on the context's stream."""
+        cfg = self._view_config(out_width, out_height, origin, zoom, filter_var, samples, rgba8)
+        self._ck(self.L.s2d_render_view_device(self._h, C.byref(cfg), C.c_void_p(ptr) if ptr else None))
+
+    def view_release(self):
+        """Frees what views allocated; the next view allocates again."""
+        self._ck(self.L.s2d_view_release(self._h))
 
     def mse(self):
         v = C.c_double()

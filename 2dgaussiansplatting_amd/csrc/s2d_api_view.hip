@@ -1,0 +1,146 @@
+// s2d_api_view.hip -- view rendering through the C ABI (s2d_view_splats, s2d_render_view, s2d_render_view_device,
+// s2d_view_release; s2d_view.h).  A view reads the context's current splats and writes the caller's
+// buffer and the ViewScratch of the context; it goes through none of the events of s2d_sequence.h, because nothing that
+// training derived becomes stale: image0, the tile lists and their rebuild counters, the projection, the hand-over, the
+// status word, the squared-error ring and the density statistics are not touched.
+#include "s2d_ctx.h"
+
+#include "../../include/splat2d_test.h"
+
+namespace {
+
+// A failed allocation of the view's scratch: S2D_E_NOMEM when the device is out of memory, S2D_E_HIP otherwise.
+int view_alloc(s2d_ctx* c, hipError_t e, const char* what)
+{
+    if (e == hipSuccess) return S2D_OK;
+    (void)hipGetLastError();
+    if (e == hipErrorOutOfMemory) return fail(c, S2D_E_NOMEM, "no device memory for %s of the view", what);
+    return fail(c, S2D_E_HIP, "allocating %s of the view failed: %s", what, hipGetErrorString(e));
+}
+
+// Everything the view calls (`who`) refuse for the configuration or the context, before any device work (S2D_E_INVALID).
+int view_refused(s2d_ctx* c, const s2d_view_config* cfg, const char* who)
+{
+    if (!cfg) return fail(c, S2D_E_INVALID, "%s: NULL s2d_view_config", who);
+    if (const char* why = view_config_invalid(cfg->struct_size, (uint32_t)sizeof(s2d_view_config), cfg->out_width, cfg->out_height,
+                                              cfg->origin_x, cfg->origin_y, cfg->zoom, cfg->filter_var, cfg->samples, cfg->format,
+                                              S2D_VIEW_RGBA8))
+        return fail(c, S2D_E_INVALID, "%s: s2d_view_config: %s", who, why);
+    return whole_scene_refused(c, who, true); // (an alive set and reference order are no obstacle)
+}
+
+// The n x 9 records of the view into the scratch (queued).
+int view_records(s2d_ctx* c, const s2d_view_config* cfg, float** rows)
+{
+    if (int rc = view_alloc(c, c->view.rows((size_t)c->n, rows), "the records")) return rc;
+    SplatState::Arrays now;
+    S2D_HIP(c, c->state.current(&now));
+    S2D_HIP(c, launch_view_transform(now.splats, c->n, view_xform(cfg->origin_x, cfg->origin_y, cfg->zoom, cfg->filter_var, cfg->samples),
+                                     *rows, c->stream));
+    return S2D_OK;
+}
+
+// The raster kernel over the view's lists as they stand (queued).
+int view_raster(s2d_ctx* c, const s2d_view_config* cfg, void* out)
+{
+    const int s = view_samples(cfg->samples);
+    TileLists& lists = c->view.lists();
+    ViewRasterArgs a;
+    a.tile_off = lists.tile_off(); a.list = lists.list(); a.proj = c->view.proj(); a.out = out;
+    a.g = view_geometry(cfg->out_width, cfg->out_height, s);
+    a.out_width = cfg->out_width; a.samples = s; a.rgba8 = cfg->format == S2D_VIEW_RGBA8;
+    a.exact_exp = (c->cfg.flags & S2D_CFG_EXACT_EXP) != 0;
+    S2D_HIP(c, launch_view_raster(a, c->stream));
+    return S2D_OK;
+}
+
+// The whole view into `out` (device memory): records, projection, lists, raster.  Queued, but for the one wait of a list
+// build (the pair count) and for the waits of buffers that are replaced.
+int view_render(s2d_ctx* c, const s2d_view_config* cfg, void* out)
+{
+    const int s = view_samples(cfg->samples);
+    const Geometry g = view_geometry(cfg->out_width, cfg->out_height, s);
+    if (int rc = view_alloc(c, c->view.lists_for(g, (size_t)c->n, (c->cfg.flags & S2D_CFG_GENERIC_BINNING) != 0, c->stream), "the lists")) return rc;
+    float* rows = nullptr;
+    if (int rc = view_records(c, cfg, &rows)) return rc;
+    TileLists& lists = c->view.lists();
+    ProjectArgs p; // mode 0, margin 0: the exact rectangles; a dead row gets an empty one
+    p.splats = rows; p.held = c->state.held(); p.n = c->n; p.g = g; p.proj = c->view.proj(); p.counts = c->view.counts();
+    p.row_counts = lists.row_counts();
+    p.check = ContainmentCheck{c->view.rects(), nullptr};
+    S2D_HIP(c, launch_project(p, c->stream));
+    uint64_t total = 0;
+    S2D_HIP(c, lists.count(ListInput{c->view.rects(), c->view.counts(), c->view.offsets(), 0, c->n, c->d_scan_temp}, c->stream, &total));
+    if (total > c->ranges.budget() || total >= 0xFFFF0000ull)
+        return fail(c, S2D_E_NOMEM, "the view needs %llu (tile, splat) pairs, S2D_CHUNK_PAIRS allows %llu (views are not rendered by index ranges)",
+                    (unsigned long long)total, (unsigned long long)c->ranges.budget());
+    if (int rc = view_alloc(c, c->view.pairs_for(total, c->stream), "the (tile, splat) pairs")) return rc;
+    S2D_HIP(c, lists.finish(c->stream));
+    return view_raster(c, cfg, out);
+}
+
+size_t view_bytes(const s2d_view_config* cfg)
+{
+    return (size_t)cfg->out_width * (size_t)cfg->out_height * (cfg->format == S2D_VIEW_RGBA8 ? 4u : 16u);
+}
+
+} // namespace
+
+extern "C" {
+
+int s2d_view_splats(s2d_ctx* c, const s2d_view_config* cfg, s2d_splat* out_host)
+{
+    if (!c) return S2D_E_INVALID;
+    if (!out_host && c->n) return fail(c, S2D_E_INVALID, "s2d_view_splats: NULL output");
+    if (int rc = view_refused(c, cfg, "s2d_view_splats")) return rc;
+    if (int rc = use_device(c)) return rc;
+    float* rows = nullptr;
+    if (int rc = view_records(c, cfg, &rows)) return rc;
+    return read_back(c, out_host, rows, (size_t)c->n * sizeof(s2d_splat));
+}
+
+int s2d_render_view_device(s2d_ctx* c, const s2d_view_config* cfg, void* out_device)
+{
+    if (!c) return S2D_E_INVALID;
+    if (!out_device) return fail(c, S2D_E_INVALID, "s2d_render_view_device: NULL output");
+    if (int rc = view_refused(c, cfg, "s2d_render_view_device")) return rc;
+    if ((uintptr_t)out_device & (cfg->format == S2D_VIEW_RGBA8 ? 3u : 15u))
+        return fail(c, S2D_E_INVALID, "s2d_render_view_device: the buffer must be 16-byte (RGBA32F) or 4-byte (RGBA8) aligned");
+    if (int rc = use_device(c)) return rc;
+    return view_render(c, cfg, out_device);
+}
+
+int s2d_render_view(s2d_ctx* c, const s2d_view_config* cfg, void* out_host)
+{
+    if (!c) return S2D_E_INVALID;
+    if (!out_host) return fail(c, S2D_E_INVALID, "s2d_render_view: NULL output");
+    if (int rc = view_refused(c, cfg, "s2d_render_view")) return rc;
+    if (int rc = use_device(c)) return rc;
+    void* image = nullptr;
+    if (int rc = view_alloc(c, c->view.image(view_bytes(cfg), &image), "the image")) return rc;
+    if (int rc = view_render(c, cfg, image)) return rc;
+    return read_back(c, out_host, image, view_bytes(cfg));
+}
+
+// (include/splat2d_test.h) The raster kernel of the view alone, over the lists the last rendering of this configuration left.
+int s2d_debug_view_raster(s2d_ctx* c, const s2d_view_config* cfg, void* out_device)
+{
+    if (!c || !out_device) return S2D_E_INVALID;
+    if (int rc = view_refused(c, cfg, "s2d_debug_view_raster")) return rc;
+    if ((uintptr_t)out_device & (cfg->format == S2D_VIEW_RGBA8 ? 3u : 15u)) return fail(c, S2D_E_INVALID, "s2d_debug_view_raster: misaligned buffer");
+    if (!c->view.has_lists(view_geometry(cfg->out_width, cfg->out_height, view_samples(cfg->samples))))
+        return fail(c, S2D_E_STATE, "s2d_debug_view_raster: no lists of this raster grid (render the view first)");
+    if (int rc = use_device(c)) return rc;
+    return view_raster(c, cfg, out_device);
+}
+
+int s2d_view_release(s2d_ctx* c)
+{
+    if (!c) return S2D_E_INVALID;
+    if (!c->view.allocated()) return S2D_OK;
+    if (int rc = use_device(c)) return rc;
+    c->view.release(c->stream);
+    return S2D_OK;
+}
+
+} // extern "C"

@@ -16,6 +16,7 @@
 #include "s2d_seed.h"
 #include "s2d_sequence.h"
 #include "s2d_state.h"
+#include "s2d_view.h"
 
 using namespace s2d;
 
@@ -62,6 +63,7 @@ struct s2d_ctx {
     bool has_frozen = false;
     DevBuf<uint8_t> d_frozen;      // n bytes, non-zero = frozen; allocated by the first mask
     SeedScratch seed;              // the importance map of s2d_importance / s2d_seed_splats / s2d_reseed (s2d_seed.h), on first use
+    ViewScratch view;              // the records, lists and image of s2d_view_splats / s2d_render_view (s2d_view.h), on first use
     DevBuf<DeviceStatus> d_status;
     DevBuf<PairCounters> d_counters;
     // pinned host mirrors

@@ -41,6 +41,14 @@ struct Options {
     int restart_at = -1;        // press "Restart" before this iteration (main.cpp:828-831)
     bool quiet = false;
     std::string out_image;      // --out-image file.(png|ppm|s2di): image0 after the last iteration (main.cpp:794)
+    // View of the final splats instead of image0 (include/splat2d.h "view rendering"; one context only): with any of the four
+    // options --out-image is the RGBA8 view.  Defaults: the image's own size, origin 0,0, zoom 1, one sample, no filter; the
+    // filter's default is PROVISIONAL: nothing is claimed about the picture it gives.
+    bool have_view = false;
+    int view_w = 0, view_h = 0;           // --out-size WxH (0: the image's)
+    float view_x = 0.0f, view_y = 0.0f, view_zoom = 1.0f; // --out-view X,Y,ZOOM
+    int view_samples = 1;                 // --out-samples S: 1, 2 or 4 per axis
+    float view_filter = 0.0f;             // --out-filter F: variance of the low-pass in output pixels^2
     std::string overlay;        // --overlay file: image0 upscaled by overlay_scale with the splat debug drawing (main.cpp:441-485)
     int overlay_scale = 2;      // viewScale, main.cpp:822
     int overlay_stride = 1;     // draw every k-th splat
@@ -112,6 +120,7 @@ int usage()
     std::fprintf(stderr,
                  "usage: splat2d_train (--image file.s2di|.ppm|.png|.jpg | --synthetic WxH) [--splats N] [--iters K] [--batch B]\n"
                  "                     [--optimize-opacity [--opacity-from IT]] [--restart-at IT] [--out-image file.png|.ppm]\n"
+                 "                     [--out-size WxH] [--out-view X,Y,ZOOM] [--out-samples S] [--out-filter F]\n"
                  "                     [--overlay file [--overlay-scale S] [--overlay-stride K] [--overlay-vertices file]]\n"
                  "       splat2d_train --convert in.(s2di|ppm|png|jpg) out.(s2di|ppm|png)\n"
                  "                     [--load-checkpoint file] [--save-checkpoint file]\n"
@@ -128,6 +137,11 @@ int usage()
                  "  --relocate-every K: before iteration K, 2K, ... move the starved splats (summed T * alpha per pass below W) onto\n"
                  "    halves of the splats with the largest summed |dL/dpos|, from statistics of the S iterations before, at most\n"
                  "    F * splats at a time (one GPU only).  Defaults S = 10, F = 0.05, W = 0.5 are provisional: not measured yet.\n");
+    std::fprintf(stderr,
+                 "  --out-size WxH, --out-view X,Y,ZOOM, --out-samples S, --out-filter F: with any of them --out-image is a view of the\n"
+                 "    final splats instead of image0: the window of the source plane whose top-left corner is X,Y at ZOOM output pixels\n"
+                 "    per source pixel, W x H pixels, S x S samples per pixel (1, 2 or 4), a low-pass of variance F output pixels^2 on\n"
+                 "    the footprints (one GPU only).  Defaults: the image's size, 0,0,1, S = 1, F = 0 (provisional).\n");
     std::fprintf(stderr,
                  "  --seed-init edges|uniform: after init(), draw every splat's position from the target's edge map (uniform: under\n"
                  "    the full uniform share) and take its colour from the target there (one GPU only).\n"
@@ -255,6 +269,10 @@ int main(int argc, char** argv)
         else if (a == "--opacity-from") o.opacity_from = std::atoi(next("--opacity-from"));
         else if (a == "--restart-at") o.restart_at = std::atoi(next("--restart-at"));
         else if (a == "--out-ppm" || a == "--out-image") o.out_image = next("--out-image");
+        else if (a == "--out-size") { if (std::sscanf(next("--out-size"), "%dx%d", &o.view_w, &o.view_h) != 2) return usage(); o.have_view = true; }
+        else if (a == "--out-view") { if (std::sscanf(next("--out-view"), "%f,%f,%f", &o.view_x, &o.view_y, &o.view_zoom) != 3) return usage(); o.have_view = true; }
+        else if (a == "--out-samples") { o.view_samples = std::atoi(next("--out-samples")); o.have_view = true; }
+        else if (a == "--out-filter") { o.view_filter = (float)std::atof(next("--out-filter")); o.have_view = true; }
         else if (a == "--overlay") o.overlay = next("--overlay");
         else if (a == "--overlay-scale") o.overlay_scale = std::atoi(next("--overlay-scale"));
         else if (a == "--overlay-stride") o.overlay_stride = std::atoi(next("--overlay-stride"));
@@ -343,6 +361,13 @@ int main(int argc, char** argv)
     }
     if (o.relocate_every > 0 && (o.gpus > 1 || std::getenv("S2D_TRAIN_FORCE_MULTI"))) {
         std::fprintf(stderr, "--relocate-every works on one context: the multi-device handle has no relocation\n");
+        return 2;
+    }
+    if (o.have_view && (o.view_w < 0 || o.view_h < 0 || (o.view_samples != 1 && o.view_samples != 2 && o.view_samples != 4) || !(o.view_zoom > 0.0f) ||
+                        !(o.view_filter >= 0.0f)))
+        return usage();
+    if (o.have_view && (o.gpus > 1 || std::getenv("S2D_TRAIN_FORCE_MULTI"))) {
+        std::fprintf(stderr, "--out-size, --out-view, --out-samples and --out-filter work on one context: the multi-device handle has no views\n");
         return 2;
     }
     if (!o.seed_init.empty() && o.seed_init != "edges" && o.seed_init != "uniform") return usage();
@@ -616,12 +641,33 @@ int main(int argc, char** argv)
             exit_code = 1;
         }
     }
-    if (!o.out_image.empty() || !o.overlay.empty()) {
+    if (o.have_view && !o.out_image.empty()) { // the RGBA8 view of the final splats (s2d_render_view)
+        s2d_view_config vc;
+        std::memset(&vc, 0, sizeof(vc));
+        vc.struct_size = sizeof(vc);
+        vc.out_width = o.view_w > 0 ? o.view_w : W;
+        vc.out_height = o.view_h > 0 ? o.view_h : H;
+        vc.origin_x = o.view_x; vc.origin_y = o.view_y; vc.zoom = o.view_zoom;
+        vc.filter_var = o.view_filter; vc.samples = o.view_samples; vc.format = S2D_VIEW_RGBA8;
+        std::vector<uint8_t> rgba((size_t)vc.out_width * (size_t)vc.out_height * 4);
+        CK(s2d_render_view(S.ctx, &vc, rgba.data()));
+        s2dio::Image8 im;
+        im.w = vc.out_width;
+        im.h = vc.out_height;
+        im.rgb.resize((size_t)im.w * im.h * 3);
+        for (size_t p = 0; p < (size_t)im.w * im.h; p++)
+            for (int c = 0; c < 3; c++) im.rgb[p * 3 + c] = rgba[p * 4 + c];
+        if (!s2dio::save_image(o.out_image, im)) {
+            std::fprintf(stderr, "cannot write %s\n", o.out_image.c_str());
+            exit_code = 1;
+        }
+    }
+    if ((!o.out_image.empty() && !o.have_view) || !o.overlay.empty()) {
         std::vector<float> image0((size_t)W * H * 4);
         CK(S.forward());
         CK(S.get_image(image0.data())); // tex0->upload(image0), main.cpp:794
         const s2dio::Image8 im = s2dio::quantise(image0, W, H);
-        if (!o.out_image.empty() && !s2dio::save_image(o.out_image, im)) {
+        if (!o.out_image.empty() && !o.have_view && !s2dio::save_image(o.out_image, im)) {
             std::fprintf(stderr, "cannot write %s\n", o.out_image.c_str());
             exit_code = 1;
         }

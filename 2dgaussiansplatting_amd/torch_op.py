@@ -95,6 +95,20 @@ class SplatRenderer:
             raise ValueError("render() takes a contiguous float32 tensor of shape (%d, 9) on %s" % (self.n, self.device))
         return _Render.apply(splats, self, bool(density_stats))
 
+    def render_view(self, splats, out_width, out_height, origin=(0.0, 0.0), zoom=1.0, filter_var=0.0, samples=1, rgba8=False):
+        """A view of `splats` (Trainer.render_view: any zoom, crop and output size) -> (out_height, out_width, 4) tensor on
+        the renderer's device, float32 with .w = 1 or uint8 with alpha 255.  No autograd: a view has no backward pass.  The
+        parameters are uploaded the way render() uploads them, so image0 and the hand-over are theirs afterwards."""
+        if not (isinstance(splats, torch.Tensor) and splats.dtype == torch.float32 and splats.device == self.device and
+                tuple(splats.shape) == (self.n, 9) and splats.is_contiguous()):
+            raise ValueError("render_view() takes a contiguous float32 tensor of shape (%d, 9) on %s" % (self.n, self.device))
+        self._check_stream()
+        with torch.no_grad():
+            self._draw(splats.detach())
+            out = torch.empty((int(out_height), int(out_width), 4), dtype=torch.uint8 if rgba8 else torch.float32, device=self.device)
+            self.trainer.render_view_device(out.data_ptr(), out_width, out_height, origin, zoom, filter_var, samples, rgba8)
+        return out
+
     def density(self):
         """-> ((n, 3) float32 tensor: sum |dL/dpos.x|, sum |dL/dpos.y|, sum T * alpha per splat over the accumulated
         statistics passes, and the number of those passes); queued on the renderer's stream like everything else."""

@@ -461,6 +461,55 @@ int s2d_prune(s2d_ctx* ctx, const s2d_prune_config* cfg, int32_t* pruned);
  * count == 0, gives S2D_OK with 0. */
 int s2d_grow(s2d_ctx* ctx, const s2d_seed_config* cfg, const int32_t* ids_host, int32_t count, int32_t* grown);
 
+/* ---- view rendering: the current splats at any zoom, crop and output size (no counterpart in the reference, which draws
+ * image0 at the target's size only, main.cpp:414-546).  A VIEW is an axis-aligned window of the source
+ * plane, drawn at a uniform zoom into a buffer of the caller's own size, with optional supersampling, an optional low-pass on
+ * the footprints, and float or 8-bit output.  It is read-only with respect to training: image0, the tile lists and their
+ * rebuild counters, the projection, the forward -> backward hand-over, the status word, the squared-error ring and the density
+ * statistics are not touched, and a context trains on after a view -- or after a refused one -- as if nothing had been asked.
+ *
+ * The records a view rasterises, all arithmetic fp32, one operation at a time, s = samples (0 meaning 1):
+ *   zr = zoom * (float)s;  fr = filter_var * (float)(s * s);
+ *   pos' = ((pos.x - origin_x) * zr, (pos.y - origin_y) * zr);  ax = sx * zr;  ay = sy * zr;
+ *   fr == 0:   sx' = ax, sy' = ay, opacity' = opacity;
+ *   otherwise: sx' = sqrtf(ax * ax + fr), sy' = sqrtf(ay * ay + fr), opacity' = opacity * ((ax * ay) / (sx' * sy'));
+ *   rot and colour unchanged.  Nothing is clamped.
+ * They are rasterised by the reference's forward loop (main.cpp:414-546), in index order, the dead rows of an alive set left
+ * out, on a grid of (out_width * s) x (out_height * s); S2D_CFG_EXACT_EXP is honoured, S2D_CFG_FP16_IMAGES and
+ * S2D_CFG_COUNT_PAIRS play no part (a view is computed in fp32 and counts nothing).  The identity view (origin 0, zoom 1,
+ * out = width x height, no filter, one sample) is image0 of s2d_forward byte for byte.
+ * Resolve: s = 2: the output pixel is ((p00 + p01) + (p10 + p11)) * 0.25f per channel, p_rc at row r, column c of its 2 x 2
+ * block of the grid; s = 4: that resolve applied twice; .w = 1.  No supersampled image exists in memory.
+ * S2D_VIEW_RGBA8: per channel (uint8)(min(max(c, 0), 1) * 255.0f + 0.5f), NaN -> 0; alpha 255.
+ * filter_var is defined exactly; nothing is claimed about the picture it gives.
+ *
+ * S2D_E_INVALID, before any device work: a NULL config or output; a wrong struct_size; sizes, zoom, origin, filter_var,
+ * samples or format outside the ranges below; a device buffer that is not 16-byte (RGBA32F) or 4-byte (RGBA8) aligned; a slab
+ * context (row_begin / row_end) or one with a held set (s2d_halo_commit).  S2D_E_NOMEM: the view's (tile, splat) pairs exceed
+ * S2D_CHUNK_PAIRS (views are not rendered by index ranges), or an allocation failed.  There is no S2D_E_STATE: a view needs
+ * splats, not a target or a forward pass.  The multi-device handle (s2d_multi) has no views: out of scope here. */
+#define S2D_VIEW_RGBA32F 0u   /* out: out_height * out_width * 4 floats, .w = 1 */
+#define S2D_VIEW_RGBA8   1u   /* out: out_height * out_width * 4 bytes,  .w = 255 */
+typedef struct s2d_view_config {
+    uint32_t struct_size;            /* = sizeof(s2d_view_config) */
+    int32_t  out_width, out_height;  /* >= 1; out_* * samples <= 65536 */
+    float    origin_x, origin_y;     /* source coordinates of the output's top-left corner; pixel i covers [i, i+1) */
+    float    zoom;                   /* output pixels per source pixel; finite, > 0 */
+    float    filter_var;             /* >= 0, finite: variance in OUTPUT pixels^2 of an isotropic low-pass; 0 = none */
+    int32_t  samples;                /* per axis: 0 -> 1; 1, 2 or 4 */
+    uint32_t format;                 /* S2D_VIEW_RGBA32F, S2D_VIEW_RGBA8 */
+} s2d_view_config;
+/* The n_splats records the view rasterises (dead rows are transformed like live ones). */
+int s2d_view_splats(s2d_ctx* ctx, const s2d_view_config* cfg, s2d_splat* out_host);
+/* The view into host memory; complete on return. */
+int s2d_render_view(s2d_ctx* ctx, const s2d_view_config* cfg, void* out_host);
+/* The view into DEVICE memory, queued on the context's stream (the host waits once, for the pair count of the list build). */
+int s2d_render_view_device(s2d_ctx* ctx, const s2d_view_config* cfg, void* out_device);
+/* Views allocate on first use and keep what they allocated -- the records, a projection and tile lists of the raster grid
+ * (re-created when the grid's size changes, grown with the pair count), the device image behind s2d_render_view -- until this
+ * call or s2d_destroy; the next view allocates again. */
+int s2d_view_release(s2d_ctx* ctx);
+
 /* `iters` whole iterations (main.cpp:414-809): forward, backward, Adam, MSE.  mse_out (may be NULL) receives
  * iters doubles: the value the reference prints for each iteration (main.cpp:796-807).  For a slab context the
  * values are this slab's sum of squared errors divided by (H*W*3), i.e. partial MSEs that add up over slabs.

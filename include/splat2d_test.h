@@ -28,6 +28,11 @@ int s2d_test_exclusive_scan(int32_t device, uint32_t* data, int64_t n, uint64_t*
 /* The tile lists the raster kernels walk, for inspection: offsets has tiles+1 entries. */
 int s2d_debug_get_tile_lists(s2d_ctx* ctx, int32_t* tiles_x, int32_t* tiles_y, uint32_t* offsets,
                              int64_t offsets_capacity, uint32_t* list, int64_t list_capacity);
+/* The raster kernel of a view alone (csrc/s2d_view.hip), queued on the context's stream over the lists that the last
+ * s2d_render_view[_device] of the SAME configuration left, into out_device: what tools/gpu_view_timing.py puts between two
+ * events.  S2D_E_STATE when the view's lists are of another raster grid or were never built; the refusals of
+ * s2d_render_view_device otherwise.  The splats must not have changed since that rendering. */
+int s2d_debug_view_raster(s2d_ctx* ctx, const s2d_view_config* cfg, void* out_device);
 
 /* Failure injection for the multi-device handle: rank `rank`'s worker thread stops answering right after it has queued
  * the raster launch of iteration `iteration` (before its gradient exchange) for `milliseconds` (< 0: until another rank has
