@@ -17,8 +17,9 @@ HOST_DIR = os.path.join(PKG_DIR, "host")
 TRAIN_BIN = os.path.join(LIB_DIR, "splat2d_train")
 
 HIP_SOURCES = ["s2d_api.hip", "s2d_api_loss.hip", "s2d_api_placement.hip", "s2d_api_optim.hip", "s2d_api_alive.hip", "s2d_api_rows.hip", "s2d_api_view.hip", "s2d_api_test.hip", "s2d_sequence.hip", "s2d_lists.hip", "s2d_state.hip", "s2d_context.hip", "s2d_scan_sort.hip", "s2d_binning.hip", "s2d_tilelists.hip", "s2d_raster.hip",
+               "s2d_raster_ranges.hip", "s2d_raster_gradient.hip", "s2d_raster_det.hip", "s2d_raster_reference.hip",
                "s2d_loss.hip", "s2d_seed.hip", "s2d_view.hip", "s2d_optim.hip", "s2d_optim_controls.hip", "s2d_alive.hip", "s2d_halo.hip", "s2d_multi.hip"]
-HIP_HEADERS = ["s2d_device.h", "s2d_math.h", "s2d_owned.h", "s2d_lists.h", "s2d_state.h", "s2d_context.h", "s2d_ctx.h", "s2d_sequence.h", "s2d_ranges.h", "s2d_density.h", "s2d_loss.h", "s2d_seed.h", "s2d_seed_math.h", "s2d_optim_rates.h", "s2d_adam.h", "s2d_alive.h", "s2d_view.h", "s2d_view_math.h"]
+HIP_HEADERS = ["s2d_device.h", "s2d_math.h", "s2d_walk.h", "s2d_walk_backward.h", "s2d_owned.h", "s2d_lists.h", "s2d_state.h", "s2d_context.h", "s2d_ctx.h", "s2d_sequence.h", "s2d_ranges.h", "s2d_density.h", "s2d_loss.h", "s2d_seed.h", "s2d_seed_math.h", "s2d_optim_rates.h", "s2d_adam.h", "s2d_alive.h", "s2d_view.h", "s2d_view_math.h"]
 
 # -ffp-contract=off: the kernels keep the reference's evaluation order (no FMA contraction) wherever a
 # discrete decision or the framebuffer depends on it; fp32 divide/sqrt stay correctly rounded (hipcc default).
@@ -33,13 +34,13 @@ HIPCC_FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off"
 
 
 def kernel_source_digest():
-    """sha256[:16] over the sources of the raster kernels (s2d_raster.hip and the two headers it is made of) with
-    comments and whitespace removed: what ties a recorded profile of the dominant kernel (profiles/traffic.json) to the
-    code it measured (bench.py drops the figure when the digests differ)."""
+    """sha256[:16] over the sources of the fused raster kernel (s2d_raster.hip and the four headers it is made of, and no
+    other raster unit) with comments and whitespace removed: what ties a recorded profile of the dominant kernel
+    (profiles/traffic.json) to the code it measured (bench.py drops the figure when the digests differ)."""
     import hashlib
     import re
     h = hashlib.sha256()
-    for name in ("s2d_device.h", "s2d_math.h", "s2d_raster.hip"):
+    for name in ("s2d_device.h", "s2d_math.h", "s2d_walk.h", "s2d_walk_backward.h", "s2d_raster.hip"):
         if os.path.exists(os.path.join(CSRC, name)):
             text = open(os.path.join(CSRC, name)).read()
             text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)

@@ -199,7 +199,8 @@ hipError_t launch_tile_lists_from_rows(const uint32_t* entries, const uint32_t* 
                                        Geometry g, uint32_t* chunk_base, uint32_t* workspace, uint32_t* tile_off, uint32_t* list,
                                        hipStream_t stream);
 
-// raster (s2d_raster.hip)
+// raster (s2d_raster.hip and the units launch_raster hands a pass to: s2d_raster_ranges.hip, s2d_raster_gradient.hip,
+// s2d_raster_det.hip)
 // Deterministic gradient accumulation (S2D_CFG_DETERMINISTIC): instead of float atomics every tile stores its
 // partial gradient of a splat into the slot offsets[splat] + (position of the tile in the splat's emission
 // rectangle), stamped with the iteration and announced in the splat's `touched` word; a gather kernel then sums each
@@ -219,7 +220,7 @@ enum class RasterPass {
     Forward,
     Backward,
     Fused,         // forward + backward walk of every tile in one launch (same results as the two launches above)
-    ForwardRange,  // index-range rendering (scenes beyond one set of lists; s2d_raster.hip "chunked", s2d_sequence.hip
+    ForwardRange,  // index-range rendering (scenes beyond one set of lists; s2d_raster_ranges.hip, s2d_sequence.hip
     BackwardRange, // chunked_forward / chunked_backward): the lists are those of ONE index range of the splats
 };
 // What a raster pass works on; a member left at its default is not used.
@@ -236,7 +237,7 @@ struct RasterArgs {
     // the pixels of the slab; the walk ACCUMULATES into it next to the gradients (the STATS kernels)
     float* density = nullptr;
     // forward -> backward walk: lane masks and splat indices of the entries the forward walk executed, compacted to the
-    // front of each tile's list range, and their number per tile (s2d_raster.hip forward_tile)
+    // front of each tile's list range, and their number per tile (s2d_walk.h forward_tile)
     unsigned long long* wave_masks = nullptr;
     uint32_t* exec_list = nullptr;
     uint32_t* tile_exec = nullptr;
@@ -267,7 +268,7 @@ struct RasterArgs {
     bool need_opacity_grad = false;
 };
 hipError_t launch_raster(RasterPass pass, const RasterArgs& a, hipStream_t stream);
-// Reference-order backward pass (S2D_CFG_REFERENCE_ORDER; s2d_raster.hip, behind everything else).  The walk stores the
+// Reference-order backward pass (S2D_CFG_REFERENCE_ORDER; s2d_raster_reference.hip).  The walk stores the
 // nine addends of every (executed pair, pixel of its tile) into the pair's slot -- the slot numbering of deterministic
 // mode: offsets[splat] + position of the tile in the splat's binned rectangle, stamped with `now` -- and, unless the loss
 // is the caller's (a.upstream), the pixel's squared error; the sum kernel then adds each splat's terms to a.grads in

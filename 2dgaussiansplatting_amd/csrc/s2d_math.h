@@ -309,7 +309,7 @@ S2D_HD float gauss_at(float px, float py, float pos_x, float pos_y, float a, flo
 
 // ----------------------------------------------------------------------------------------------
 // The backward loop body of one (splat, pixel), main.cpp:601-709, with the reference's own expressions and association
-// (S2D_CFG_REFERENCE_ORDER; the fast path regroups some of them, s2d_raster.hip backward_tile).  Every `/` is one IEEE
+// (S2D_CFG_REFERENCE_ORDER; the fast path regroups some of them, s2d_walk_backward.h backward_tile).  Every `/` is one IEEE
 // division; glm::dot(vec3, vec3) is (x + y) + z.
 // ----------------------------------------------------------------------------------------------
 struct RefSplat { // what the body reads of the splat: inv_cov (main.cpp:561-565; b = [1][0], c = [0][1]), cov_of's trig, raw scales

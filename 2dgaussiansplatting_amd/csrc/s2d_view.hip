@@ -1,11 +1,11 @@
 // s2d_view.hip -- view rendering: the record transform and the view raster kernel (s2d_view.h).
 //
-// view_raster_kernel is the forward walk of s2d_raster.hip (forward_tile, main.cpp:414-546) over the lists of a view's raster
-// grid, with everything that serves training taken out: no hand-over to a backward walk, no retirement hint, no status word,
-// no abort stamp, no counters.  The walk is restated here instead of shared through a template flag, so that no instruction of
-// a training kernel depends on this file; the arithmetic of a (pixel, entry) body, the staging of the lane masks and tile
-// retirement are the forward walk's, operation for operation (-ffp-contract=off), which is what makes the identity view the
-// bytes of image0.  One 256-thread workgroup per 16 x 16 tile of the grid, four wave64 of 8 x 8 pixels, lane = 8 * row + column.
+// view_raster_kernel is the forward walk (s2d_walk.h forward_tile, main.cpp:414-546) over the lists of a view's raster grid, with
+// everything that serves training taken out: no hand-over to a backward walk, no retirement hint, no status word, no abort
+// stamp, no counters.  The loop is its own; what it is made of is the walk's (s2d_walk.h): the staging of the lane masks
+// (stage_masks), the body of a (pixel, entry) (blend_entry) and tile retirement (block_any_alive), operation for operation
+// (-ffp-contract=off), which is what makes the identity view the bytes of image0.  One 256-thread workgroup per 16 x 16 tile of
+// the grid, four wave64 of 8 x 8 pixels, lane = 8 * row + column.
 //
 // Without the hand-over a batch's masks and index words are dead behind its last barrier, so they need one copy instead of
 // two and no index words at all: 5.1 KB of LDS per workgroup against the forward walk's 18.9 KB.
@@ -16,72 +16,11 @@
 // memory, and an RGBA8 view writes 4 bytes per output pixel.  Lane exchange rather than LDS: it runs once per tile behind a
 // walk of hundreds of entries, needs no barrier and keeps the workgroup's LDS at the walk's.
 #include "s2d_view.h"
+#include "s2d_walk.h"
 
 namespace s2d {
 
 namespace {
-
-constexpr int B = kRasterBatch;
-static_assert(B == 64, "lane l of a wave holds the mask of batch entry l");
-constexpr int kWaveW = 8;
-constexpr int kWaveH = 64 / kWaveW;
-constexpr int kWavesX = kTile / kWaveW;
-
-struct f2 {
-    float x, y;
-};
-__device__ __forceinline__ f2 operator+(f2 a, f2 b) { return f2{a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ f2 operator-(f2 a, f2 b) { return f2{a.x - b.x, a.y - b.y}; }
-__device__ __forceinline__ f2 operator*(f2 a, f2 b) { return f2{a.x * b.x, a.y * b.y}; }
-__device__ __forceinline__ f2 operator*(f2 a, float b) { return f2{a.x * b, a.y * b}; }
-__device__ __forceinline__ f2 operator*(float a, f2 b) { return f2{a * b.x, a * b.y}; }
-__device__ __forceinline__ f2& operator+=(f2& a, f2 b) { a = a + b; return a; }
-__device__ __forceinline__ f2 mk2(float a, float b)
-{
-    f2 r;
-    r.x = a;
-    r.y = b;
-    return r;
-}
-
-__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int src_lane)
-{
-    const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)v, src_lane);
-    const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(v >> 32), src_lane);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-template <bool EXACT>
-__device__ __forceinline__ float gauss_of(float d2, bool* nonzero)
-{
-    if (EXACT) {
-        *nonzero = true;
-        return expf_ref(-0.5f * d2); // main.cpp:51, :527
-    }
-    return gauss_pow8(d2, nonzero);
-}
-
-// Staging thread (se = entry, sub = 0..3) evaluates tile rows sub*4 .. sub*4+3 of entry se and deposits the bits into the
-// per-(wave, entry) lane masks, s_mask[wave][entry] as 2 x 32-bit words each (s2d_raster.hip stage_masks).
-__device__ __forceinline__ void stage_masks(uint32_t* s_mask32, int se, int sub, const float4& q0, const float4& q1, int begY,
-                                            int endY, int y_tile, int x_tile, int W, int row_end)
-{
-    uint32_t rm[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int yy = y_tile + sub * 4 + k;
-        rm[k] = 0;
-        if (yy < row_end) rm[k] = row_mask16(q0.x, q0.y, q0.z, q0.w, q1.x, begY, endY, yy, x_tile, W);
-    }
-    const int wy = sub >> 1, half = sub & 1;
-#pragma unroll
-    for (int wx = 0; wx < 2; wx++) {
-        const int sh = 8 * wx;
-        const uint32_t word = ((rm[0] >> sh) & 0xFFu) | (((rm[1] >> sh) & 0xFFu) << 8) | (((rm[2] >> sh) & 0xFFu) << 16) |
-                              (((rm[3] >> sh) & 0xFFu) << 24);
-        s_mask32[((wy * 2 + wx) * B + se) * 2 + half] = word;
-    }
-}
 
 // LDS of the view walk: per-entry record as the forward walk lays it out -- [0] pos.x, pos.y, a, b  [1] b, d, col_r, col_g
 // [2] col_b, opacity, -, - -- and one copy of the lane masks.
@@ -90,14 +29,6 @@ struct ViewShared {
     unsigned long long mask[4 * B]; // [wave][entry]
     int4 alive;                     // per wave: does it still have a live pixel
 };
-
-__device__ __forceinline__ bool block_any_alive(int4* flags, int w, int lane, unsigned long long alive_mask)
-{
-    if (lane == 0) reinterpret_cast<int*>(flags)[w] = alive_mask != 0ull ? 1 : 0;
-    __syncthreads();
-    const int4 f = *flags;
-    return ((f.x | f.y) | (f.z | f.w)) != 0;
-}
 
 // One level of the resolve: the 2 x 2 block whose top-left lane is this one, DX / DY = the lane distance of its right / lower
 // neighbour.  Every lane runs it; the value is the block's only in its top-left lane.
@@ -133,7 +64,7 @@ __global__ __launch_bounds__(256) void view_raster_kernel(const uint32_t* __rest
     if (tile >= g.num_tiles) return;
     const int tx = tile % g.tiles_x, ty = tile / g.tiles_x;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int lx = (w % kWavesX) * kWaveW + (lane % kWaveW), ly = (w / kWavesX) * kWaveH + (lane / kWaveW);
+    const int lx = (w % kWavesX) * kWaveW + (lane % kWaveW), ly = (w / kWavesX) * kWaveH + (lane / kWaveW); // pixel_of_thread
     const int x = tx * kTile + lx, y = ty * kTile + ly;
     const bool inside = x < g.W && y < g.row_end;
     const f2 pxy = mk2((float)x + 0.5f, (float)y + 0.5f); // pixel centre, main.cpp:523
@@ -167,20 +98,10 @@ __global__ __launch_bounds__(256) void view_raster_kernel(const uint32_t* __rest
                 cand &= cand - 1ull;
                 const unsigned long long act = readlane_u64(my_mask, e) & alive_mask; // visited (main.cpp:511-514), not cut off (:520)
                 if (act == 0ull) continue;
-                // Branch-free body: lanes outside `act` run the same instructions with alpha forced to 0, which makes
-                // c += (T*c)*0 and T *= 1 exact no-ops.
-                const float4 q0 = s.rec[e][0], q1 = s.rec[e][1], q2 = s.rec[e][2];
-                const f2 v = pxy - mk2(q0.x, q0.y);                          // main.cpp:523-524
-                const f2 m = mk2(q0.z, q0.w) * v.x + mk2(q1.x, q1.y) * v.y;  // inv_cov * v
-                const f2 vm = v * m;
-                bool nonzero;
-                const float G = gauss_of<EXACT>(vm.x + vm.y, &nonzero);      // main.cpp:526-527
-                const unsigned long long on = act & __ballot(nonzero);
-                const float alpha = __builtin_amdgcn_inverse_ballot_w64(on) ? G * q2.y : 0.0f;
-                crg += (T * mk2(q1.z, q1.w)) * alpha;                        // main.cpp:529-530: (T*c)*alpha
-                cb += T * q2.x * alpha;                                      // main.cpp:531
-                T *= (1.0f - alpha);                                         // main.cpp:533
-                alive_mask &= __ballot(!(T < kMinThroughput));               // main.cpp:520, for the next splat
+                const Blended bl = blend_entry<EXACT>(s.rec[e][0], s.rec[e][1], s.rec[e][2], pxy, act, crg, cb, T, alive_mask);
+                cb = bl.cb;
+                T = bl.T;
+                alive_mask = bl.alive_mask;
             }
         }
         // (also the barrier behind which the next batch may overwrite the records and masks)

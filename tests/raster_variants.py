@@ -1,4 +1,5 @@
-"""The table of raster kernel variants: one row per instantiation of the five raster templates of csrc/s2d_raster.hip, with
+"""The table of raster kernel variants: one row per instantiation of the five raster templates of the raster units
+(csrc/s2d_raster.hip, s2d_raster_ranges.hip, s2d_raster_gradient.hip; the templates' walks: s2d_walk.h, s2d_walk_backward.h), with
 the public recipe that launches it.  A helper module: tests/test_raster_variants_cpu.py holds the table to the compiler's own
 list of kernels, tests/test_gpu_raster_variants.py runs every row against the oracle, tools/gpu_variant_coverage.py shows from a
 kernel trace that every row was dispatched.

@@ -102,7 +102,7 @@ def test_colour_and_alpha_derivatives_of_the_blend(trial):
 
 
 def test_regrouped_forms_used_by_the_kernel_are_identities():
-    """s2d_raster.hip evaluates 0.5*alpha*(2a vx + (b+c) vy) as alpha*(a vx + b vy); DESIGN.md section 5 also quotes
+    """s2d_walk_backward.h (backward_tile) evaluates 0.5*alpha*(2a vx + (b+c) vy) as alpha*(a vx + b vy); DESIGN.md section 5 also quotes
     the u/w identities.  Check them as algebra."""
     for _ in range(100):
         vx, vy = RNG.uniform(-20, 20, 2)

@@ -1,4 +1,4 @@
-"""The forward walk hands the backward walk the entries it executed, compacted (s2d_raster.hip forward_tile).
+"""The forward walk hands the backward walk the entries it executed, compacted (s2d_walk.h forward_tile).
 
 A counting context (count_pairs=True) keeps the older hand-over -- every staged entry at its list position, the backward
 walk going through the tile's whole list -- so the two paths are two implementations of the same sums.  With

@@ -1,4 +1,4 @@
-"""Every raster kernel variant of the dispatch (csrc/s2d_raster.hip, launch_raster) against the oracle: one test per row of
+"""Every raster kernel variant of the dispatch (csrc/s2d_raster.hip launch_raster and the units it hands a pass to) against the oracle: one test per row of
 tests/raster_variants.py, the kernel's name as its id.  A row is launched through its public recipe and held to the yardstick
 the suite already has for that kind of pass; nothing here is a new tolerance:
   * forward rows: image0 byte-equal to the oracle's (fp16 rows: rounded as test_forward_and_gradients_random_sweep rounds;

@@ -1,7 +1,7 @@
-"""The table of raster kernel variants (tests/raster_variants.py) against the compiler's own list: the raster unit is
-cross-compiled for gfx950 (no GPU needed) and every `s2d::raster_*` kernel it holds must have exactly one row.  A template flag
-added to the dispatch of csrc/s2d_raster.hip makes this fail until its variants have rows, and with rows they get their test
-against the oracle (tests/test_gpu_raster_variants.py)."""
+"""The table of raster kernel variants (tests/raster_variants.py) against the compiler's own list: the raster units
+(csrc/s2d_raster*.hip) are cross-compiled for gfx950 (no GPU needed) and every `s2d::raster_*` kernel they hold together must
+have exactly one row and come out of exactly one unit.  A template flag added to a unit's dispatch makes this fail until its
+variants have rows, and with rows they get their test against the oracle (tests/test_gpu_raster_variants.py)."""
 import collections
 import importlib
 import importlib.util
@@ -40,6 +40,7 @@ def test_table_rows_are_well_formed():
 @pytest.mark.skipif(not _have_hipcc(), reason="hipcc is not installed: the raster unit cannot be cross-compiled")
 def test_table_equals_the_compiled_raster_kernels():
     KR = _kernel_resources()
+    # (without a unit: all raster units together; ValueError for a kernel that two of them emit)
     compiled = {n for n in KR.report(os.path.join(O.ROOT, "2dgaussiansplatting_amd", "csrc")) if n.startswith("s2d::raster_")}
     twice = sorted(n for n, k in collections.Counter(RV.NAMES).items() if k > 1)
     missing, surplus = sorted(compiled - set(RV.NAMES)), sorted(set(RV.NAMES) - compiled)

@@ -4,6 +4,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 import oracle_lib as O
 
 TOOL = os.path.join(O.ROOT, "tools", "profile_summarise.py")
@@ -98,7 +100,7 @@ def test_variant_coverage_names_the_rows_a_trace_never_dispatched(tmp_path):
 
 
 def test_one_residual_correction_gives_the_ieee_quotient():
-    """csrc/s2d_raster.hip::div_by_recip: q = S*r; q += (S - den*q)*r with r a 1-ulp reciprocal.  What its comment claims, on
+    """csrc/s2d_walk_backward.h::div_by_recip: q = S*r; q += (S - den*q)*r with r a 1-ulp reciprocal.  What its comment claims, on
     three operand populations of the backward blend's range incl. den = 1e-15 and quotients placed next to rounding midpoints
     (tools/check_recip_division.py, numpy emulation of the fma; the full 3 x 10^8-trial run is profiles/r04/r04_recip_division_check.txt):
     the bare estimate S*r misses the IEEE quotient often, one correction leaves at most a ~1e-7 sliver, and with a correctly
@@ -116,3 +118,17 @@ def test_one_residual_correction_gives_the_ieee_quotient():
             assert c0 > 40_000, (kind, name, c0)          # the bare estimate misses the IEEE quotient in > 10 % of the cases
             assert c1 <= 2 and c2 <= c1 + 1 and c3 <= c1 + 1, (kind, name, t[name])
         assert t["r = RN(1/den)"][1] == 0, (kind, t)       # correctly rounded reciprocal: one correction is IEEE division
+
+
+def test_kernel_resources_pools_units_and_refuses_a_kernel_emitted_twice():
+    """tools/kernel_resources.py pooled: the kernels of several units of one tree as one table (a kernel is matched by name
+    whichever unit holds it), and a name that two units emit is an error."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(O.ROOT, "tools", "kernel_resources.py"))
+    KR = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(KR)
+    units = {"a.hip": {"s2d::k<true>": 1}, "b.hip": {"s2d::k<false>": 2}, "c.hip": {"s2d::k<true>": 3}, "gone.hip": {}}
+    what = lambda csrc, unit: units[unit]
+    assert KR.pooled(what, "csrc", ["a.hip", "gone.hip", "b.hip"]) == {"s2d::k<true>": 1, "s2d::k<false>": 2}
+    with pytest.raises(ValueError, match="a.hip and by c.hip"):
+        KR.pooled(what, "csrc", ["a.hip", "b.hip", "c.hip"])

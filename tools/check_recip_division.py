@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Container tool (CPU, numpy): how often does  q = num*r; q += (num - den*q)*r  (exact residual, fused multiply-adds) differ
 from IEEE fp32 division, with r the rounded reciprocal of den or one ulp beside it (v_rcp_f32 is a 1-ulp instruction), after
-0, 1, 2 and 3 corrections?  (csrc/s2d_raster.hip div_by_recip applies ONE.)
+0, 1, 2 and 3 corrections?  (csrc/s2d_walk_backward.h div_by_recip applies ONE.)
 
 Operands as in the backward blend (main.cpp:627-628): den = fl(fl(1 - alpha) + 1e-15) with alpha = G * o in [0, 1] -- so den is
 1e-15 (alpha == 1) or a multiple of 2^-24 in [2^-24, 1] -- and num = S = final - colour, |num| <~ 1.  Three populations:

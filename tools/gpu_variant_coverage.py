@@ -7,8 +7,8 @@
 Reads the Kernel_Name column of every *_kernel_trace.csv given (a directory is searched for them; one file per process),
 brings the names into the form tools/kernel_resources.py prints (demangled, no argument list, no `void`), and lists every
 row of the table with the number of its dispatches.  Exit status 1 if a row was never dispatched, or a `s2d::raster_*`
-kernel without a row was.  The kernels of the raster unit that are no template instantiations (gather_*, reference_*,
-sqerr_finalize) are listed for information only.
+kernel without a row was.  The kernels of the raster units that are no template instantiations (gather_* of s2d_raster_det.hip,
+reference_* of s2d_raster_reference.hip, sqerr_finalize) are listed for information only.
 """
 import collections
 import csv

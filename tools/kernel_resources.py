@@ -1,7 +1,7 @@
 """Register / LDS / occupancy report of the raster kernels from the gfx950 cross-compile, and its comparison between two trees.
 
-    python tools/kernel_resources.py report [csrc_dir] [unit.hip] > new.json     (no GPU needed: hipcc -Rpass-analysis=kernel-resource-usage;
-                                                                  unit: default s2d_raster.hip, e.g. s2d_loss.hip)
+    python tools/kernel_resources.py report [csrc_dir] [unit.hip ...] > new.json (no GPU needed: hipcc -Rpass-analysis=kernel-resource-usage;
+                                                                  units: default the raster units, s2d_raster*.hip)
     python tools/kernel_resources.py compare old.json new.json
     python tools/kernel_resources.py asm old_csrc_dir [new_csrc_dir] [unit.hip ...]
 
@@ -9,12 +9,14 @@ compare: every kernel instantiation of `old` must be in `new` with the same SGPR
 (exit status 1 otherwise); instantiations only `new` has are listed.  A kernel that gained a trailing template flag is
 matched with its `false` instantiation (`k<a, b>` of old == `k<a, b, false>` of new), and one that lost a trailing flag
 with the old `false` instantiation (`k<a, b, false>` of old == `k<a, b>` of new): adding or dropping a defaulted flag renames
-the symbol and must change nothing else.  The order in which variants are instantiated has moved the register allocation of
-unrelated kernels before (s2d_raster.hip, with_variant), which is what this is run for.
+the symbol and must change nothing else.  An instantiation added to a unit has moved the register allocation of unrelated
+kernels of that unit before, which is what this is run for.
 asm: the device assembly (--offload-device-only -S) of every kernel of the old tree against the same kernel of the new one,
-comments dropped and local labels unnumbered: which are instruction for instruction the same (exit status 1 if one is not).
-Of the named translation units, by default of every one the build compiles (_build.HIP_SOURCES); a unit that only one of
-the trees has counts as one without kernels there.
+comments dropped and local labels unnumbered: which are instruction for instruction the same (exit status 1 if one is not);
+kernels only the new tree has are listed.
+The kernels of the named translation units -- by default of every one the build compiles (_build.HIP_SOURCES) -- are pooled per
+tree, so a kernel is matched by its name whichever unit holds it; a unit that a tree does not have counts as one without kernels
+there, and a kernel name that two units of one tree emit is an error.
 """
 import json
 import os
@@ -51,6 +53,21 @@ def _renamed(new, name):
     return got
 
 
+def raster_units():
+    return [u for u in _build_flags()[0].HIP_SOURCES if u.startswith("s2d_raster")]
+
+
+def pooled(what, csrc, units):
+    """what = assembly or report: its results for several translation units of one tree as one {kernel: ...}."""
+    out, unit_of = {}, {}
+    for u in units:
+        for name, v in what(csrc, u).items():
+            if name in out:
+                raise ValueError("%s: emitted by %s and by %s" % (name, unit_of[name], u))
+            out[name], unit_of[name] = v, u
+    return out
+
+
 def assembly(csrc, source="s2d_raster.hip"):
     """{kernel: its instructions as text} of one translation unit."""
     build, flags = _build_flags()
@@ -81,11 +98,18 @@ def compare_assembly(old, new, label=""):
     print("%s%d of %d kernels of the old tree instruction for instruction the same (%d kernels in the new tree)" % (label, same, len(old), len(new)))
     for n in changed:
         print("  CHANGED: " + n)
+    for n in sorted(n for n in new if n not in old and not any(_renamed(new, o) is new[n] for o in old)):
+        print("  new: " + n)
     return not changed
 
 
-def report(csrc, source="s2d_raster.hip"):
+def report(csrc, source=None):
+    """{kernel: its resources} of one translation unit; without a unit, of the raster units together (pooled)."""
+    if source is None:
+        return pooled(report, csrc, raster_units())
     build, flags = _build_flags()
+    if not os.path.exists(os.path.join(csrc, source)):
+        return {}
     with tempfile.TemporaryDirectory() as tmp:
         cmd = [build.hipcc()] + flags + ["-I", os.path.join(ROOT, "include"), "-c", os.path.join(csrc, source), "-o",
                                          os.path.join(tmp, "out.o"), "-Rpass-analysis=kernel-resource-usage"]
@@ -126,17 +150,16 @@ def compare(old, new):
 
 if __name__ == "__main__":
     if len(sys.argv) >= 2 and sys.argv[1] == "report":
-        units = [a for a in sys.argv[2:] if a.endswith(".hip")] or ["s2d_raster.hip"]
+        units = [a for a in sys.argv[2:] if a.endswith(".hip")] or raster_units()  # (as report() without a unit)
         dirs = [a for a in sys.argv[2:] if not a.endswith(".hip")]
         csrc = dirs[0] if dirs else os.path.join(ROOT, "2dgaussiansplatting_amd", "csrc")
-        json.dump(report(csrc, units[0]), sys.stdout, indent=1, sort_keys=True)
+        json.dump(pooled(report, csrc, units), sys.stdout, indent=1, sort_keys=True)
     elif len(sys.argv) == 4 and sys.argv[1] == "compare":
         sys.exit(0 if compare(json.load(open(sys.argv[2])), json.load(open(sys.argv[3]))) else 1)
     elif len(sys.argv) >= 3 and sys.argv[1] == "asm":
         dirs = [a for a in sys.argv[3:] if not a.endswith(".hip")]
         units = [a for a in sys.argv[3:] if a.endswith(".hip")] or _build_flags()[0].HIP_SOURCES
         new = dirs[0] if dirs else os.path.join(ROOT, "2dgaussiansplatting_amd", "csrc")
-        same = [compare_assembly(assembly(sys.argv[2], u), assembly(new, u), "%-20s " % u) for u in units]
-        sys.exit(0 if all(same) else 1)
+        sys.exit(0 if compare_assembly(pooled(assembly, sys.argv[2], units), pooled(assembly, new, units)) else 1)
     else:
         sys.exit(__doc__)
