@@ -820,7 +820,7 @@ class Trainer:
 
 
 class MultiTrainer:
-    """Several GPUs behind one handle (s2d_multi_*, csrc/s2d_multi.hip): the Trainer's state and step() on a list of
+    """Several GPUs behind one handle (s2d_multi_*, csrc/s2d_multi.h and its units): the Trainer's state and step() on a list of
     devices -- row slabs and, inside the library, either slab ownership with peer-to-peer copies of the shared
     gradient rows (default) or replicated state with an RCCL all-reduce of all gradients (replicated=True).
     share_gpu: every rank on devices[0] (a rehearsal where there are fewer GPUs than ranks)."""

@@ -2,7 +2,7 @@
 // Each starts empty, lets go in its destructor, cannot be copied and converts to the raw handle, so launch sites read
 // as with plain pointers.  Whoever lets a buffer go (release(), a second alloc(), a growing reserve(), the destructor)
 // makes sure first that no stream still uses it, and that its device is current.
-// Host-only and self-contained (s2d_multi.hip includes it in the host simulation of the tests, without s2d_device.h).
+// Host-only and self-contained (the s2d_multi units include it in the host simulation of the tests, without s2d_device.h).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,9 +1,9 @@
-// hip/hip_runtime.h of the HOST SIMULATION (tests/hostsim): the handful of runtime calls csrc/s2d_multi.hip makes, backed by
+// hip/hip_runtime.h of the HOST SIMULATION (tests/hostsim): the handful of runtime calls the csrc/s2d_multi units make, backed by
 // threads instead of a GPU, so that its host protocol -- worker threads, the breakable barrier, pairwise sequence counters,
 // stream event waits, two send buffers -- can run under ThreadSanitizer on a machine without a GPU.
 //
 // TEST INFRASTRUCTURE ONLY.  Not a HIP implementation and not a CPU fallback of the product: only tests/hostsim builds
-// against it (g++ -x c++ -fsanitize=thread -I tests/hostsim/include ... csrc/s2d_multi.hip).
+// against it (g++ -x c++ -fsanitize=thread -I tests/hostsim/include ... csrc/s2d_multi*.hip).
 //
 // Semantics that matter to the protocol under test, and that the simulation keeps:
 //  * a stream is an in-order queue run by its own thread; every *Async call only enqueues (copies too -- stricter than HIP,

@@ -1,4 +1,4 @@
-// rccl/rccl.h of the HOST SIMULATION (tests/hostsim): the five RCCL entry points csrc/s2d_multi.hip resolves at run time.
+// rccl/rccl.h of the HOST SIMULATION (tests/hostsim): the five RCCL entry points csrc/s2d_multi_replicated.hip resolves at run time.
 // TEST INFRASTRUCTURE ONLY (see hip/hip_runtime.h beside it).  sim_rccl.cpp builds into a library with SONAME librccl.so.1.
 #pragma once
 

@@ -1,4 +1,4 @@
-// multi_sim_main.cpp -- scenarios that drive csrc/s2d_multi.hip (compiled as host C++ against tests/hostsim) under
+// multi_sim_main.cpp -- scenarios that drive the csrc/s2d_multi units (compiled as host C++ against tests/hostsim) under
 // ThreadSanitizer: 2 / 4 / 8 rank threads, slab ownership and replicated state side by side over more than 200 iterations
 // with hold-set refreshes, a get_splats / set_splats in the middle, ranks slowed down at random, an injected rank that
 // stops answering (both schemes), and a non-finite stop.  Prints one line per scenario; exit code 0 = all good.

@@ -1,4 +1,4 @@
-// sim_ctx.cpp -- the single-device context (include/splat2d.h s2d_*) as csrc/s2d_multi.hip uses it, simulated on the host:
+// sim_ctx.cpp -- the single-device context (include/splat2d.h s2d_*) as the csrc/s2d_multi units use it, simulated on the host:
 // every call queues an operation on the context's simulated stream, and the operations compute with the CPU oracle
 // (oracle/s2d_oracle.c) -- forward / backward over the rank's rows for the splats it holds, the Adam step on them, the row
 // gathers / scatters / the rank-ordered combine of slab ownership.  TEST INFRASTRUCTURE ONLY: this is how the multi-device

@@ -1,4 +1,4 @@
-// sim_hip.cpp -- the host simulation of the HIP runtime calls csrc/s2d_multi.hip makes (see include/hip/hip_runtime.h).
+// sim_hip.cpp -- the host simulation of the HIP runtime calls the csrc/s2d_multi units make (see include/hip/hip_runtime.h).
 // TEST INFRASTRUCTURE ONLY.
 #include <hip/hip_runtime.h>
 

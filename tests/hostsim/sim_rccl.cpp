@@ -1,4 +1,4 @@
-// sim_rccl.cpp -- host simulation of the RCCL calls csrc/s2d_multi.hip makes (SONAME librccl.so.1: the library finds it
+// sim_rccl.cpp -- host simulation of the RCCL calls csrc/s2d_multi_replicated.hip makes (SONAME librccl.so.1: the library finds it
 // already mapped, as it finds PyTorch's bundled RCCL).  TEST INFRASTRUCTURE ONLY.
 //
 // ncclAllReduce queues, on the caller's stream, an operation that waits until every rank of the group has queued its share

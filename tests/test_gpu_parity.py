@@ -1858,7 +1858,7 @@ def test_multi_device_handle_reports_a_rank_that_stopped_answering(world, replic
 @pytest.mark.parametrize("world", [2, 4])
 def test_multi_device_handle_free_running_exchange_with_ranks_at_different_speeds(world):
     """Between refreshes the rank threads of a slab-ownership handle do not meet: they order the gradient exchange with
-    pairwise sequence counters, stream event waits and two send buffers (csrc/s2d_multi.hip exchange_grads).  Make the
+    pairwise sequence counters, stream event waits and two send buffers (csrc/s2d_multi_ownership.hip exchange_grads).  Make the
     ranks run at different speeds -- one rank's thread sleeps a few milliseconds at several iterations, another at
     others -- across three refresh intervals: parameters, moments and trace must equal those of the replicated scheme
     (whose sums are formed in the same rank order) bit for bit."""

@@ -1,8 +1,9 @@
-"""The host protocol of the multi-device handle (2dgaussiansplatting_amd/csrc/s2d_multi.hip: worker threads, the breakable
-barrier, pairwise sequence counters, stream event waits, two send buffers, the stop / abort path) under ThreadSanitizer,
-without a GPU.
+"""The host protocol of the multi-device handle (2dgaussiansplatting_amd/csrc: s2d_multi.hip the entry points, s2d_multi_run.hip
+the worker threads and the watchdog, s2d_multi_ownership.hip pairwise sequence counters, stream event waits and two send
+buffers, s2d_multi_replicated.hip the all-reduce, s2d_multi_stop.hip the breakable barrier and the stop / abort path) under
+ThreadSanitizer, without a GPU.
 
-s2d_multi.hip has no kernels: it is compiled here as plain C++ against tests/hostsim -- a thread-backed stand-in for the
+These units have no kernels: they are compiled here as plain C++ against tests/hostsim -- a thread-backed stand-in for the
 handful of HIP / RCCL calls it makes (a stream = an in-order queue with its own thread, an event = a sequence number,
 hipStreamWaitEvent = a wait for the record that was the latest when it was called) -- with the single-device contexts
 simulated on the CPU oracle.  tests/hostsim/multi_sim_main.cpp then runs 2 / 4 / 8 rank threads through 230 iterations with
@@ -22,7 +23,9 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SIM = os.path.join(HERE, "hostsim")
-MULTI = os.path.join(os.path.dirname(HERE), "2dgaussiansplatting_amd", "csrc", "s2d_multi.hip")
+CSRC = os.path.join(os.path.dirname(HERE), "2dgaussiansplatting_amd", "csrc")
+MULTI = [os.path.join(CSRC, name) for name in ("s2d_multi.hip", "s2d_multi_run.hip", "s2d_multi_ownership.hip", "s2d_multi_replicated.hip",
+                                               "s2d_multi_stop.hip")]
 # ROCm's clang carries a ThreadSanitizer runtime that knows pthread_cond_clockwait (what libstdc++'s
 # condition_variable::wait_for calls); gcc 11's does not and reports every timed wait as a double lock
 CLANG = "/opt/rocm/lib/llvm/bin/clang++"
@@ -68,19 +71,20 @@ def test_multi_device_host_protocol_is_race_free_and_fails_informatively(sim):
 def test_the_harness_sees_a_seeded_race(sim, tmp_path):
     """Sensitivity check: with ONE send buffer instead of two (a rank gathers iteration k + 1 while a neighbour may still be
     copying iteration k) ThreadSanitizer must report the race between the gather and the peer copy."""
-    src = open(MULTI).read()
     needle = "const int b = (int)((seq - 1u) & 1u);"
+    holders = [unit for unit in MULTI if needle in open(unit).read()]
+    assert len(holders) == 1
+    src = open(holders[0]).read()
     assert src.count(needle) == 1
     src = src.replace(needle, "const int b = 0;")
-    root = os.path.dirname(HERE)
-    src = src.replace('#include "../../include/', '#include "%s/include/' % root)
     mut = tmp_path / "s2d_multi_mutant.hip"
     mut.write_text(src)
+    units = [str(mut) if unit == holders[0] else unit for unit in MULTI]   # the mutant beside the unmodified others
     exe = str(tmp_path / "multi_sim_mutant")
     build = os.path.join(SIM, "_build")
     subprocess.check_call([_tsan_compiler(), "-O1", "-g", "-std=c++17", "-fPIC", "-pthread", "-fsanitize=thread", "-I" + os.path.join(SIM, "include"),
-                           "-I" + os.path.dirname(MULTI),  # the mutant lies outside the tree: s2d_owned.h is beside the original
-                           "-o", exe, os.path.join(SIM, "multi_sim_main.cpp"), os.path.join(SIM, "sim_ctx.cpp"), "-x", "c++", str(mut), "-x", "none",
+                           "-I" + CSRC,  # the mutant lies outside the tree: the headers it includes are beside the original
+                           "-o", exe, os.path.join(SIM, "multi_sim_main.cpp"), os.path.join(SIM, "sim_ctx.cpp"), "-x", "c++"] + units + ["-x", "none",
                            os.path.join(build, "s2d_oracle.o"), "-L" + build, "-lsimhip", "-Wl,--no-as-needed", "-l:librccl.so.1", "-Wl,--as-needed",
                            "-ldl", "-lm", "-Wl,--disable-new-dtags", "-Wl,-rpath," + build])
     p = _run(exe, "quick")
