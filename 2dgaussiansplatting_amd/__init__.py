@@ -81,6 +81,7 @@ class _ViewConfig(C.Structure):
 
 
 S2D_VIEW_RGBA32F, S2D_VIEW_RGBA8 = 0, 1
+S2D_VIEW_BWD_FROM_TARGET = 0x8  # s2d_view_backward_device / s2d_view_grads: the buffer is a target, dL = view - target
 
 
 class _OptimConfig(C.Structure):
@@ -122,6 +123,7 @@ ABI_SYMBOLS = [
     "s2d_set_optim", "s2d_optim_rates_at", "s2d_set_frozen", "s2d_set_frozen_device",
     "s2d_set_alive", "s2d_set_alive_device", "s2d_get_alive", "s2d_prune", "s2d_grow",
     "s2d_view_splats", "s2d_render_view", "s2d_render_view_device", "s2d_view_release",
+    "s2d_view_backward_device", "s2d_view_grads",
     "s2d_last_error", "s2d_test_sincos", "s2d_test_sort_pairs", "s2d_test_exclusive_scan",
     "s2d_test_sort_tile_offsets", "s2d_debug_get_tile_lists", "s2d_debug_view_raster",
     "s2d_halo_masks", "s2d_halo_commit", "s2d_rows_gather", "s2d_rows_scatter", "s2d_grads_combine",
@@ -303,6 +305,8 @@ def load_library(path=None):
     sig("s2d_render_view", [vp, C.POINTER(_ViewConfig), vp])
     sig("s2d_render_view_device", [vp, C.POINTER(_ViewConfig), vp])
     sig("s2d_view_release", [vp])
+    sig("s2d_view_backward_device", [vp, C.POINTER(_ViewConfig), vp, u32])
+    sig("s2d_view_grads", [vp, C.POINTER(_ViewConfig), vp, u32, vp])
     sig("s2d_debug_view_raster", [vp, C.POINTER(_ViewConfig), vp])
     sig("s2d_step", [vp, i32, u32, vp])
     sig("s2d_get_mse", [vp, vp])
@@ -749,6 +753,30 @@ class Trainer:
         """render_view into device memory (16-byte aligned for float32, 4-byte for rgba8), queued on the context's stream."""
         cfg = self._view_config(out_width, out_height, origin, zoom, filter_var, samples, rgba8)
         self._ck(self.L.s2d_render_view_device(self._h, C.byref(cfg), C.c_void_p(ptr) if ptr else None))
+
+    def _view_bwd_flags(self, from_target, skip_opacity_grad):
+        if skip_opacity_grad is None:
+            skip_opacity_grad = self.lean_backward and not self.optimize_opacity
+        return (S2D_VIEW_BWD_FROM_TARGET if from_target else 0) | (S2D_BWD_SKIP_OPACITY_GRAD if skip_opacity_grad else 0)
+
+    def view_backward_device(self, ptr, out_width, out_height, origin=(0.0, 0.0), zoom=1.0, filter_var=0.0, samples=1,
+                             from_target=False, skip_opacity_grad=None):
+        """Backward pass through the view (s2d_view_backward_device): from dL/d(view) at `ptr` (device, out_height x out_width
+        RGBA32F, 16-byte aligned, .w ignored) -- or, from_target, from a target of the view's size, dL = view - target -- ADDED
+        into the gradient buffer, queued on the context's stream; skip_opacity_grad as backward()."""
+        cfg = self._view_config(out_width, out_height, origin, zoom, filter_var, samples)
+        self._ck(self.L.s2d_view_backward_device(self._h, C.byref(cfg), C.c_void_p(ptr) if ptr else None,
+                                                 self._view_bwd_flags(from_target, skip_opacity_grad)))
+
+    def view_grads(self, ptr, out_width, out_height, origin=(0.0, 0.0), zoom=1.0, filter_var=0.0, samples=1,
+                   from_target=False, skip_opacity_grad=None):
+        """The same pass stopped before the adjoint of the record transform: the n gradients of the records view_splats()
+        returns (s2d_view_grads); the gradient buffer is not touched."""
+        cfg = self._view_config(out_width, out_height, origin, zoom, filter_var, samples)
+        a = np.zeros(self.n, dtype=SPLAT_DTYPE)
+        self._ck(self.L.s2d_view_grads(self._h, C.byref(cfg), C.c_void_p(ptr) if ptr else None,
+                                       self._view_bwd_flags(from_target, skip_opacity_grad), _p(a)))
+        return a
 
     def view_release(self):
         """Frees what views allocated; the next view allocates again."""

@@ -3,6 +3,8 @@
 // buffer and the ViewScratch of the context; it goes through none of the events of s2d_sequence.h, because nothing that
 // training derived becomes stale: image0, the tile lists and their rebuild counters, the projection, the hand-over, the
 // status word, the squared-error ring and the density statistics are not touched.
+// The backward pass through a view (s2d_view_backward_device, s2d_view_grads) is as read-only, but for the
+// gradient buffer it adds into -- which no event of s2d_sequence.h watches either: s2d_backward_image_grads accumulates the same way.
 #include "s2d_ctx.h"
 
 #include "../../include/splat2d_test.h"
@@ -54,9 +56,9 @@ int view_raster(s2d_ctx* c, const s2d_view_config* cfg, void* out)
     return S2D_OK;
 }
 
-// The whole view into `out` (device memory): records, projection, lists, raster.  Queued, but for the one wait of a list
-// build (the pair count) and for the waits of buffers that are replaced.
-int view_render(s2d_ctx* c, const s2d_view_config* cfg, void* out)
+// The records, the projection and the lists of the view.  Queued, but for the one wait of a list build (the pair count) and
+// for the waits of buffers that are replaced.
+int view_lists(s2d_ctx* c, const s2d_view_config* cfg)
 {
     const int s = view_samples(cfg->samples);
     const Geometry g = view_geometry(cfg->out_width, cfg->out_height, s);
@@ -76,7 +78,48 @@ int view_render(s2d_ctx* c, const s2d_view_config* cfg, void* out)
                     (unsigned long long)total, (unsigned long long)c->ranges.budget());
     if (int rc = view_alloc(c, c->view.pairs_for(total, c->stream), "the (tile, splat) pairs")) return rc;
     S2D_HIP(c, lists.finish(c->stream));
+    return S2D_OK;
+}
+
+// The whole view into `out` (device memory): records, projection, lists, raster.
+int view_render(s2d_ctx* c, const s2d_view_config* cfg, void* out)
+{
+    if (int rc = view_lists(c, cfg)) return rc;
     return view_raster(c, cfg, out);
+}
+
+// Everything the gradient calls (`who`) refuse, before any device work (S2D_E_INVALID).
+int view_gradient_refused(s2d_ctx* c, const s2d_view_config* cfg, const float* src, uint32_t flags, const char* who)
+{
+    if (int rc = view_refused(c, cfg, who)) return rc;
+    if (cfg->format != S2D_VIEW_RGBA32F) return fail(c, S2D_E_INVALID, "%s: the gradient of a view is RGBA32F (format S2D_VIEW_RGBA32F)", who);
+    if (!src) return fail(c, S2D_E_INVALID, "%s: NULL image gradient (or target)", who);
+    if ((uintptr_t)src & 15u) return fail(c, S2D_E_INVALID, "%s: the image gradient (or target) must be 16-byte aligned", who);
+    if (flags & ~(S2D_VIEW_BWD_FROM_TARGET | S2D_BWD_SKIP_OPACITY_GRAD)) return fail(c, S2D_E_INVALID, "%s: unknown flags %#x", who, flags);
+    if (c->cfg.flags & S2D_CFG_COUNT_PAIRS) return fail(c, S2D_E_INVALID, "%s: not available with S2D_CFG_COUNT_PAIRS", who);
+    if (c->scratch.reference_order()) return fail(c, S2D_E_INVALID, "%s: not available with S2D_CFG_REFERENCE_ORDER", who);
+    return S2D_OK;
+}
+
+// The gradients of the view's records from `src` (dL/d(view), or the target with S2D_VIEW_BWD_FROM_TARGET) into the scratch's
+// n x 9 buffer (queued behind the list build): records, projection, lists, view_gradient_kernel, deterministic mode's gather.
+int view_record_grads(s2d_ctx* c, const s2d_view_config* cfg, const float* src, uint32_t flags, float** grads)
+{
+    if (int rc = view_lists(c, cfg)) return rc;
+    const int s = view_samples(cfg->samples);
+    TileLists& lists = c->view.lists();
+    ViewGradientArgs a;
+    if (int rc = view_alloc(c, c->view.gradient_for((size_t)c->n, c->scratch.deterministic(), c->stream, &a), "the gradient pass")) return rc;
+    a.tile_off = lists.tile_off(); a.list = lists.list(); a.proj = c->view.proj();
+    a.src = reinterpret_cast<const float4*>(src);
+    a.g = view_geometry(cfg->out_width, cfg->out_height, s);
+    a.out_width = cfg->out_width; a.samples = s;
+    a.exact_exp = (c->cfg.flags & S2D_CFG_EXACT_EXP) != 0;
+    a.need_opacity_grad = !(flags & S2D_BWD_SKIP_OPACITY_GRAD);
+    a.from_target = (flags & S2D_VIEW_BWD_FROM_TARGET) != 0;
+    S2D_HIP(c, launch_view_gradient(a, c->stream));
+    *grads = a.grads;
+    return S2D_OK;
 }
 
 size_t view_bytes(const s2d_view_config* cfg)
@@ -120,6 +163,32 @@ int s2d_render_view(s2d_ctx* c, const s2d_view_config* cfg, void* out_host)
     if (int rc = view_alloc(c, c->view.image(view_bytes(cfg), &image), "the image")) return rc;
     if (int rc = view_render(c, cfg, image)) return rc;
     return read_back(c, out_host, image, view_bytes(cfg));
+}
+
+int s2d_view_backward_device(s2d_ctx* c, const s2d_view_config* cfg, const float* dview_or_target_device, uint32_t flags)
+{
+    if (!c) return S2D_E_INVALID;
+    if (int rc = view_gradient_refused(c, cfg, dview_or_target_device, flags, "s2d_view_backward_device")) return rc;
+    if (int rc = use_device(c)) return rc;
+    float* record_grads = nullptr;
+    if (int rc = view_record_grads(c, cfg, dview_or_target_device, flags, &record_grads)) return rc;
+    SplatState::Arrays now;
+    S2D_HIP(c, c->state.current(&now));
+    S2D_HIP(c, launch_view_adjoint(now.splats, c->state.held(), c->n,
+                                   view_xform(cfg->origin_x, cfg->origin_y, cfg->zoom, cfg->filter_var, cfg->samples), record_grads,
+                                   c->d_grads, c->stream));
+    return S2D_OK;
+}
+
+int s2d_view_grads(s2d_ctx* c, const s2d_view_config* cfg, const float* dview_or_target_device, uint32_t flags, s2d_splat* dview_records_host)
+{
+    if (!c) return S2D_E_INVALID;
+    if (!dview_records_host && c->n) return fail(c, S2D_E_INVALID, "s2d_view_grads: NULL output");
+    if (int rc = view_gradient_refused(c, cfg, dview_or_target_device, flags, "s2d_view_grads")) return rc;
+    if (int rc = use_device(c)) return rc;
+    float* record_grads = nullptr;
+    if (int rc = view_record_grads(c, cfg, dview_or_target_device, flags, &record_grads)) return rc;
+    return read_back(c, dview_records_host, record_grads, (size_t)c->n * sizeof(s2d_splat));
 }
 
 // (include/splat2d_test.h) The raster kernel of the view alone, over the lists the last rendering of this configuration left.

@@ -30,15 +30,6 @@ struct ViewShared {
     int4 alive;                     // per wave: does it still have a live pixel
 };
 
-// One level of the resolve: the 2 x 2 block whose top-left lane is this one, DX / DY = the lane distance of its right / lower
-// neighbour.  Every lane runs it; the value is the block's only in its top-left lane.
-template <int DX, int DY>
-__device__ __forceinline__ float resolve_level(float v)
-{
-    const float h = v + __shfl_xor(v, DX, 64);  // p00 + p01 (p10 + p11 in the lane below)
-    return (h + __shfl_xor(h, DY, 64)) * 0.25f; // view_resolve4
-}
-
 } // namespace
 
 __global__ __launch_bounds__(256) void view_transform_kernel(const float* __restrict__ splats, int n, ViewXform x,

@@ -9,6 +9,14 @@
 //   fr == 0:  sx' = ax, sy' = ay, opacity' = opacity
 //   else:     sx' = sqrtf(ax * ax + fr), sy' = sqrtf(ay * ay + fr), opacity' = opacity * ((ax * ay) / (sx' * sy'))
 //   rot and colour unchanged; nothing is clamped.
+//
+// view_row_adjoint (view gradients): the gradient g' with respect to a view record, taken back to the source
+// record.  With k = (ax * ay) / (sx' * sy') as above, every line one fp32 operation after the other, left to right:
+//   g_pos = g'_pos * zr,  g_rot = g'_rot,  g_col = g'_col
+//   fr == 0:  g_sx = g'_sx * zr,  g_sy = g'_sy * zr,  g_op = g'_op
+//   else:     g_op = g'_op * k,   t = (g'_op * opacity) * k
+//             g_sx = zr * (g'_sx * (ax / sx') + t * (fr / (ax * (sx' * sx'))))      (d sx'/d ax = ax / sx',
+//             g_sy = zr * (g'_sy * (ay / sy') + t * (fr / (ay * (sy' * sy'))))       d opacity'/d ax = opacity * k * fr / (ax sx'^2))
 #pragma once
 
 #include "s2d_math.h"
@@ -56,6 +64,32 @@ S2D_HD void view_row(const ViewXform& x, const float* in9, float* out9)
     out9[6] = in9[6];
     out9[7] = in9[7];
     out9[8] = opacity;
+}
+
+// The gradient g9_view with respect to view_row(x, in9) as the gradient with respect to in9 (the header comment has the order).
+S2D_HD void view_row_adjoint(const ViewXform& x, const float* in9, const float* g9_view, float* g9_out)
+{
+    g9_out[0] = g9_view[0] * x.zr;
+    g9_out[1] = g9_view[1] * x.zr;
+    g9_out[4] = g9_view[4];
+    g9_out[5] = g9_view[5];
+    g9_out[6] = g9_view[6];
+    g9_out[7] = g9_view[7];
+    if (x.fr == 0.0f) {
+        g9_out[2] = g9_view[2] * x.zr;
+        g9_out[3] = g9_view[3] * x.zr;
+        g9_out[8] = g9_view[8];
+        return;
+    }
+    const float ax = in9[2] * x.zr;
+    const float ay = in9[3] * x.zr;
+    const float sx = sqrt_f32(ax * ax + x.fr);
+    const float sy = sqrt_f32(ay * ay + x.fr);
+    const float k = (ax * ay) / (sx * sy);
+    const float t = (g9_view[8] * in9[8]) * k;
+    g9_out[2] = x.zr * (g9_view[2] * (ax / sx) + t * (x.fr / (ax * (sx * sx))));
+    g9_out[3] = x.zr * (g9_view[3] * (ay / sy) + t * (x.fr / (ay * (sy * sy))));
+    g9_out[8] = g9_view[8] * k;
 }
 
 // One channel of a 2 x 2 block of samples, p_rc at row r, column c; samples = 4 applies it twice.

@@ -9,6 +9,9 @@
         loss = (img[..., :3] - target).abs().sum()
         loss.backward()                           # splats.grad: the hand-derived backward walk, from dL/d(img)
 
+render_view() is the same for a view of the splats (any zoom, crop and output size, supersampled): s2d_render_view_device
+forward, s2d_view_backward_device backward.
+
 Both directions are the library's HIP kernels (s2d_forward, s2d_backward_image_grads) on device pointers of torch's
 tensors: nothing crosses the host and nothing synchronises.  The library and torch touch the same buffers, so they work
 on ONE stream -- the one that is current when the renderer is created (as distributed.HipHaloOps documents); a call
@@ -97,16 +100,27 @@ class SplatRenderer:
 
     def render_view(self, splats, out_width, out_height, origin=(0.0, 0.0), zoom=1.0, filter_var=0.0, samples=1, rgba8=False):
         """A view of `splats` (Trainer.render_view: any zoom, crop and output size) -> (out_height, out_width, 4) tensor on
-        the renderer's device, float32 with .w = 1 or uint8 with alpha 255.  No autograd: a view has no backward pass.  The
-        parameters are uploaded the way render() uploads them, so image0 and the hand-over are theirs afterwards."""
+        the renderer's device, float32 with .w = 1 or uint8 with alpha 255.  The parameters are uploaded the way render()
+        uploads them, so image0 and the hand-over are theirs afterwards.
+        With splats.requires_grad the float view is differentiable with respect to `splats`: its backward is the library's
+        pass through the view (s2d_view_backward_device) -- coarse-to-fine, crop and supersampled losses written in torch.  An
+        8-bit view has no gradient: rgba8 with requires_grad raises.  Without requires_grad nothing is recorded."""
         if not (isinstance(splats, torch.Tensor) and splats.dtype == torch.float32 and splats.device == self.device and
                 tuple(splats.shape) == (self.n, 9) and splats.is_contiguous()):
             raise ValueError("render_view() takes a contiguous float32 tensor of shape (%d, 9) on %s" % (self.n, self.device))
         self._check_stream()
+        view = (int(out_width), int(out_height), (float(origin[0]), float(origin[1])), float(zoom), float(filter_var), int(samples))
+        if splats.requires_grad:
+            if rgba8:
+                raise ValueError("render_view(rgba8=True) is not differentiable: render the float view of a tensor that requires grad")
+            return _RenderView.apply(splats, self, view)
         with torch.no_grad():
-            self._draw(splats.detach())
-            out = torch.empty((int(out_height), int(out_width), 4), dtype=torch.uint8 if rgba8 else torch.float32, device=self.device)
-            self.trainer.render_view_device(out.data_ptr(), out_width, out_height, origin, zoom, filter_var, samples, rgba8)
+            return self._draw_view(splats.detach(), view, rgba8)
+
+    def _draw_view(self, splats, view, rgba8=False):
+        self._draw(splats)
+        out = torch.empty((view[1], view[0], 4), dtype=torch.uint8 if rgba8 else torch.float32, device=self.device)
+        self.trainer.render_view_device(out.data_ptr(), *view, rgba8)
         return out
 
     def density(self):
@@ -144,4 +158,27 @@ class _Render(torch.autograd.Function):
         g = grad_image.to(torch.float32).contiguous()
         r.grads.zero_()
         r.trainer.backward_image_grads(g.data_ptr(), skip_opacity_grad=False, density_stats=ctx.density_stats)
+        return r.grads[:r.n].clone(), None, None
+
+
+class _RenderView(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, splats, r, view):
+        out = r._draw_view(splats, view)
+        ctx.renderer, ctx.view = r, view
+        ctx.save_for_backward(splats)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_view):
+        r = ctx.renderer
+        (splats,) = ctx.saved_tensors  # (torch raises here if they were modified in place since render_view())
+        r._check_stream()
+        # the pass reads the context's CURRENT parameters and needs no frame: upload this call's, which makes image0 and the
+        # hand-over of a pending render() stale -- the generation says so, and that call's backward draws its frame again
+        r.trainer.set_splats_device(splats.data_ptr())
+        r.generation += 1
+        g = grad_view.to(torch.float32).contiguous()
+        r.grads.zero_()
+        r.trainer.view_backward_device(g.data_ptr(), *ctx.view, from_target=False, skip_opacity_grad=False)
         return r.grads[:r.n].clone(), None, None

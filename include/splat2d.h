@@ -510,6 +510,46 @@ int s2d_render_view_device(s2d_ctx* ctx, const s2d_view_config* cfg, void* out_d
  * call or s2d_destroy; the next view allocates again. */
 int s2d_view_release(s2d_ctx* ctx);
 
+/* ---- view gradients: the backward pass through a view, for coarse-to-fine, crop and supersampled
+ * training.  s2d_view_backward_device queues, on the context's stream, the view's transform, projection and list build (the
+ * one host wait of a view: the pair count), then ONE kernel that walks every tile of the raster grid forward and backward
+ * (the final sample colours stay in registers; with samples > 1 the upstream gradient of an output pixel reaches the samples
+ * of its block through lane reads, times 0.25f per resolve level -- no supersampled image or gradient exists in memory), on a
+ * deterministic context the gather over the view's slots, and the adjoint of the record transform, which ADDS the result into
+ * the gradient buffer s2d_backward and s2d_backward_image_grads accumulate into (the bound one after s2d_bind_grads_device):
+ * s2d_adam_step afterwards steps on it and re-zeroes it as always.
+ *
+ * dview_or_target_device: out_height * out_width RGBA32F in device memory, 16-byte aligned, .w ignored -- dL/d(view), or with
+ * S2D_VIEW_BWD_FROM_TARGET a TARGET of the view's size: the kernel forms dL = resolved - target itself, one fp32 subtraction
+ * per channel (the gradient of sum (view - target)^2 / 2, the reference's loss at the view's size), so a C caller trains
+ * against a small target with no elementwise kernel of its own.  No squared error is formed either way.
+ * flags: S2D_VIEW_BWD_FROM_TARGET, S2D_BWD_SKIP_OPACITY_GRAD; anything else is S2D_E_INVALID.
+ *
+ * The adjoint of the records above, g' the gradient of a view record, k = (ax * ay) / (sx' * sy'), fp32, one operation at a
+ * time, left to right:
+ *   g_pos = g'_pos * zr;  g_rot = g'_rot;  g_col = g'_col;
+ *   fr == 0:   g_sx = g'_sx * zr;  g_sy = g'_sy * zr;  g_op = g'_op;
+ *   otherwise: g_op = g'_op * k;  t = (g'_op * opacity) * k;
+ *              g_sx = zr * (g'_sx * (ax / sx') + t * (fr / (ax * (sx' * sx'))));  g_sy alike with y.
+ * The row of a dead splat is left as it is.
+ *
+ * Otherwise the call is as read-only as a view: image0, the training lists and their rebuild counters, the projection, the
+ * context's forward -> backward hand-over (the view has one of its own), the status word, the squared-error ring and the density
+ * statistics are untouched.  It needs splats, not a target or a prior s2d_forward.  S2D_CFG_EXACT_EXP and
+ * S2D_CFG_DETERMINISTIC are honoured (deterministic: bitwise reproducible, the slots being those of the view's rectangles).
+ *
+ * S2D_E_INVALID, before any device work: everything a view is refused for; format != S2D_VIEW_RGBA32F; a NULL or misaligned
+ * pointer; unknown flags; a context with S2D_CFG_COUNT_PAIRS or S2D_CFG_REFERENCE_ORDER.  S2D_E_NOMEM as for a view; on top of
+ * a view's buffers the pass keeps n x 9 floats, 36 bytes per pair of the lists' capacity for its hand-over and, deterministic,
+ * 13 more words per pair -- all freed by s2d_view_release.  After a refusal the context trains on unchanged. */
+#define S2D_VIEW_BWD_FROM_TARGET 0x8u
+int s2d_view_backward_device(s2d_ctx* ctx, const s2d_view_config* cfg, const float* dview_or_target_device, uint32_t flags);
+/* The same pass stopped before the adjoint of the record transform: the n_splats x 9 gradients of the VIEW's records (those of
+ * s2d_view_splats) into host memory, complete on return; the context's gradient buffer is not touched.  An inspection seam: it
+ * lets the two kernels be judged separately. */
+int s2d_view_grads(s2d_ctx* ctx, const s2d_view_config* cfg, const float* dview_or_target_device, uint32_t flags,
+                   s2d_splat* dview_records_host);
+
 /* `iters` whole iterations (main.cpp:414-809): forward, backward, Adam, MSE.  mse_out (may be NULL) receives
  * iters doubles: the value the reference prints for each iteration (main.cpp:796-807).  For a slab context the
  * values are this slab's sum of squared errors divided by (H*W*3), i.e. partial MSEs that add up over slabs.
