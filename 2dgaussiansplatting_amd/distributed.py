@@ -13,6 +13,7 @@ parameters are never exchanged.  Two exchange schemes sit on that partition:
 `backend` is anything with forward() / backward() / adam_step() (and optionally forward_backward(), the fused form):
 the HIP Trainer in bench.py, or the oracle-backed stand-in of tests/test_distributed_cpu.py.
 """
+from ._abi import ROWS_ADAM, ROWS_GRADS, ROWS_SPLATS  # noqa: F401  (callers name them as distributed.ROWS_*)
 
 
 def _raster(backend, before, after):
@@ -99,7 +100,6 @@ def reduce_sqerr(sqerr, dist=None):
 # all_to_all_single with fixed split sizes and one combine kernel -- no host synchronisation.
 # ---------------------------------------------------------------------------------------------------------
 
-ROWS_GRADS, ROWS_SPLATS, ROWS_ADAM = 0, 1, 2
 _ROW_WIDTH = {ROWS_GRADS: 9, ROWS_SPLATS: 9, ROWS_ADAM: 18}
 
 

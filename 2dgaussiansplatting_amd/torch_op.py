@@ -23,7 +23,7 @@ This module imports torch; the package itself does not.
 """
 import torch
 
-from . import Trainer
+from .trainer import Trainer
 
 __all__ = ["SplatRenderer"]
 
@@ -83,6 +83,11 @@ class SplatRenderer:
             raise RuntimeError("SplatRenderer was created on stream %#x and is called with another stream current: its "
                                "kernels would not be ordered with torch's" % self.stream)
 
+    def _check_splats(self, who, splats):
+        if not (isinstance(splats, torch.Tensor) and splats.dtype == torch.float32 and splats.device == self.device and
+                tuple(splats.shape) == (self.n, 9) and splats.is_contiguous()):
+            raise ValueError("%s() takes a contiguous float32 tensor of shape (%d, 9) on %s" % (who, self.n, self.device))
+
     def _draw(self, splats):
         """Forward pass of `splats`: afterwards image0 and the hand-over to the backward walk are theirs."""
         self.trainer.set_splats_device(splats.data_ptr())
@@ -93,9 +98,7 @@ class SplatRenderer:
         """(n, 9) float32 contiguous tensor on the renderer's device -> the slab's rows of the image, (rows, W, 4), .w = 1;
         differentiable with respect to `splats`.  density_stats: the backward call of this frame also accumulates the
         density statistics (S2D_BWD_DENSITY_STATS; density() returns them, trainer.relocate() acts on them)."""
-        if not (isinstance(splats, torch.Tensor) and splats.dtype == torch.float32 and splats.device == self.device and
-                tuple(splats.shape) == (self.n, 9) and splats.is_contiguous()):
-            raise ValueError("render() takes a contiguous float32 tensor of shape (%d, 9) on %s" % (self.n, self.device))
+        self._check_splats("render", splats)
         return _Render.apply(splats, self, bool(density_stats))
 
     def render_view(self, splats, out_width, out_height, origin=(0.0, 0.0), zoom=1.0, filter_var=0.0, samples=1, rgba8=False):
@@ -105,9 +108,7 @@ class SplatRenderer:
         With splats.requires_grad the float view is differentiable with respect to `splats`: its backward is the library's
         pass through the view (s2d_view_backward_device) -- coarse-to-fine, crop and supersampled losses written in torch.  An
         8-bit view has no gradient: rgba8 with requires_grad raises.  Without requires_grad nothing is recorded."""
-        if not (isinstance(splats, torch.Tensor) and splats.dtype == torch.float32 and splats.device == self.device and
-                tuple(splats.shape) == (self.n, 9) and splats.is_contiguous()):
-            raise ValueError("render_view() takes a contiguous float32 tensor of shape (%d, 9) on %s" % (self.n, self.device))
+        self._check_splats("render_view", splats)
         self._check_stream()
         view = (int(out_width), int(out_height), (float(origin[0]), float(origin[1])), float(zoom), float(filter_var), int(samples))
         if splats.requires_grad:

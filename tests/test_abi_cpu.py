@@ -72,6 +72,89 @@ def test_struct_layouts_match_header():
     assert O.SPLAT_DTYPE == S2D.SPLAT_DTYPE and O.ADAM_DTYPE.itemsize == S2D.ADAM_DTYPE.itemsize
 
 
+def declared_in_order(headers=(HEADER, TEST_HEADER)):
+    """The declared symbols in the order of their declarations, the product header first."""
+    names = []
+    for h in headers:
+        src = re.sub(r"/\*.*?\*/", "", open(h).read(), flags=re.S)
+        names += [n for n in re.findall(r"\b(s2d_[a-z0-9_]+)\s*\(", src) if n not in names]
+    return names
+
+
+def header_constants():
+    """({every `#define S2D_<NAME> <integer literal>` of the product header}, {every enumerator of s2d_status})."""
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    defines = {n: int(v, 0) for n, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(S2D_[A-Z0-9_]+)[ \t]+(0[xX][0-9a-fA-F]+|\d+)[uU]?[ \t]*$",
+                                                   src, flags=re.M)}
+    enum = re.search(r"typedef\s+enum\s+s2d_status\s*\{(.*?)\}\s*s2d_status\s*;", src, flags=re.S).group(1)
+    status = {n: int(v, 0) for n, v in re.findall(r"\b(S2D_[A-Z0-9_]+)\s*=\s*(0[xX][0-9a-fA-F]+|\d+)", enum)}
+    assert len(status) == len([x for x in enum.split(",") if x.strip()])   # every enumerator has its value written out
+    return defines, status
+
+
+def test_constants_are_the_headers():
+    """Every integer S2D_* macro and every status of include/splat2d.h is in the binding with the header's value, the
+    binding exports no integer S2D_* name the header lacks, and STATUS_NAMES is the enum."""
+    defines, status = header_constants()
+    assert len(defines) >= 25 and len(status) == 6 and not set(defines) & set(status)
+    assert {"S2D_ABI_VERSION", "S2D_CFG_REFERENCE_ORDER", "S2D_ROWS_ADAM", "S2D_MULTI_REPLICATED", "S2D_VIEW_BWD_FROM_TARGET"} <= set(defines)
+    want = dict(defines, **status)
+    for name, value in want.items():
+        assert getattr(S2D, name, None) == value, name
+    exported = {n: v for n, v in vars(S2D).items() if n.startswith("S2D_") and isinstance(v, int)}
+    assert exported == want
+    assert S2D.STATUS_NAMES == {v: n for n, v in status.items()}
+    assert (S2D.ROWS_GRADS, S2D.ROWS_SPLATS, S2D.ROWS_ADAM) == (defines["S2D_ROWS_GRADS"], defines["S2D_ROWS_SPLATS"], defines["S2D_ROWS_ADAM"])
+    D = importlib.import_module("2dgaussiansplatting_amd.distributed")
+    assert (D.ROWS_GRADS, D.ROWS_SPLATS, D.ROWS_ADAM) == (S2D.ROWS_GRADS, S2D.ROWS_SPLATS, S2D.ROWS_ADAM)
+    assert [S2D.SEED_SOURCES[k] for k in ("edges", "error", "caller")] == [defines["S2D_SEED_TARGET_EDGES"], defines["S2D_SEED_ERROR"],
+                                                                          defines["S2D_SEED_CALLER"]]
+
+
+def test_every_struct_field_matches_header():
+    """One C program generated from STRUCTS prints, per mirrored type, sizeof and per field offsetof and sizeof; ctypes must
+    say the same for all nine structures (the ctypes field names are the C field names)."""
+    assert len(S2D.STRUCTS) == 9 and all(n.startswith("s2d_") for n in S2D.STRUCTS)
+    mirrored = {getattr(S2D, n) for n in dir(S2D) if isinstance(getattr(S2D, n), type) and issubclass(getattr(S2D, n), C.Structure)}
+    assert mirrored == set(S2D.STRUCTS.values())                 # no structure of the binding escapes the comparison
+    lines = []
+    for ctype, T in S2D.STRUCTS.items():
+        lines.append('printf("%s %%zu", sizeof(%s));' % (ctype, ctype))
+        for field, _ in T._fields_:
+            lines.append('printf(" %%zu %%zu", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (ctype, field, ctype, field))
+        lines.append('printf("\\n");')
+    code = '#include <stdio.h>\n#include <stddef.h>\n#include "splat2d.h"\nint main(void) {\n%s\nreturn 0;\n}\n' % "\n".join(lines)
+    with tempfile.TemporaryDirectory() as d:
+        src = os.path.join(d, "t.c")
+        open(src, "w").write(code)
+        exe = os.path.join(d, "t")
+        subprocess.check_call(["gcc", "-std=c11", "-I", os.path.join(O.ROOT, "include"), src, "-o", exe])
+        got = {l.split()[0]: [int(v) for v in l.split()[1:]] for l in subprocess.check_output([exe], text=True).splitlines()}
+    assert set(got) == set(S2D.STRUCTS)
+    for ctype, T in S2D.STRUCTS.items():
+        want = [C.sizeof(T)]
+        for field, _ in T._fields_:
+            want += [getattr(T, field).offset, getattr(T, field).size]
+        assert got[ctype] == want, ctype
+        # the fields cover the C type: nothing but alignment padding may follow the last one
+        last = getattr(T, T._fields_[-1][0])
+        assert got[ctype][0] - (last.offset + last.size) < C.alignment(T), ctype
+
+
+def test_signature_table_is_the_headers_and_is_applied(lib):
+    """SIGNATURES lists exactly the declarations of the two headers, in their order, and load_library() leaves every
+    symbol with the table's argtypes and restype (none is left to ctypes' default `int` arguments)."""
+    assert list(S2D.SIGNATURES) == declared_in_order() and sorted(S2D.SIGNATURES) == declared_symbols()
+    assert S2D.ABI_SYMBOLS == list(S2D.SIGNATURES)
+    for name, (argtypes, restype) in S2D.SIGNATURES.items():
+        f = getattr(lib, name)
+        assert f.argtypes is not None and list(f.argtypes) == list(argtypes), name
+        assert f.restype == restype, name
+    assert [n for n, (_, r) in S2D.SIGNATURES.items() if r is None] == ["s2d_destroy", "s2d_multi_destroy"]
+    assert [n for n, (_, r) in S2D.SIGNATURES.items() if r is C.c_char_p] == ["s2d_multi_last_error", "s2d_last_error"]
+    assert [n for n, (_, r) in S2D.SIGNATURES.items() if r is C.c_void_p] == ["s2d_grads_device_ptr", "s2d_stream"]
+
+
 def test_create_rejects_bad_configs(lib):
     h = C.c_void_p()
     cfg = S2D._Config()

@@ -24,9 +24,7 @@ MODE = {}
 
 
 def run(path, W, H, n, iters, rows):
-    S2D._lib = None
-    L = S2D.load_library(path)
-    S2D._lib = L
+    S2D.use_library(path)
     kw = dict(MODE)
     if rows is not None:
         kw.update(row_begin=rows[0], row_end=rows[1])
@@ -39,7 +37,7 @@ def run(path, W, H, n, iters, rows):
         t.step(iters, want_mse=False)
         t.synchronize()
         dt = time.perf_counter() - t0
-    S2D._lib = None
+    S2D.use_library()
     return iters / dt
 
 

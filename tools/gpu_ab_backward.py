@@ -18,8 +18,7 @@ N = 1_000_000
 
 
 def run(path, upstream):
-    S2D._lib = None
-    S2D._lib = S2D.load_library(path)
+    S2D.use_library(path)
     with S2D.Trainer(W, H, N) as t:
         t.set_target_synthetic(); t.init()
         t.step(30, want_mse=False)
@@ -46,7 +45,7 @@ def run(path, upstream):
             call()
         t.synchronize()
         dt = time.perf_counter() - t0
-    S2D._lib = None
+    S2D.use_library()
     return 1e3 * dt / iters
 
 

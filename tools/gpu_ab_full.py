@@ -12,8 +12,7 @@ WORK = [("4096^2/1M", 4096, 4096, 1_000_000, 200), ("2048^2/250k", 2048, 2048, 2
 
 
 def run(path, W, H, n, iters, full):
-    S2D._lib = None
-    S2D._lib = S2D.load_library(path)
+    S2D.use_library(path)
     with S2D.Trainer(W, H, n) as t:
         t.lean_backward = not full
         t.set_target_synthetic(); t.init()
@@ -25,7 +24,7 @@ def run(path, W, H, n, iters, full):
             t.forward_backward(skip_image=True); t.adam_step()
         t.synchronize()
         dt = time.perf_counter() - t0
-    S2D._lib = None
+    S2D.use_library()
     return iters / dt
 
 
