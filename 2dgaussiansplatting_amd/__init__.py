@@ -18,7 +18,7 @@ from ._abi import (ABI_SYMBOLS, ABI_VERSION, ADAM_DTYPE, OPTIM_GROUPS, ROWS_ADAM
                    SIGNATURES, SPLAT_DTYPE, STATUS_NAMES, STRUCTS, _Config, _LossConfig, _LossTerms, _OptimConfig,
                    _PruneConfig, _RelocateConfig, _SeedConfig, _Stats, _ViewConfig)
 from ._abi import (S2D_ABI_VERSION, S2D_BWD_DENSITY_STATS, S2D_BWD_SKIP_OPACITY_GRAD, S2D_CFG_ADAM_FP32, S2D_CFG_COUNT_PAIRS,
-                   S2D_CFG_DETERMINISTIC, S2D_CFG_EXACT_EXP, S2D_CFG_FP16_IMAGES, S2D_CFG_GENERIC_BINNING,
+                   S2D_CFG_COVERAGE, S2D_CFG_DETERMINISTIC, S2D_CFG_EXACT_EXP, S2D_CFG_FP16_IMAGES, S2D_CFG_GENERIC_BINNING,
                    S2D_CFG_REFERENCE_ORDER, S2D_E_HIP, S2D_E_INVALID, S2D_E_NOMEM, S2D_E_NONFINITE, S2D_E_STATE,
                    S2D_FB_SKIP_IMAGE, S2D_MULTI_REPLICATED, S2D_MULTI_SHARE_GPU, S2D_OK, S2D_ROWS_ADAM, S2D_ROWS_GRADS,
                    S2D_ROWS_SPLATS, S2D_SEED_CALLER, S2D_SEED_ERROR, S2D_SEED_SQUARED, S2D_SEED_TARGET_EDGES,

@@ -33,6 +33,7 @@ S2D_CFG_EXACT_EXP = 0x8
 S2D_CFG_ADAM_FP32 = 0x10
 S2D_CFG_GENERIC_BINNING = 0x20
 S2D_CFG_REFERENCE_ORDER = 0x40
+S2D_CFG_COVERAGE = 0x80
 S2D_SEED_TARGET_EDGES, S2D_SEED_ERROR, S2D_SEED_CALLER = 0, 1, 2
 S2D_SEED_SQUARED = 0x1
 SEED_SOURCES = {"edges": S2D_SEED_TARGET_EDGES, "error": S2D_SEED_ERROR, "caller": S2D_SEED_CALLER}

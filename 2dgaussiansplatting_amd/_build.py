@@ -17,7 +17,7 @@ HOST_DIR = os.path.join(PKG_DIR, "host")
 TRAIN_BIN = os.path.join(LIB_DIR, "splat2d_train")
 
 HIP_SOURCES = ["s2d_api.hip", "s2d_api_loss.hip", "s2d_api_placement.hip", "s2d_api_optim.hip", "s2d_api_alive.hip", "s2d_api_rows.hip", "s2d_api_view.hip", "s2d_api_test.hip", "s2d_sequence.hip", "s2d_lists.hip", "s2d_state.hip", "s2d_context.hip", "s2d_scan_sort.hip", "s2d_binning.hip", "s2d_tilelists.hip", "s2d_raster.hip",
-               "s2d_raster_ranges.hip", "s2d_raster_gradient.hip", "s2d_raster_det.hip", "s2d_raster_reference.hip",
+               "s2d_raster_ranges.hip", "s2d_raster_gradient.hip", "s2d_raster_det.hip", "s2d_raster_reference.hip", "s2d_raster_coverage.hip",
                "s2d_loss.hip", "s2d_seed.hip", "s2d_view.hip", "s2d_view_gradient.hip", "s2d_optim.hip", "s2d_optim_controls.hip", "s2d_alive.hip", "s2d_halo.hip",
                "s2d_multi.hip", "s2d_multi_run.hip", "s2d_multi_ownership.hip", "s2d_multi_replicated.hip", "s2d_multi_stop.hip"]
 HIP_HEADERS = ["s2d_device.h", "s2d_math.h", "s2d_walk.h", "s2d_walk_backward.h", "s2d_owned.h", "s2d_lists.h", "s2d_state.h", "s2d_context.h", "s2d_ctx.h", "s2d_sequence.h", "s2d_ranges.h", "s2d_density.h", "s2d_loss.h", "s2d_seed.h", "s2d_seed_math.h", "s2d_optim_rates.h", "s2d_adam.h", "s2d_alive.h", "s2d_view.h", "s2d_view_math.h",

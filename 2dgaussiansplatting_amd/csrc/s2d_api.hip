@@ -67,6 +67,10 @@ int s2d_create(const s2d_config* cfg, s2d_ctx** out)
     if (rb < 0 || re > cfg->height || rb >= re || (rb % kTile) != 0) return S2D_E_INVALID;
     if ((cfg->flags & (S2D_CFG_EXACT_EXP | S2D_CFG_REFERENCE_ORDER)) && (cfg->flags & (S2D_CFG_COUNT_PAIRS | S2D_CFG_FP16_IMAGES)))
         return S2D_E_INVALID;
+    // the coverage channel: kernels of the plain lists of a whole image, without counting and with exp_approx (s2d_raster_coverage.hip)
+    if ((cfg->flags & S2D_CFG_COVERAGE) && ((cfg->flags & (S2D_CFG_COUNT_PAIRS | S2D_CFG_EXACT_EXP | S2D_CFG_REFERENCE_ORDER)) ||
+                                            rb != 0 || re != cfg->height))
+        return S2D_E_INVALID;
 
     s2d_ctx* c = new (std::nothrow) s2d_ctx();
     if (!c) return S2D_E_NOMEM;

@@ -16,7 +16,7 @@ int loss_refused(s2d_ctx* c, const s2d_loss_config* cfg)
     if (int rc = whole_scene_refused(c, "the loss passes", true)) return rc; // (the window crosses slab rows)
     if (c->cfg.flags & S2D_CFG_COUNT_PAIRS)
         return fail(c, S2D_E_INVALID, "pair counting (S2D_CFG_COUNT_PAIRS) has no backward pass from an image gradient");
-    return S2D_OK;
+    return coverage_refused(c, "the loss passes"); // (the native losses have no coverage term)
 }
 
 // The loss kernels of the current frame: dL/d(image0) -> dimage, the totals -> `slot` of the loss ring, the squared error

@@ -52,6 +52,7 @@ int view_raster(s2d_ctx* c, const s2d_view_config* cfg, void* out)
     a.g = view_geometry(cfg->out_width, cfg->out_height, s);
     a.out_width = cfg->out_width; a.samples = s; a.rgba8 = cfg->format == S2D_VIEW_RGBA8;
     a.exact_exp = (c->cfg.flags & S2D_CFG_EXACT_EXP) != 0;
+    a.coverage = coverage(c);
     S2D_HIP(c, launch_view_raster(a, c->stream));
     return S2D_OK;
 }
@@ -98,7 +99,7 @@ int view_gradient_refused(s2d_ctx* c, const s2d_view_config* cfg, const float* s
     if (flags & ~(S2D_VIEW_BWD_FROM_TARGET | S2D_BWD_SKIP_OPACITY_GRAD)) return fail(c, S2D_E_INVALID, "%s: unknown flags %#x", who, flags);
     if (c->cfg.flags & S2D_CFG_COUNT_PAIRS) return fail(c, S2D_E_INVALID, "%s: not available with S2D_CFG_COUNT_PAIRS", who);
     if (c->scratch.reference_order()) return fail(c, S2D_E_INVALID, "%s: not available with S2D_CFG_REFERENCE_ORDER", who);
-    return S2D_OK;
+    return coverage_refused(c, who); // (the view gradient kernels carry no coverage)
 }
 
 // The gradients of the view's records from `src` (dL/d(view), or the target with S2D_VIEW_BWD_FROM_TARGET) into the scratch's

@@ -117,6 +117,15 @@ S2D_LOCAL inline int read_back(s2d_ctx* c, void* dst, const void* src, size_t by
     return S2D_OK;
 }
 
+// A coverage context (S2D_CFG_COVERAGE): image0.w, the target's .w and an image gradient's .w are the coverage channel.
+S2D_LOCAL inline bool coverage(const s2d_ctx* c) { return (c->cfg.flags & S2D_CFG_COVERAGE) != 0; }
+// What a coverage context has no kernels for (`who`: a call's name).  S2D_E_INVALID, before any device work.
+S2D_LOCAL inline int coverage_refused(s2d_ctx* c, const char* who)
+{
+    if (coverage(c)) return fail(c, S2D_E_INVALID, "%s: not available with S2D_CFG_COVERAGE", who);
+    return S2D_OK;
+}
+
 S2D_LOCAL inline double mse_norm(const s2d_ctx* c) { return (double)((long long)c->g.H * c->g.W * 3); }
 
 S2D_LOCAL inline size_t slab_pixels(const s2d_ctx* c) { return (size_t)c->g.W * (size_t)(c->g.row_end - c->g.row_begin); }

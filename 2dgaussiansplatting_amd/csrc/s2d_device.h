@@ -266,6 +266,7 @@ struct RasterArgs {
     bool count = false; // Forward, Backward: pair counting into `counters`
     bool exact_exp = false;
     bool need_opacity_grad = false;
+    bool coverage = false; // Forward, Backward: image0.w / image_ref.w / upstream.w are the coverage channel (s2d_raster_coverage.hip)
 };
 hipError_t launch_raster(RasterPass pass, const RasterArgs& a, hipStream_t stream);
 // Reference-order backward pass (S2D_CFG_REFERENCE_ORDER; s2d_raster_reference.hip).  The walk stores the

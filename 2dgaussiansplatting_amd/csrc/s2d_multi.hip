@@ -48,6 +48,7 @@ int s2d_multi_create(const s2d_config* cfg, const int32_t* devices, int32_t n_de
     *out = nullptr;
     if (cfg->row_begin != 0 || cfg->row_end != 0 || cfg->stream != nullptr) return S2D_E_INVALID; // the handle cuts the slabs itself
     if (cfg->flags & S2D_CFG_REFERENCE_ORDER) return S2D_E_INVALID; // one device's validation mode: its chains run over all splats
+    if (cfg->flags & S2D_CFG_COVERAGE) return S2D_E_INVALID;        // the coverage channel has no slab kernels (and no fused one)
     DeviceGuard guard;
     s2d_multi* m = new (std::nothrow) s2d_multi();
     if (!m) return S2D_E_NOMEM;

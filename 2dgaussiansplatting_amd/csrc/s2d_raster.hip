@@ -25,7 +25,7 @@
 // plain iteration -- forward, backward from the target image, fused, the squared-error sum -- and launch_raster; every other
 // kernel family has a unit of its own: s2d_raster_ranges.hip (index ranges), s2d_raster_gradient.hip
 // (backward from a caller's gradient, density statistics), s2d_raster_det.hip (deterministic mode's gather),
-// s2d_raster_reference.hip (reference-order validation).
+// s2d_raster_reference.hip (reference-order validation), s2d_raster_coverage.hip (the coverage channel).
 //
 // The alpha / throughput / colour arithmetic is the reference's, operation for operation
 // (-ffp-contract=off), in both walks, so the framebuffer is bit-identical to the oracle's and the backward
@@ -128,10 +128,12 @@ __global__ __launch_bounds__(256) void sqerr_finalize_kernel(const double* __res
 
 // Which unit's kernels run a pass: the pass, then whether the backward walk starts from the target image or from a caller's
 // gradient (a.upstream), then whether it also sums the density statistics (a.density).  Only the backward kernels have the last
-// two; a combination without a kernel is hipErrorInvalidValue.
+// two; a combination without a kernel is hipErrorInvalidValue.  A coverage context (a.coverage) has its own forward and backward
+// kernels and no others.
 hipError_t launch_raster(RasterPass pass, const RasterArgs& a, hipStream_t stream)
 {
     if (a.g.num_tiles <= 0) return hipSuccess;
+    if (a.coverage) return launch_raster_coverage(pass, a, stream);
     const dim3 grid(raster_grid(a.g.num_tiles)), block(256);
     const bool from_target = a.upstream == nullptr, stats = a.density != nullptr;
     const bool det_mode = a.det.now != 0u;

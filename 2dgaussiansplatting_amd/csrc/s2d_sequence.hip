@@ -75,6 +75,7 @@ RasterArgs raster_args(const s2d_ctx* c, int range = -1)
     c->scratch.fill(&a, c->d_rects, c->d_offsets, c->d_counts, first, count);
     c->ranges.fill(&a, range);
     a.half_images = c->half_images; a.count = (c->cfg.flags & S2D_CFG_COUNT_PAIRS) != 0; a.exact_exp = (c->cfg.flags & S2D_CFG_EXACT_EXP) != 0;
+    a.coverage = coverage(c);
     return a;
 }
 
@@ -232,6 +233,9 @@ int queue_raster(s2d_ctx* c, const RasterJob& job)
         if (need_ranges && (c->cfg.flags & S2D_CFG_COUNT_PAIRS))
             return fail(c, S2D_E_NOMEM, "pair counting (S2D_CFG_COUNT_PAIRS) is not available for scenes beyond %llu (tile, splat) pairs",
                         (unsigned long long)c->ranges.budget());
+        if (need_ranges && coverage(c))
+            return fail(c, S2D_E_NOMEM, "the coverage channel (S2D_CFG_COVERAGE) is not available for scenes beyond %llu (tile, splat) pairs",
+                        (unsigned long long)c->ranges.budget());
         if (need_ranges && c->scratch.reference_order())
             return fail(c, S2D_E_NOMEM, "reference order (S2D_CFG_REFERENCE_ORDER) is not available for scenes beyond %llu (tile, splat) pairs",
                         (unsigned long long)c->ranges.budget());
@@ -289,9 +293,9 @@ int parse_walk_flags(s2d_ctx* c, uint32_t flags, bool step, WalkFlags* out)
 {
     out->need_opacity_grad = step ? (flags & S2D_STEP_OPTIMIZE_OPACITY) != 0 : !(flags & S2D_BWD_SKIP_OPACITY_GRAD);
     out->density = (flags & (step ? S2D_STEP_DENSITY_STATS : S2D_BWD_DENSITY_STATS)) != 0;
-    if (out->density && ((c->cfg.flags & (S2D_CFG_COUNT_PAIRS | S2D_CFG_EXACT_EXP)) || c->scratch.reference_order()))
-        return fail(c, S2D_E_INVALID, "density statistics are not available with S2D_CFG_COUNT_PAIRS, S2D_CFG_EXACT_EXP or "
-                    "S2D_CFG_REFERENCE_ORDER");
+    if (out->density && ((c->cfg.flags & (S2D_CFG_COUNT_PAIRS | S2D_CFG_EXACT_EXP | S2D_CFG_COVERAGE)) || c->scratch.reference_order()))
+        return fail(c, S2D_E_INVALID, "density statistics are not available with S2D_CFG_COUNT_PAIRS, S2D_CFG_EXACT_EXP, "
+                    "S2D_CFG_REFERENCE_ORDER or S2D_CFG_COVERAGE");
     return S2D_OK;
 }
 
@@ -319,10 +323,11 @@ int queue_backward(s2d_ctx* c, bool need_opacity_grad, const float4* upstream, b
 }
 
 // Forward + backward (+ squared error) of the current parameters through the fused kernel.  Pair counting is a
-// property of the separate kernels only, so a counting context takes those.
+// property of the separate kernels only, so a counting context takes those; so does a coverage context, whose kernels are the
+// separate ones (image0 stored every time, whatever write_image says).
 int queue_forward_backward(s2d_ctx* c, bool need_opacity_grad, bool write_image)
 {
-    if ((c->cfg.flags & S2D_CFG_COUNT_PAIRS) || c->scratch.reference_order()) { // (reference order: its backward pass is a launch of its own)
+    if ((c->cfg.flags & S2D_CFG_COUNT_PAIRS) || c->scratch.reference_order() || coverage(c)) { // (reference order: its backward pass is a launch of its own)
         if (int rc = queue_forward(c)) return rc;
         return queue_backward(c, need_opacity_grad);
     }

@@ -49,6 +49,7 @@ struct ViewRasterArgs {
     int samples = 1;        // 1, 2 or 4 per axis
     bool rgba8 = false;
     bool exact_exp = false;
+    bool coverage = false;  // .w (the alpha byte) is the coverage channel, S2D_CFG_COVERAGE; never with exact_exp
 };
 // The forward walk of every tile of the grid, resolved to output pixels inside the workgroup: writes nothing but `out`.
 hipError_t launch_view_raster(const ViewRasterArgs& a, hipStream_t stream);

@@ -15,6 +15,9 @@
 // block's top-left lane forms ((p00 + p01) + (p10 + p11)) * 0.25f and stores the output pixel: no supersampled image exists in
 // memory, and an RGBA8 view writes 4 bytes per output pixel.  Lane exchange rather than LDS: it runs once per tile behind a
 // walk of hundreds of entries, needs no barrier and keeps the workgroup's LDS at the walk's.
+//
+// COVERAGE (S2D_CFG_COVERAGE): the walk blends through blend_entry_coverage, the coverage goes through the
+// same resolve steps as the colours and ends in .w (RGBA8: the alpha byte, quantised like the colours).
 #include "s2d_view.h"
 #include "s2d_walk.h"
 
@@ -45,7 +48,7 @@ __global__ __launch_bounds__(256) void view_transform_kernel(const float* __rest
     for (int k = 0; k < 9; k++) out[(size_t)i * 9 + k] = out9[k];
 }
 
-template <bool EXACT, int S, bool RGBA8>
+template <bool EXACT, int S, bool RGBA8, bool COVERAGE = false>
 __global__ __launch_bounds__(256) void view_raster_kernel(const uint32_t* __restrict__ tile_off, const uint32_t* __restrict__ list,
                                                           const ProjRec* __restrict__ proj, void* __restrict__ out, Geometry g,
                                                           int out_width)
@@ -62,6 +65,7 @@ __global__ __launch_bounds__(256) void view_raster_kernel(const uint32_t* __rest
 
     f2 crg = mk2(0.0f, 0.0f); // main.cpp:414: (0,0,0,1)
     float cb = 0.0f, T = 1.0f;
+    [[maybe_unused]] float ca = 0.0f;
     unsigned long long alive_mask = __ballot(inside); // pixels still above the throughput cut-off (main.cpp:520), wave-uniform
     const uint32_t beg = tile_off[tile], end = tile_off[tile + 1];
     const int se = tid >> 2, sub = tid & 3;
@@ -89,10 +93,18 @@ __global__ __launch_bounds__(256) void view_raster_kernel(const uint32_t* __rest
                 cand &= cand - 1ull;
                 const unsigned long long act = readlane_u64(my_mask, e) & alive_mask; // visited (main.cpp:511-514), not cut off (:520)
                 if (act == 0ull) continue;
-                const Blended bl = blend_entry<EXACT>(s.rec[e][0], s.rec[e][1], s.rec[e][2], pxy, act, crg, cb, T, alive_mask);
-                cb = bl.cb;
-                T = bl.T;
-                alive_mask = bl.alive_mask;
+                if constexpr (COVERAGE) {
+                    const BlendedCoverage bl = blend_entry_coverage<EXACT>(s.rec[e][0], s.rec[e][1], s.rec[e][2], pxy, act, crg, cb, ca, T, alive_mask);
+                    cb = bl.cb;
+                    ca = bl.ca;
+                    T = bl.T;
+                    alive_mask = bl.alive_mask;
+                } else {
+                    const Blended bl = blend_entry<EXACT>(s.rec[e][0], s.rec[e][1], s.rec[e][2], pxy, act, crg, cb, T, alive_mask);
+                    cb = bl.cb;
+                    T = bl.T;
+                    alive_mask = bl.alive_mask;
+                }
             }
         }
         // (also the barrier behind which the next batch may overwrite the records and masks)
@@ -104,17 +116,24 @@ __global__ __launch_bounds__(256) void view_raster_kernel(const uint32_t* __rest
         cr = resolve_level<1, 8>(cr);
         cg = resolve_level<1, 8>(cg);
         cb = resolve_level<1, 8>(cb);
+        if constexpr (COVERAGE) ca = resolve_level<1, 8>(ca);
     }
     if (S == 4) {
         cr = resolve_level<2, 16>(cr);
         cg = resolve_level<2, 16>(cg);
         cb = resolve_level<2, 16>(cb);
+        if constexpr (COVERAGE) ca = resolve_level<2, 16>(ca);
     }
     // the top-left sample of an output pixel stores it (S divides 8: lx % S == x % S); a block is inside the grid as a whole
     if (inside && (lx % S) == 0 && (ly % S) == 0) {
         const size_t o = (size_t)(y / S) * (size_t)out_width + (size_t)(x / S);
-        if (RGBA8) reinterpret_cast<uint32_t*>(out)[o] = view_pack_rgba8(cr, cg, cb);
-        else reinterpret_cast<float4*>(out)[o] = make_float4(cr, cg, cb, 1.0f); // .w reset, main.cpp:543-546
+        if constexpr (COVERAGE) {
+            if (RGBA8) reinterpret_cast<uint32_t*>(out)[o] = view_pack_rgba8(cr, cg, cb, ca);
+            else reinterpret_cast<float4*>(out)[o] = make_float4(cr, cg, cb, ca);
+        } else {
+            if (RGBA8) reinterpret_cast<uint32_t*>(out)[o] = view_pack_rgba8(cr, cg, cb);
+            else reinterpret_cast<float4*>(out)[o] = make_float4(cr, cg, cb, 1.0f); // .w reset, main.cpp:543-546
+        }
     }
 }
 
@@ -131,6 +150,15 @@ template <bool EXACT, int S>
 void launch_view_format(const ViewRasterArgs& a, hipStream_t stream)
 {
     const dim3 grid((unsigned)a.g.num_tiles), block(256);
+    if constexpr (!EXACT) { // (the coverage kernels exist with exp_approx alone: launch_view_raster)
+        if (a.coverage) {
+            if (a.rgba8)
+                hipLaunchKernelGGL((view_raster_kernel<false, S, true, true>), grid, block, 0, stream, a.tile_off, a.list, a.proj, a.out, a.g, a.out_width);
+            else
+                hipLaunchKernelGGL((view_raster_kernel<false, S, false, true>), grid, block, 0, stream, a.tile_off, a.list, a.proj, a.out, a.g, a.out_width);
+            return;
+        }
+    }
     if (a.rgba8)
         hipLaunchKernelGGL((view_raster_kernel<EXACT, S, true>), grid, block, 0, stream, a.tile_off, a.list, a.proj, a.out, a.g, a.out_width);
     else
@@ -154,6 +182,7 @@ hipError_t launch_view_samples(const ViewRasterArgs& a, hipStream_t stream)
 hipError_t launch_view_raster(const ViewRasterArgs& a, hipStream_t stream)
 {
     if (a.g.num_tiles <= 0) return hipErrorInvalidValue;
+    if (a.coverage && a.exact_exp) return hipErrorInvalidValue; // a missing kernel is an error
     return a.exact_exp ? launch_view_samples<true>(a, stream) : launch_view_samples<false>(a, stream);
 }
 

@@ -108,6 +108,12 @@ S2D_HD uint32_t view_pack_rgba8(float r, float g, float b)
     return view_quantise(r) | (view_quantise(g) << 8) | (view_quantise(b) << 16) | 0xFF000000u;
 }
 
+// With the coverage channel (S2D_CFG_COVERAGE): the alpha byte is the coverage, quantised like the colours.
+S2D_HD uint32_t view_pack_rgba8(float r, float g, float b, float a)
+{
+    return view_quantise(r) | (view_quantise(g) << 8) | (view_quantise(b) << 16) | (view_quantise(a) << 24);
+}
+
 S2D_HD bool view_finite(float v) { return (f32_bits(v) & 0x7f800000u) != 0x7f800000u; }
 
 // What a configuration is refused for (S2D_E_INVALID), as a message; nullptr: nothing.  format_max: the largest S2D_VIEW_*.

@@ -256,6 +256,33 @@ __device__ __forceinline__ Blended blend_entry(const float4 q0, const float4 q1,
     return Blended{cb, T, alive_mask};
 }
 
+// The same body with the coverage channel (S2D_CFG_COVERAGE): ca += T * alpha, the colour sum of a channel
+// whose colour is 1 in every splat ((T * 1) * alpha, the product of main.cpp:529-531 with c = 1) -- two more VALU operations per
+// executed (wave, entry).  A function of its own, so that blend_entry and every kernel made of it stay what they were.
+struct BlendedCoverage {
+    float cb, ca, T;
+    unsigned long long alive_mask;
+};
+template <bool EXACT>
+__device__ __forceinline__ BlendedCoverage blend_entry_coverage(const float4 q0, const float4 q1, const float4 q2, const f2 pxy,
+                                                                unsigned long long act, f2& crg, float cb, float ca, float T,
+                                                                unsigned long long alive_mask)
+{
+    const f2 v = pxy - mk2(q0.x, q0.y);                          // main.cpp:523-524
+    const f2 m = mk2(q0.z, q0.w) * v.x + mk2(q1.x, q1.y) * v.y;  // inv_cov * v: (a vx + b vy, b vx + d vy)
+    const f2 vm = v * m;
+    bool nonzero;
+    const float G = gauss_of<EXACT>(vm.x + vm.y, &nonzero);      // main.cpp:526-527
+    const unsigned long long on = act & __ballot(nonzero);
+    const float alpha = __builtin_amdgcn_inverse_ballot_w64(on) ? G * q2.y : 0.0f;
+    crg += (T * mk2(q1.z, q1.w)) * alpha;                        // main.cpp:529-530: (T*c)*alpha
+    cb += T * q2.x * alpha;                                      // main.cpp:531
+    ca += T * alpha;                                             // the same with c = 1
+    T *= (1.0f - alpha);                                         // main.cpp:533
+    alive_mask &= __ballot(!(T < kMinThroughput));               // main.cpp:520, for the next splat
+    return BlendedCoverage{cb, ca, T, alive_mask};
+}
+
 // One tile's forward walk (main.cpp:419-536 for its pixels): leaves the final colour of this thread's pixel in
 // (crg, cb) and hands the entries the backward walk has to run over to it.  The backward walk makes exactly this walk's
 // per-pixel decisions, so the (wave, entry) bodies it will run are the ones that ran here: entry k (k = 0 ..) of them
@@ -268,13 +295,16 @@ __device__ __forceinline__ Blended blend_entry(const float4 q0, const float4 q1,
 // splats of one INDEX RANGE only; the walk continues from the pixel's state after the ranges before it -- (crg, cb) and
 // *T_io on entry -- and leaves the state for the range after it.  The reference's loop is front to back in index order
 // (main.cpp:419), so cutting it at any index and carrying (colour, T) across the cut changes no operation.
-template <bool COUNT, bool EXACT, bool CHUNK = false>
+// COVERAGE (s2d_raster_coverage.hip): the walk blends through blend_entry_coverage and leaves the pixel's coverage in *ca_out.
+template <bool COUNT, bool EXACT, bool CHUNK = false, bool COVERAGE = false>
 __device__ __forceinline__ uint32_t forward_tile(FwdShared& s, const TileCtx& c, const uint32_t* __restrict__ tile_off,
                                              const uint32_t* __restrict__ list, const ProjRec* __restrict__ proj,
                                              unsigned long long* __restrict__ wave_masks, uint32_t* __restrict__ exec_list,
                                              uint32_t* __restrict__ retire_hint, const Geometry& g,
-                                             PairCounters* __restrict__ counters, f2& crg, float& cb, float* T_io = nullptr)
+                                             PairCounters* __restrict__ counters, f2& crg, float& cb, float* T_io = nullptr,
+                                             float* ca_out = nullptr)
 {
+    static_assert(!(COVERAGE && (COUNT || EXACT || CHUNK)), "the coverage channel: plain lists, exp_approx, no pair counting");
     constexpr bool HINT = !COUNT && !CHUNK;
     const int tid = c.tid, lane = c.lane, w = c.w;
     const f2 pxy = c.pxy;
@@ -285,6 +315,7 @@ __device__ __forceinline__ uint32_t forward_tile(FwdShared& s, const TileCtx& c,
         crg = mk2(0.0f, 0.0f);                              // main.cpp:414: (0,0,0,1)
         cb = 0.0f;
     }
+    [[maybe_unused]] float ca = 0.0f;
     // Pixels still above the throughput cut-off (main.cpp:520), as ONE wave-uniform 64-bit mask in scalar registers.
     // (A per-lane bool here costs ~15 scalar instructions per blended entry to merge with exec, and the CU's
     // single scalar unit -- not the SIMDs -- then bounds the loop; measured, profiles/r01/valu_rates.txt.)
@@ -350,10 +381,18 @@ __device__ __forceinline__ uint32_t forward_tile(FwdShared& s, const TileCtx& c,
                 if (act == 0ull) continue;
                 if (COUNT) n_exec += (lane == 0);
                 else touched |= 1ull << e;
-                const Blended bl = blend_entry<EXACT>(s.rec[e][0], s.rec[e][1], s.rec[e][2], pxy, act, crg, cb, T, alive_mask);
-                cb = bl.cb;
-                T = bl.T;
-                alive_mask = bl.alive_mask;
+                if constexpr (COVERAGE) {
+                    const BlendedCoverage bl = blend_entry_coverage<EXACT>(s.rec[e][0], s.rec[e][1], s.rec[e][2], pxy, act, crg, cb, ca, T, alive_mask);
+                    cb = bl.cb;
+                    ca = bl.ca;
+                    T = bl.T;
+                    alive_mask = bl.alive_mask;
+                } else {
+                    const Blended bl = blend_entry<EXACT>(s.rec[e][0], s.rec[e][1], s.rec[e][2], pxy, act, crg, cb, T, alive_mask);
+                    cb = bl.cb;
+                    T = bl.T;
+                    alive_mask = bl.alive_mask;
+                }
                 if (COUNT) n_act += (act >> lane) & 1ull;
             }
         }
@@ -377,6 +416,7 @@ __device__ __forceinline__ uint32_t forward_tile(FwdShared& s, const TileCtx& c,
         }
     }
     if (CHUNK) *T_io = T;
+    if constexpr (COVERAGE) *ca_out = ca;
     if constexpr (HINT)
         if (tid == 0) retire_hint[c.tile] = retired ? last_exec : kNoHint;
     if (COUNT) {
@@ -429,5 +469,6 @@ static hipError_t with_variant(F&& f, std::bool_constant<FLAG>, REST... rest)
 hipError_t launch_raster_ranges(RasterPass pass, const RasterArgs& a, hipStream_t stream); // s2d_raster_ranges.hip
 hipError_t launch_raster_gradient(const RasterArgs& a, hipStream_t stream);                // s2d_raster_gradient.hip
 hipError_t launch_det_gather(const RasterArgs& a, hipStream_t stream);                     // s2d_raster_det.hip
+hipError_t launch_raster_coverage(RasterPass pass, const RasterArgs& a, hipStream_t stream); // s2d_raster_coverage.hip
 
 } // namespace s2d

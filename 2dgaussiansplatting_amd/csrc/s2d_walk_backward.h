@@ -17,10 +17,11 @@ __device__ __forceinline__ float4 load_ref_or_upstream(const void* src, size_t i
 // (By value on purpose: handed over as whole 16-byte values, the way backward_tile took `ref` before, the kernels without
 // UPSTREAM compile to the instructions they had when the subtraction stood inside backward_tile -- DESIGN.md section 10;
 // by reference the compiler narrows their image loads and renumbers registers.)
-template <bool UPSTREAM>
+// COVERAGE (S2D_CFG_COVERAGE): the fourth channel is the coverage, its loss the same half squared error -- dL/dA = fin.w - ref.w.
+template <bool UPSTREAM, bool COVERAGE = false>
 __device__ __forceinline__ float4 loss_grad(const float4 fin, const float4 src)
 {
-    return UPSTREAM ? src : make_float4(fin.x - src.x, fin.y - src.y, fin.z - src.z, 0.0f);
+    return UPSTREAM ? src : make_float4(fin.x - src.x, fin.y - src.y, fin.z - src.z, COVERAGE ? fin.w - src.w : 0.0f);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -188,7 +189,11 @@ struct BwdShared {
 // STATS: next to the nine gradients the walk sums |g_px|, |g_py| and alpha * T (the blend weight, main.cpp:618) of every
 // (pixel, splat) the reference's body reaches -- words 9..11 of the same slots, flushed into `stats` (n x 3 floats, float
 // atomics) or, in deterministic mode, into words 9..11 of the tile's global slot for gather_stats_kernel.
-template <bool COUNT, bool NEED_OP, bool DET, bool EXACT, bool CHUNK = false, bool UPSTREAM = false, bool STATS = false>
+// COVERAGE (S2D_CFG_COVERAGE, s2d_raster_coverage.hip): fin.w is the pixel's final coverage and dL.w its loss
+// gradient; the walk keeps the running coverage ca beside the colours and the channel sum gets a fourth addend, dL.w * dCa_a with
+// dCa_a = T - (fin.w - ca) / (1 - alpha + 1e-15): main.cpp:627-630 for a channel whose colour is 1.  One more running value, one
+// more div_by_recip and one more product; everything behind gs, the LDS layout, the wave sums and the flush are untouched.
+template <bool COUNT, bool NEED_OP, bool DET, bool EXACT, bool CHUNK = false, bool UPSTREAM = false, bool STATS = false, bool COVERAGE = false>
 __device__ __forceinline__ void backward_tile(BwdShared<DET, STATS>& s, const TileCtx& c, const float4 fin, const float4 dL,
                                               const uint32_t* __restrict__ tile_off, const uint32_t* __restrict__ list,
                                               const ProjRec* __restrict__ proj,
@@ -198,6 +203,7 @@ __device__ __forceinline__ void backward_tile(BwdShared<DET, STATS>& s, const Ti
                                               const Geometry& g, const DetSlots& det, PairCounters* __restrict__ counters,
                                               const SqerrJob& sq, float4* state_io = nullptr, float* __restrict__ stats = nullptr)
 {
+    static_assert(!(COVERAGE && (COUNT || EXACT || CHUNK || STATS)), "the coverage channel: plain lists, exp_approx, no counting, no statistics");
     using Shared = BwdShared<DET, STATS>;
     constexpr int BB = Shared::kBatch;      // entries per staged batch
     constexpr int KF = STATS ? 12 : 9;      // floats of a slot the flush moves
@@ -249,6 +255,7 @@ __device__ __forceinline__ void backward_tile(BwdShared<DET, STATS>& s, const Ti
 
     f2 crg = mk2(0.0f, 0.0f);                        // image1 = (0,0,0,1), main.cpp:549
     float cb = 0.0f, T = 1.0f;
+    [[maybe_unused]] float ca = 0.0f;
     if (CHUNK) {
         crg = mk2(state_io->x, state_io->y);
         cb = state_io->z;
@@ -334,6 +341,7 @@ __device__ __forceinline__ void backward_tile(BwdShared<DET, STATS>& s, const Ti
                     const float Tb = T * q2.x;
                     crg += Trg * alpha;                                              // main.cpp:623-625
                     cb += Tb * alpha;
+                    if constexpr (COVERAGE) ca += T * alpha;                         // the same with c = 1
                     // ---- gradient terms ----
                     const float dC_dc = alpha * T;                                   // main.cpp:618
                     const f2 g_rg = dLrg * dC_dc;
@@ -352,7 +360,8 @@ __device__ __forceinline__ void backward_tile(BwdShared<DET, STATS>& s, const Ti
                     const float dCa_b = Tb - div_by_recip(fin.z - cb, den, rd);
                     // the three channel products may cancel: same products, same order as main.cpp:629-630
                     const f2 pr = dLrg * dCa_rg;
-                    const float gs = (pr.x + pr.y) + dLb * dCa_b;
+                    float gs = (pr.x + pr.y) + dLb * dCa_b;
+                    if constexpr (COVERAGE) gs = gs + dL.w * (T - div_by_recip(fin.w - ca, den, rd)); // + dLa * dCa_a
                     const float ga = gs * alpha;
                     const f2 g_pos = ga * m;                                         // main.cpp:639-640, :654-655
                     g_px = g_pos.x;

@@ -1,6 +1,7 @@
 // image_io.h -- image files for the host program: the reference loads its target through prlib/stb_image
 // (main.cpp:253-259) and shows image0 in a window (:794, :839-840); headless, that becomes file I/O.
-// Readers return tightly packed RGB8.  Formats: .s2di (the repo's raw fixtures), binary PPM (P6), PNG
+// Readers return tightly packed RGB8 (load_image), or RGBA8 with a PNG's alpha kept (load_image_rgba: opaque for the formats and
+// PNG colour types without one; save_png_rgba writes it).  Formats: .s2di (the repo's raw fixtures), binary PPM (P6), PNG
 // (8-bit grey / RGB / palette / with or without alpha, non-interlaced; inflate/deflate by zlib), JPEG (read only,
 // jpeg_decode.h).  Host-side
 // C++ only: nothing here is on the training path.
@@ -22,6 +23,10 @@ namespace s2dio {
 struct Image8 {
     int w = 0, h = 0;
     std::vector<uint8_t> rgb; // w*h*3
+};
+struct ImageRGBA8 {
+    int w = 0, h = 0;
+    std::vector<uint8_t> rgba; // w*h*4, straight (not premultiplied) alpha, as a PNG stores it
 };
 
 inline bool ends_with(const std::string& s, const char* suf)
@@ -85,7 +90,8 @@ inline bool load_ppm(const std::vector<uint8_t>& d, Image8* im)
 
 inline uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
 
-inline bool load_png(const std::vector<uint8_t>& d, Image8* im)
+// alpha (may be null): w*h bytes, the alpha channel of colour types 4 and 6, 255 for the others (a palette's tRNS is not read).
+inline bool load_png(const std::vector<uint8_t>& d, Image8* im, std::vector<uint8_t>* alpha = nullptr)
 {
     static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
     if (d.size() < 8 || std::memcmp(d.data(), sig, 8) != 0) return false;
@@ -136,14 +142,16 @@ inline bool load_png(const std::vector<uint8_t>& d, Image8* im)
     im->w = w;
     im->h = h;
     im->rgb.resize((size_t)w * h * 3);
+    if (alpha) alpha->assign((size_t)w * h, 255);
     for (size_t i = 0; i < (size_t)w * h; i++) {
         const uint8_t* s = &px[i * ch];
+        if (alpha && (ctype == 4 || ctype == 6)) (*alpha)[i] = s[ch - 1];
         uint8_t* o = &im->rgb[i * 3];
         if (ctype == 0 || ctype == 4) o[0] = o[1] = o[2] = s[0];
         else if (ctype == 3) {
             if ((size_t)s[0] * 3 + 2 >= plte.size()) return false;
             std::memcpy(o, &plte[(size_t)s[0] * 3], 3);
-        } else std::memcpy(o, s, 3); // alpha, where present, is dropped: imageRef's .w is never read
+        } else std::memcpy(o, s, 3); // (without `alpha`, a file's alpha is dropped: imageRef's .w is read by coverage contexts alone)
     }
     return true;
 }
@@ -157,6 +165,28 @@ inline bool load_image(const std::string& path, Image8* im)
     if (d.size() >= 4 && !std::memcmp(d.data(), "S2DI", 4)) return load_s2di(d, im);
     if (d.size() >= 2 && d[0] == 'P' && d[1] == '6') return load_ppm(d, im);
     return false;
+}
+
+// The file with its alpha: a PNG's own (colour types 4 and 6), opaque for everything else.
+inline bool load_image_rgba(const std::string& path, ImageRGBA8* out)
+{
+    std::vector<uint8_t> d, alpha;
+    Image8 im;
+    if (!read_file(path, &d)) return false;
+    if (d.size() >= 8 && d[0] == 0x89 && d[1] == 'P') {
+        if (!load_png(d, &im, &alpha)) return false;
+    } else {
+        if (!load_image(path, &im)) return false;
+        alpha.assign((size_t)im.w * im.h, 255);
+    }
+    out->w = im.w;
+    out->h = im.h;
+    out->rgba.resize((size_t)im.w * im.h * 4);
+    for (size_t i = 0; i < (size_t)im.w * im.h; i++) {
+        std::memcpy(&out->rgba[i * 4], &im.rgb[i * 3], 3);
+        out->rgba[i * 4 + 3] = alpha[i];
+    }
+    return true;
 }
 
 inline bool save_ppm(const std::string& path, const Image8& im)
@@ -180,13 +210,14 @@ inline bool save_s2di(const std::string& path, const Image8& im)
     return ok;
 }
 
-inline bool save_png(const std::string& path, const Image8& im)
+// w x h pixels of ch = 3 (RGB, colour type 2) or 4 (RGBA, colour type 6) bytes.
+inline bool save_png_pixels(const std::string& path, int w, int h, int ch, const uint8_t* pixels)
 {
-    const size_t stride = (size_t)im.w * 3;
-    std::vector<uint8_t> raw((stride + 1) * (size_t)im.h);
-    for (int y = 0; y < im.h; y++) {
+    const size_t stride = (size_t)w * ch;
+    std::vector<uint8_t> raw((stride + 1) * (size_t)h);
+    for (int y = 0; y < h; y++) {
         raw[(stride + 1) * (size_t)y] = 0; // filter type 0 (None)
-        std::memcpy(&raw[(stride + 1) * (size_t)y + 1], &im.rgb[stride * (size_t)y], stride);
+        std::memcpy(&raw[(stride + 1) * (size_t)y + 1], pixels + stride * (size_t)y, stride);
     }
     uLongf zlen = compressBound((uLong)raw.size());
     std::vector<uint8_t> z(zlen);
@@ -205,14 +236,17 @@ inline bool save_png(const std::string& path, const Image8& im)
     };
     static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
     uint8_t ihdr[13];
-    put32(ihdr, (uint32_t)im.w);
-    put32(ihdr + 4, (uint32_t)im.h);
-    ihdr[8] = 8; ihdr[9] = 2; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;
+    put32(ihdr, (uint32_t)w);
+    put32(ihdr + 4, (uint32_t)h);
+    ihdr[8] = 8; ihdr[9] = ch == 4 ? 6 : 2; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;
     const bool ok = std::fwrite(sig, 1, 8, f) == 8 && chunk("IHDR", ihdr, 13) && chunk("IDAT", z.data(), (uint32_t)zlen) &&
                     chunk("IEND", nullptr, 0);
     std::fclose(f);
     return ok;
 }
+
+inline bool save_png(const std::string& path, const Image8& im) { return save_png_pixels(path, im.w, im.h, 3, im.rgb.data()); }
+inline bool save_png_rgba(const std::string& path, const ImageRGBA8& im) { return save_png_pixels(path, im.w, im.h, 4, im.rgba.data()); }
 
 inline bool save_image(const std::string& path, const Image8& im)
 {
@@ -233,6 +267,38 @@ inline Image8 quantise(const std::vector<float>& rgba, int w, int h)
             const float v = rgba[p * 4 + c] * 255.0f + 0.5f;
             im.rgb[p * 3 + c] = (uint8_t)(v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v));
         }
+    return im;
+}
+
+// A coverage context's target from a file with alpha: colour premultiplied by alpha, .w = alpha (what image0 = (premultiplied
+// colour on black, coverage) is fitted to).
+inline std::vector<float> premultiplied_target(const ImageRGBA8& im)
+{
+    std::vector<float> t((size_t)im.w * im.h * 4);
+    for (size_t p = 0; p < (size_t)im.w * im.h; p++) {
+        const float a = (float)im.rgba[p * 4 + 3] / 255.0f;
+        for (int c = 0; c < 3; c++) t[p * 4 + c] = ((float)im.rgba[p * 4 + c] / 255.0f) * a;
+        t[p * 4 + 3] = a;
+    }
+    return t;
+}
+
+// A coverage context's image0 (premultiplied colour, coverage) -> RGBA8 with straight alpha: rgb / A where A > 0, otherwise 0.
+inline ImageRGBA8 quantise_straight(const std::vector<float>& rgba, int w, int h)
+{
+    ImageRGBA8 im;
+    im.w = w;
+    im.h = h;
+    im.rgba.resize((size_t)w * h * 4);
+    auto q = [](float c) {
+        const float v = c * 255.0f + 0.5f;
+        return (uint8_t)(v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v));
+    };
+    for (size_t p = 0; p < (size_t)w * h; p++) {
+        const float a = rgba[p * 4 + 3];
+        for (int c = 0; c < 3; c++) im.rgba[p * 4 + c] = a > 0.0f ? q(rgba[p * 4 + c] / a) : 0;
+        im.rgba[p * 4 + 3] = a > 0.0f ? q(a) : 0;
+    }
     return im;
 }
 

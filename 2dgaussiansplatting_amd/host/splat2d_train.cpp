@@ -103,6 +103,10 @@ struct Options {
     float rebin_margin = 0.0f;       // --rebin-margin PX: s2d_config.rebin_margin (0: the library's 2 pixels)
     bool freeze_unmoved = false;     // --freeze-unmoved: after each --reseed-every / --relocate-every event only the rows it wrote
                                      // are trained until the next event (s2d_set_frozen)
+    // --coverage: a coverage context (S2D_CFG_COVERAGE).  The target is the file's colour premultiplied by its alpha with .w =
+    // alpha (a file without alpha, or --synthetic: alpha 1); --out-image is written as an RGBA8 PNG with straight alpha, rgb / A
+    // where A > 0, otherwise 0.  One context only, the squared error only, and nothing that needs the density statistics.
+    bool coverage = false;
     bool replicated = false;    // --exchange dense: replicated state + RCCL all-reduce of all gradients (default: slab ownership)
                                 // (RCCL takes one rank per GPU): a rehearsal of the N-rank host logic on a box with fewer GPUs
 };
@@ -131,7 +135,7 @@ int usage()
                  "                     [--reseed-every K [--reseed-window S] [--reseed-max-fraction F] [--reseed-min-weight W] [--reseed-scale X]]\n"
                  "                     [--lr-groups P,S,R,C,O [--lr-final-ratio P,S,R,C,O --lr-decay-iters T]] [--rebin-margin PX] [--freeze-unmoved]\n"
                  "                     [--alive-from K0] [--grow-every M --grow-count C [--grow-scale X]]\n"
-                 "                     [--prune-every K [--prune-min-weight W] [--prune-window S]]\n"
+                 "                     [--prune-every K [--prune-min-weight W] [--prune-window S]] [--coverage]\n"
                  "  --loss-weights M,L,D: train with the sum over pixels and channels of M * d^2 / 2 + L * |d| + D * (1 - SSIM), e.g.\n"
                  "    0,0.8,0.2, instead of the reference's squared error (one GPU only); every line ends with the loss's mean.\n"
                  "  --relocate-every K: before iteration K, 2K, ... move the starved splats (summed T * alpha per pass below W) onto\n"
@@ -161,6 +165,10 @@ int usage()
                  "    (not together with --relocate-every / --reseed-every).  One GPU only, not with --reference-order, and not with\n"
                  "    --save-checkpoint / --load-checkpoint: the checkpoint format does not carry the set.  Defaults X = 3, W = 0.5,\n"
                  "    S = 10 are provisional: not measured yet.\n");
+    std::fprintf(stderr,
+                 "  --coverage: fit the image's alpha as well (a cut-out, a sprite, a layer): the target is the file's colour times its\n"
+                 "    alpha, with the alpha as a fourth channel; --out-image file.png is written as RGBA with straight alpha.  One GPU\n"
+                 "    only; not with --loss-weights, --reference-order, --relocate-every, --reseed-every or --prune-every.\n");
     return 2;
 }
 
@@ -184,6 +192,7 @@ struct Session {
         cfg.rebin_margin = o.rebin_margin;
         if (o.deterministic) cfg.flags |= S2D_CFG_DETERMINISTIC;
         if (o.reference_order) cfg.flags |= S2D_CFG_REFERENCE_ORDER;
+        if (o.coverage) cfg.flags |= S2D_CFG_COVERAGE;
         is_multi = o.gpus > 1 || std::getenv("S2D_TRAIN_FORCE_MULTI"); // (the variable sends --gpus 1 through the handle)
         if (!is_multi) {
             cfg.device = o.device;
@@ -324,6 +333,7 @@ int main(int argc, char** argv)
         else if (a == "--prune-every") o.prune_every = std::atoi(next("--prune-every"));
         else if (a == "--prune-min-weight") o.prune_min_weight = (float)std::atof(next("--prune-min-weight"));
         else if (a == "--prune-window") o.prune_window = std::atoi(next("--prune-window"));
+        else if (a == "--coverage") o.coverage = true;
         else return usage();
     }
     if (!o.convert_in.empty()) { // file conversion between .s2di / .ppm / .png; touches no GPU
@@ -337,7 +347,38 @@ int main(int argc, char** argv)
     // imageRef, main.cpp:253-259
     int W = o.syn_w, H = o.syn_h;
     std::vector<float> imageRef;
-    if (!o.image.empty()) {
+    if (o.coverage) { // (all of it before a file or the device is touched)
+        if (o.gpus > 1 || std::getenv("S2D_TRAIN_FORCE_MULTI")) {
+            std::fprintf(stderr, "--coverage works on one context: the multi-device handle has no coverage channel\n");
+            return 2;
+        }
+        if (o.have_loss) {
+            std::fprintf(stderr, "--coverage trains with the squared error over four channels: not together with --loss-weights\n");
+            return 2;
+        }
+        if (o.relocate_every > 0 || o.reseed_every > 0 || o.prune_every > 0) {
+            std::fprintf(stderr, "--coverage has no density statistics: not together with --relocate-every, --reseed-every or --prune-every\n");
+            return 2;
+        }
+        if (o.reference_order) {
+            std::fprintf(stderr, "--coverage is not available with --reference-order\n");
+            return 2;
+        }
+        if (!o.out_image.empty() && !s2dio::ends_with(o.out_image, ".png")) {
+            std::fprintf(stderr, "--coverage writes --out-image with its alpha: the file must be a .png\n");
+            return 2;
+        }
+    }
+    if (!o.image.empty() && o.coverage) {
+        s2dio::ImageRGBA8 im;
+        if (!s2dio::load_image_rgba(o.image, &im)) {
+            std::fprintf(stderr, "cannot read %s (.s2di, binary .ppm, 8-bit non-interlaced .png and Huffman .jpg are supported)\n", o.image.c_str());
+            return 1;
+        }
+        W = im.w;
+        H = im.h;
+        imageRef = s2dio::premultiplied_target(im);
+    } else if (!o.image.empty()) {
         s2dio::Image8 im;
         if (!s2dio::load_image(o.image, &im)) {
             std::fprintf(stderr, "cannot read %s (.s2di, binary .ppm, 8-bit non-interlaced .png and Huffman .jpg are supported)\n", o.image.c_str());
@@ -651,13 +692,25 @@ int main(int argc, char** argv)
         vc.filter_var = o.view_filter; vc.samples = o.view_samples; vc.format = S2D_VIEW_RGBA8;
         std::vector<uint8_t> rgba((size_t)vc.out_width * (size_t)vc.out_height * 4);
         CK(s2d_render_view(S.ctx, &vc, rgba.data()));
+        if (o.coverage) { // premultiplied bytes and the coverage byte -> straight alpha
+            s2dio::ImageRGBA8 out;
+            out.w = vc.out_width;
+            out.h = vc.out_height;
+            std::vector<float> f(rgba.size());
+            for (size_t i = 0; i < rgba.size(); i++) f[i] = (float)rgba[i] / 255.0f;
+            out = s2dio::quantise_straight(f, out.w, out.h);
+            if (!s2dio::save_png_rgba(o.out_image, out)) {
+                std::fprintf(stderr, "cannot write %s\n", o.out_image.c_str());
+                exit_code = 1;
+            }
+        }
         s2dio::Image8 im;
         im.w = vc.out_width;
         im.h = vc.out_height;
         im.rgb.resize((size_t)im.w * im.h * 3);
         for (size_t p = 0; p < (size_t)im.w * im.h; p++)
             for (int c = 0; c < 3; c++) im.rgb[p * 3 + c] = rgba[p * 4 + c];
-        if (!s2dio::save_image(o.out_image, im)) {
+        if (!o.coverage && !s2dio::save_image(o.out_image, im)) {
             std::fprintf(stderr, "cannot write %s\n", o.out_image.c_str());
             exit_code = 1;
         }
@@ -667,7 +720,8 @@ int main(int argc, char** argv)
         CK(S.forward());
         CK(S.get_image(image0.data())); // tex0->upload(image0), main.cpp:794
         const s2dio::Image8 im = s2dio::quantise(image0, W, H);
-        if (!o.out_image.empty() && !o.have_view && !s2dio::save_image(o.out_image, im)) {
+        if (!o.out_image.empty() && !o.have_view &&
+            !(o.coverage ? s2dio::save_png_rgba(o.out_image, s2dio::quantise_straight(image0, W, H)) : s2dio::save_image(o.out_image, im))) {
             std::fprintf(stderr, "cannot write %s\n", o.out_image.c_str());
             exit_code = 1;
         }

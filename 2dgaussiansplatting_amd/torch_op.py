@@ -5,7 +5,7 @@
     with torch.cuda.stream(torch.cuda.Stream()):
         r = torch_op.SplatRenderer(W, H, n)
         splats = torch.nn.Parameter(...)          # (n, 9) float32: pos.xy, sx, sy, rot, color.rgb, opacity (main.cpp:85-93)
-        img = r.render(splats)                    # (rows, W, 4) float32, .w = 1
+        img = r.render(splats)                    # (rows, W, 4) float32, .w = 1 (coverage=True: .w = coverage)
         loss = (img[..., :3] - target).abs().sum()
         loss.backward()                           # splats.grad: the hand-derived backward walk, from dL/d(img)
 
@@ -36,7 +36,12 @@ class SplatRenderer:
 
     reference_order=True (passed through to the Trainer like every other keyword): the backward walk adds each splat's
     terms in the reference's own order (S2D_CFG_REFERENCE_ORDER), so `splats.grad` is what the reference's loops would
-    accumulate from the same dL/d(img), bit for bit -- a validation mode, slower and memory-hungry."""
+    accumulate from the same dL/d(img), bit for bit -- a validation mode, slower and memory-hungry.
+
+    coverage=True (S2D_CFG_COVERAGE, passed through likewise): .w of render() and render_view() is the coverage of the pixel,
+    1 - its final throughput, instead of the constant 1 (255), and the gradient a loss sends into .w of render() reaches
+    position, scales, rotation and opacity -- alpha losses, compositing over a background, written in torch.  A view is then
+    not differentiable (render_view of a tensor that requires grad raises the library's refusal)."""
 
     def __init__(self, width, height, n_splats, **trainer_kw):
         if "stream" in trainer_kw:
@@ -95,15 +100,16 @@ class SplatRenderer:
         self.generation += 1
 
     def render(self, splats, density_stats=False):
-        """(n, 9) float32 contiguous tensor on the renderer's device -> the slab's rows of the image, (rows, W, 4), .w = 1;
-        differentiable with respect to `splats`.  density_stats: the backward call of this frame also accumulates the
+        """(n, 9) float32 contiguous tensor on the renderer's device -> the slab's rows of the image, (rows, W, 4), .w = 1 (a coverage
+        renderer: .w = coverage); differentiable with respect to `splats`.  density_stats: the backward call of this frame also accumulates the
         density statistics (S2D_BWD_DENSITY_STATS; density() returns them, trainer.relocate() acts on them)."""
         self._check_splats("render", splats)
         return _Render.apply(splats, self, bool(density_stats))
 
     def render_view(self, splats, out_width, out_height, origin=(0.0, 0.0), zoom=1.0, filter_var=0.0, samples=1, rgba8=False):
         """A view of `splats` (Trainer.render_view: any zoom, crop and output size) -> (out_height, out_width, 4) tensor on
-        the renderer's device, float32 with .w = 1 or uint8 with alpha 255.  The parameters are uploaded the way render()
+        the renderer's device, float32 with .w = 1 or uint8 with alpha 255 (a coverage renderer: .w = coverage, the alpha
+        byte its quantisation).  The parameters are uploaded the way render()
         uploads them, so image0 and the hand-over are theirs afterwards.
         With splats.requires_grad the float view is differentiable with respect to `splats`: its backward is the library's
         pass through the view (s2d_view_backward_device) -- coarse-to-fine, crop and supersampled losses written in torch.  An

@@ -6,7 +6,7 @@ import os
 import numpy as np
 
 from ._abi import (S2D_BWD_DENSITY_STATS, S2D_BWD_SKIP_OPACITY_GRAD, S2D_CFG_ADAM_FP32, S2D_CFG_COUNT_PAIRS,
-                   S2D_CFG_DETERMINISTIC, S2D_CFG_EXACT_EXP, S2D_CFG_FP16_IMAGES, S2D_CFG_GENERIC_BINNING,
+                   S2D_CFG_COVERAGE, S2D_CFG_DETERMINISTIC, S2D_CFG_EXACT_EXP, S2D_CFG_FP16_IMAGES, S2D_CFG_GENERIC_BINNING,
                    S2D_CFG_REFERENCE_ORDER, S2D_FB_SKIP_IMAGE, S2D_SEED_SQUARED, S2D_STEP_DENSITY_STATS,
                    S2D_STEP_OPTIMIZE_OPACITY, S2D_VIEW_BWD_FROM_TARGET, S2D_VIEW_RGBA8, S2D_VIEW_RGBA32F, SEED_SOURCES,
                    SPLAT_DTYPE, _Config, _LossConfig, _LossTerms, _OptimConfig, _PruneConfig, _RelocateConfig, _SeedConfig,
@@ -46,7 +46,7 @@ class Trainer(_Handle):
 
     def __init__(self, width, height, n_splats, device=0, row_begin=0, row_end=0, training_rate=0.0,
                  rebin_interval=0, rebin_margin=0.0, count_pairs=False, fp16_images=False, deterministic=False, exact_exp=False,
-                 adam_fp32=False, generic_binning=False, stream=None, chunk_pairs=None, reference_order=False):
+                 adam_fp32=False, generic_binning=False, stream=None, chunk_pairs=None, reference_order=False, coverage=False):
         self.W, self.H, self.n = int(width), int(height), int(n_splats)
         cfg = _Config()
         cfg.struct_size = C.sizeof(_Config)
@@ -57,13 +57,15 @@ class Trainer(_Handle):
         cfg.flags = ((S2D_CFG_COUNT_PAIRS if count_pairs else 0) | (S2D_CFG_FP16_IMAGES if fp16_images else 0) |
                      (S2D_CFG_DETERMINISTIC if deterministic else 0) | (S2D_CFG_EXACT_EXP if exact_exp else 0) |
                      (S2D_CFG_ADAM_FP32 if adam_fp32 else 0) | (S2D_CFG_GENERIC_BINNING if generic_binning else 0) |
-                     (S2D_CFG_REFERENCE_ORDER if reference_order else 0))
+                     (S2D_CFG_REFERENCE_ORDER if reference_order else 0) | (S2D_CFG_COVERAGE if coverage else 0))
         cfg.rebin_interval = int(rebin_interval)
         cfg.rebin_margin = float(rebin_margin)
         cfg.stream = stream
         self.stream = stream  # HIP stream handle the context works on; None: a stream the library owns
         # reference_order: validation mode, gradients / optimiser state / MSE bytes-equal to the reference's
         # (S2D_CFG_REFERENCE_ORDER, include/splat2d.h); slower and memory-hungry, results otherwise those of the reference
+        # coverage: image0.w, the target's .w and the .w of a caller's image gradient are the coverage channel
+        # (S2D_CFG_COVERAGE, include/splat2d.h) instead of a constant 1 / ignored
         # chunk_pairs (tests): the (tile, splat) pair budget beyond which a scene is rendered by index ranges of the splats;
         # the library reads S2D_CHUNK_PAIRS when the context is created (default 2^30)
         with _chunk_pairs_env(chunk_pairs):
@@ -115,7 +117,8 @@ class Trainer(_Handle):
         self._ck(self.L.s2d_get_image_rows_device(self._h, _dev(ptr)))
 
     def backward_image_grads(self, ptr, skip_opacity_grad=None, density_stats=False):
-        """Backward pass from the caller's dL/d(image0) (device pointer, the slab's rows, RGBA32F, .w ignored) instead of
+        """Backward pass from the caller's dL/d(image0) (device pointer, the slab's rows, RGBA32F, .w ignored -- a coverage context:
+        .w = dL/d(coverage)) instead of
         image0 - imageRef; skip_opacity_grad and density_stats as backward()."""
         self._ck(self.L.s2d_backward_image_grads(self._h, _dev(ptr), self._bwd_flags(skip_opacity_grad, density_stats)))
 
@@ -333,7 +336,7 @@ class Trainer(_Handle):
 
     def render_view(self, out_width, out_height, origin=(0.0, 0.0), zoom=1.0, filter_var=0.0, samples=1, rgba8=False):
         """The window of the source plane that starts at `origin`, at `zoom` output pixels per source pixel, as an
-        (out_height, out_width, 4) array: float32 with .w = 1, or uint8 with alpha 255 (rgba8).  samples: 1, 2 or 4 per axis;
+        (out_height, out_width, 4) array: float32 with .w = 1, or uint8 with alpha 255 (rgba8); a coverage context: .w = coverage.  samples: 1, 2 or 4 per axis;
         filter_var: variance, in output pixels^2, of a low-pass on the footprints."""
         cfg = self._view_config(out_width, out_height, origin, zoom, filter_var, samples, rgba8)
         a = np.zeros((int(out_height), int(out_width), 4), dtype=np.uint8 if rgba8 else np.float32)

@@ -133,6 +133,20 @@ typedef enum s2d_status {
                                     * result is that of this flag alone.  Not combinable with S2D_CFG_COUNT_PAIRS /
                                     * S2D_CFG_FP16_IMAGES, s2d_multi_create or slab ownership (s2d_halo_commit with masks):
                                     * S2D_E_INVALID; no index-range rendering (see s2d_forward). */
+#define S2D_CFG_COVERAGE 0x80u     /* coverage channel: every pixel carries a fourth running value
+                                    * ca, 0 at the start and ca += T * alpha beside main.cpp:529-531 -- the colour sum of a
+                                    * channel whose colour is 1 in every splat, 1 - T_final up to rounding.  s2d_forward stores
+                                    * image0 = (r, g, b, ca); the .w of the target (s2d_set_target) is the alpha to fit and the
+                                    * loss of s2d_backward is the half squared error over four channels; the .w of the image
+                                    * gradient of s2d_backward_image_grads is dL/d(ca); a view's .w (alpha byte) is ca resolved
+                                    * (quantised) like the colours.  .rgb stays premultiplied colour on black, and the squared
+                                    * error (trace ring, s2d_get_mse) the three-channel quantity.  s2d_forward_backward and
+                                    * s2d_step queue the separate launches and store image0 every iteration (S2D_FB_SKIP_IMAGE
+                                    * has no effect).  S2D_E_INVALID: together with S2D_CFG_COUNT_PAIRS, S2D_CFG_EXACT_EXP,
+                                    * S2D_CFG_REFERENCE_ORDER or a row slab at s2d_create; s2d_multi_create; s2d_halo_masks
+                                    * and s2d_halo_commit; S2D_BWD_DENSITY_STATS / S2D_STEP_DENSITY_STATS; s2d_loss_backward,
+                                    * s2d_step_loss, s2d_loss_image_grads_device; s2d_view_backward_device and s2d_view_grads.
+                                    * S2D_E_NOMEM for a scene that would be rendered by index ranges (see s2d_forward). */
 
 typedef struct s2d_config {
     uint32_t struct_size;   /* = sizeof(s2d_config) */
@@ -205,7 +219,8 @@ int s2d_get_adam(s2d_ctx* ctx, s2d_splat_adam* adams, float* beta1t, float* beta
  * (forward, backward and s2d_step alike; only S2D_CFG_COUNT_PAIRS and S2D_CFG_REFERENCE_ORDER contexts answer S2D_E_NOMEM
  * there, the latter because its term scratch is addressed by the pairs of one set of lists). */
 int s2d_forward(s2d_ctx* ctx);
-/* image0 as uploaded at main.cpp:794: width*height RGBA32F, .w = 1.  Rows outside the slab are returned as 0. */
+/* image0 as uploaded at main.cpp:794: width*height RGBA32F, .w = 1 (S2D_CFG_COVERAGE: .w = coverage).  Rows outside the
+ * slab are returned as 0. */
 int s2d_get_image(s2d_ctx* ctx, float* rgba32f);
 /* The slab's rows of image0 alone: (row_end - row_begin) * width RGBA32F, first row = row_begin (what a multi-GPU host
  * stitches together; s2d_get_image of a whole-image context returns the same bytes). */
@@ -223,7 +238,8 @@ int s2d_get_grads(s2d_ctx* ctx, s2d_splat* dsplats);
 /* ---- the rasteriser as a building block: any loss on image0, formed by the caller on the device (INTEGRATION.md
  * section 5; torch_op.py wraps these three into a torch.autograd.Function) ---- */
 /* Backward pass (main.cpp:548-712) with dL/d(image0) supplied by the caller instead of image0 - imageRef (main.cpp:616):
- * DEVICE pointer, (row_end - row_begin) * width RGBA32F, first row = row_begin, .w ignored, 16-byte aligned.
+ * DEVICE pointer, (row_end - row_begin) * width RGBA32F, first row = row_begin, 16-byte aligned; .w ignored, or with
+ * S2D_CFG_COVERAGE dL/d(coverage), which reaches position, scales, rotation and opacity but no colour.
  * Accumulates into the gradient buffer like s2d_backward; needs s2d_forward on the current parameters (S2D_E_STATE
  * otherwise, also after a fused launch with S2D_FB_SKIP_IMAGE); S2D_E_INVALID for a S2D_CFG_COUNT_PAIRS context.
  * flags: S2D_BWD_SKIP_OPACITY_GRAD.  Forms no squared error: the trace ring and s2d_get_mse keep what they had.
@@ -488,8 +504,8 @@ int s2d_grow(s2d_ctx* ctx, const s2d_seed_config* cfg, const int32_t* ids_host, 
  * context (row_begin / row_end) or one with a held set (s2d_halo_commit).  S2D_E_NOMEM: the view's (tile, splat) pairs exceed
  * S2D_CHUNK_PAIRS (views are not rendered by index ranges), or an allocation failed.  There is no S2D_E_STATE: a view needs
  * splats, not a target or a forward pass.  The multi-device handle (s2d_multi) has no views: out of scope here. */
-#define S2D_VIEW_RGBA32F 0u   /* out: out_height * out_width * 4 floats, .w = 1 */
-#define S2D_VIEW_RGBA8   1u   /* out: out_height * out_width * 4 bytes,  .w = 255 */
+#define S2D_VIEW_RGBA32F 0u   /* out: out_height * out_width * 4 floats, .w = 1 (S2D_CFG_COVERAGE: coverage, resolved like the colours) */
+#define S2D_VIEW_RGBA8   1u   /* out: out_height * out_width * 4 bytes,  .w = 255 (S2D_CFG_COVERAGE: coverage, quantised like the colours) */
 typedef struct s2d_view_config {
     uint32_t struct_size;            /* = sizeof(s2d_view_config) */
     int32_t  out_width, out_height;  /* >= 1; out_* * samples <= 65536 */
