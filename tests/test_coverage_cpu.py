@@ -118,6 +118,65 @@ def test_the_alpha_term_of_the_backward_walk_is_the_derivative_of_the_coverage(i
 
 
 # ---------------------------------------------------------------------------------------------------------
+# the references of tests/test_gpu_coverage_limits.py, on their own
+# ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("opacity", [False, True], ids=["fixed_opacity", "optimize_opacity"])
+@pytest.mark.parametrize("name", CR.SCENES)
+def test_the_four_channel_loop_is_ten_times_closer_to_itself_than_the_bar_it_is_used_with(name, opacity):
+    """coverage_ref.FourChannelOracle adds the gradients of two oracle passes.  Whether the two fp32 results are added ("f32")
+    or all terms are summed in double and rounded once ("f64") is a choice the GPU does not share with either: after five
+    iterations the two must agree ten times better than the bar the GPU is held to against "f32" (the update bar of
+    tests/test_gpu_parity.py::test_training_steps_random_sweep).  Measured: mini 1.3e-4 of 2.9e-3 (opacity on), 17 x 17 1.9e-6
+    of 4.1e-4, stack 1.9e-6 of 1.1e-3."""
+    mse32, sp32 = CR.five_steps(name, opacity, "f32")
+    mse64, sp64 = CR.five_steps(name, opacity, "f64")
+    bar = CR.update_bar(sp32)
+    worst = float(np.abs(sp32 - sp64).max())
+    print("\n[coverage] %s opacity=%s: max |f32 - f64| after 5 steps %.3e, bar %.3e" % (name, opacity, worst, bar))
+    assert np.isfinite(sp32).all() and np.isfinite(mse32).all() and mse32[0] == mse64[0]
+    assert worst <= 0.1 * bar, (worst, bar)
+    np.testing.assert_allclose(mse64, mse32, rtol=2e-6)   # (a tenth of the trace bar)
+    s0 = CR.scene(name)[1]
+    moved = np.abs(sp32 - s0)
+    assert moved[:, CR.GEOM[:5]].max() > 10 * bar / 5 and (moved[:, 8].any() if opacity else not moved[:, 8].any())
+    # ... and the fourth channel is at work: the plain oracle alone ends somewhere else
+    o = CR.oracle_of(CR.scene(name)[0], s0)
+    o.optimize_opacity = opacity
+    for _ in range(5):
+        o.step()
+    assert np.abs(o.splats.view(np.float32).reshape(-1, 9) - sp32).max() > bar
+
+
+def test_the_sweep_is_not_trivial():
+    """Over seeds 0 .. 23 of coverage_ref.sweep_case the oracle twin's coverage has pixels at exactly 0, in (0.05, 0.95) and
+    above 0.99, every splat count and every variant occurs with splats, and the twin's gradient under a signed upstream is
+    finite for every seed (a seed whose oracle gradient is not would be replaced, not forgiven)."""
+    import test_image_grads_cpu as IG
+    zero = mid = high = 0
+    counts, with_splats = set(), set()
+    for seed in CR.SWEEP_SEEDS:
+        W, H, n, s, tgt = CR.sweep_case(seed)
+        assert tgt.shape == (H, W, 4) and len(s) == n and 1 <= W < 300 and 1 <= H < 220
+        assert W * H == 1 or len(np.unique(tgt[..., 3])) > 1
+        counts.add(n)
+        if n == 0:
+            continue
+        with_splats.add(seed % 4)
+        o = CR.oracle_of(tgt, CR.white_twin(s))
+        frame = o.forward().copy()
+        cov = frame[..., 0]
+        zero, mid, high = zero + int((cov == 0).sum()), mid + int(((cov > 0.05) & (cov < 0.95)).sum()), high + int((cov > 0.99).sum())
+        gu = np.zeros(frame.shape, dtype=np.float32)
+        gu[..., 0] = CR.signed_upstream(H, W, seed)
+        o.ref = np.ascontiguousarray(IG.pseudo_target(frame, gu))
+        d, dsum, dabs = o.backward_stats()
+        assert np.isfinite(d.view(np.float32)).all() and np.isfinite(dsum).all() and np.isfinite(dabs).all(), seed
+    print("\n[coverage] sweep: %d pixels at 0, %d in (0.05, 0.95), %d above 0.99; counts %s" % (zero, mid, high, sorted(counts)))
+    assert zero > 1000 and mid > 1000 and high > 1000
+    assert counts == {0, 1, 3, 40, 300, 700} and with_splats == {0, 1, 2, 3}
+
+
+# ---------------------------------------------------------------------------------------------------------
 # RGBA files of the host program
 # ---------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
@@ -191,6 +250,37 @@ def test_the_coverage_target_is_premultiplied_and_the_output_is_straight(io_exe,
     assert np.array_equal(s[..., 3], a[..., 3])
     assert not s[a[..., 3] == 0].any()
     assert np.array_equal(s[a[..., 3] > 0][:, :3], a[a[..., 3] > 0][:, :3])
+
+
+def test_straight_rgba8_is_quantise_straight(io_exe, tmp_path):
+    """coverage_ref.straight_rgba8, which the GPU tests of the host program compare files with, against the C++ it restates:
+    a random float image with a = 0, a < 0, a tiny (the quotient overflows), rgb > a, negative colours and exact byte steps."""
+    rng = np.random.default_rng(11)
+    W, H = 37, 21
+    f = np.zeros((H, W, 4), dtype=np.float32)
+    f[..., 3] = rng.uniform(0.0, 1.0, (H, W))
+    f[..., :3] = rng.uniform(0.0, 1.0, (H, W, 3)) * f[..., 3:4]            # premultiplied, as image0 is
+    f[0, :, 3] = 0.0                                                       # transparent, with colour left behind it
+    f[0, :, :3] = rng.uniform(-1, 1, (W, 3))
+    f[1, :, 3] = -rng.uniform(0, 1, W)
+    f[2, :, 3] = np.array([1e-45, 1e-38, 1e-30, 1e-12], dtype=np.float32)[np.arange(W) % 4]   # c / a overflows or is huge
+    f[3, :, :3] = f[3, :, 3:4] * rng.uniform(1.0, 3.0, (W, 3))             # rgb > a
+    f[4, :, :3] = -f[4, :, :3]
+    f[5, :, 3] = 1.0 + rng.uniform(0, 1, W)                                # coverage above 1 clamps
+    k = np.arange(W, dtype=np.float32)
+    f[6, :, 3] = 1.0
+    f[6, :, 0] = (k + np.float32(0.5)) / np.float32(255.0)                 # on the rounding boundary of a byte
+    f[6, :, 1] = k / np.float32(255.0)
+    f[7, :, 3] = (k * 7 % 256) / np.float32(255.0)
+    assert np.isfinite(f).all()
+    open(tmp_path / "f.f32", "wb").write(f.tobytes())
+    subprocess.check_call([io_exe, "straight", str(W), str(H), str(tmp_path / "f.f32"), str(tmp_path / "s.bin")])
+    want = np.frombuffer(open(tmp_path / "s.bin", "rb").read(), dtype=np.uint8).reshape(H, W, 4)
+    got = CR.straight_rgba8(f)
+    assert got.dtype == np.uint8 and got.tobytes() == want.tobytes()
+    assert not got[0].any() and not got[1].any() and (got[2, :, 3] == 0).all() and (got[2, :, :3] == 255).any()
+    assert (got[3, :, :3] == 255).all() and not got[4, :, :3].any() and (got[5, :, 3] == 255).all()
+    assert len(np.unique(got[..., 3])) > 200 and len(np.unique(got[..., :3])) > 200
 
 
 def test_the_host_program_refuses_coverage_with_what_it_cannot_combine(tmp_path):
