@@ -24,6 +24,15 @@ def white_twin(splats):
     return s9
 
 
+def check_view_against_white_twin(vc, vp, vw, rgba8):
+    """The white-twin yardstick for a view: vc, vp, vw are one view drawn by a coverage context, by a plain context with the same
+    splats and by a plain context with their white twin.  The colours are the plain view's and the fourth channel is the
+    twin's red, in bytes."""
+    assert vc[..., :3].tobytes() == vp[..., :3].tobytes() and vp[..., :3].any()
+    assert vc[..., 3].tobytes() == vw[..., 0].tobytes()
+    assert len(np.unique(vc[..., 3])) > 1 and (vp[..., 3] == (255 if rgba8 else 1)).all()  # (a channel, not a constant)
+
+
 @functools.lru_cache(maxsize=None)
 def scene(name):
     """-> (target RGBA32F with a non-trivial alpha, (n, 9) float32 splats), computed once and never written.

@@ -16,7 +16,6 @@ rasteriser to the oracle on, and each test asserts that first.  The 513-tile-col
 the library is compared with itself only.
 Scenes: 64 x 48, n = 600 (tests/view_ref.py): every tile's list spans several batches, a view has more than one workgroup."""
 import ctypes as C
-import functools
 import importlib
 import os
 
@@ -28,6 +27,8 @@ import oracle_lib as O
 import test_image_grads_cpu as IG
 import view_grad_ref as G
 import view_ref as V
+from view_grad_cases import (_torch, assert_pinned, check_against_second_context, check_from_target, context, dev, g9, oracle_case,
+                             scene, vkw)
 
 pytestmark = pytest.mark.gpu
 
@@ -39,80 +40,8 @@ F = np.float32
 WIDE = ((0.0, 16.0), 128.25, 0.0, (8208, 16))  # 513 tile columns: the generic list builder
 
 
-def _torch():
-    import torch
-    return torch
-
-
-def dev(a):
-    """numpy -> device tensor, complete before the library's stream may read it."""
-    torch = _torch()
-    x = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    torch.cuda.synchronize()
-    return x
-
-
-@functools.lru_cache(maxsize=None)
-def scene(name):
-    return {"M": V.scene_m, "A": V.scene_a}[name]()
-
-
-def context(splats, width=W, height=H, **kw):
-    t = S2D.Trainer(width, height, len(splats), **kw)
-    t.set_target_synthetic()
-    t.set_splats(np.ascontiguousarray(splats).view(S2D.SPLAT_DTYPE))
-    return t
-
-
-def vkw(view, samples=1):
-    origin, zoom, fv, (ow, oh) = view
-    return dict(out_width=ow, out_height=oh, origin=origin, zoom=zoom, filter_var=fv, samples=samples)
-
-
-def assert_pinned(view, samples):
-    origin, zoom, fv, _ = view
-    assert V.scales_in_pinned_range(V.view_rows(scene("M"), origin, zoom, fv, samples))
-
-
-def g9(a):
-    return G.rows9(a)
-
-
 # 1 ---------------------------------------------------------------------------------------------------------------------------
-def second_context_grads(records, gw, gh, upstream, skip, alive=None, **kw):
-    with context(records, gw, gh, deterministic=True, **kw) as t2:
-        if alive is not None:
-            t2.set_alive(alive)
-        t2.forward()
-        u = dev(upstream)
-        t2.backward_image_grads(u.data_ptr(), skip_opacity_grad=skip)
-        return t2.get_grads()
-
-
-def check_against_second_context(name, view, samples, skip=False, dead=False, pinned=True, **kw):
-    if pinned:
-        assert_pinned(view, samples)
-    origin, zoom, fv, (ow, oh) = view
-    alive = (np.arange(N) % 3 != 0) if dead else None
-    up = G.signed_upstream(oh, ow, seed=samples)
-    assert (up < 0).any() and not up[:, : ow // 3].any()
-    with context(scene(name), deterministic=True, **kw) as t:
-        if dead:
-            t.set_alive(alive)
-        records = t.view_splats(ow, oh, origin, zoom, fv, samples)
-        u = dev(up)
-        got = t.view_grads(u.data_ptr(), skip_opacity_grad=skip, **vkw(view, samples))
-        again = t.view_grads(u.data_ptr(), skip_opacity_grad=skip, **vkw(view, samples))
-    want = second_context_grads(records, ow * samples, oh * samples, G.expand(up, samples), skip, alive, **kw)
-    assert np.abs(g9(want)).max() > 0
-    assert got.tobytes() == want.tobytes()
-    assert again.tobytes() == got.tobytes()  # the buffer is zeroed per call, the slots are re-stamped
-    if skip:
-        assert not got["opacity"].any()
-    if dead:
-        assert not g9(got)[~alive].any()
-
-
+# (the second context: view_grad_cases.check_against_second_context)
 PAIRS = [(0, 1), (0, 2), (0, 4), (1, 1), (1, 2), (2, 1), (2, 2), (2, 4), (3, 1), (4, 2)]
 
 
@@ -172,59 +101,11 @@ def test_the_adjoint_is_the_restatement_and_accumulates(k, samples, dead):
 # 3 ---------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("k,samples", [(0, 1), (0, 4), (2, 2)], ids=["v1_s1", "v1_s4", "v3_s2"])
 def test_from_target_is_the_upstream_of_view_minus_target(k, samples):
-    torch = _torch()
-    view = V.VIEWS[k]
-    assert_pinned(view, samples)
-    _, _, _, (ow, oh) = view
-    tgt = np.random.default_rng(k + samples).uniform(0, 1, (oh, ow, 4)).astype(F)
-    with context(scene("M"), deterministic=True) as t:
-        tg = dev(tgt)
-        img = torch.empty((oh, ow, 4), dtype=torch.float32, device="cuda")
-        torch.cuda.synchronize()
-        t.render_view_device(img.data_ptr(), **vkw(view, samples))
-        t.synchronize()
-        up = img - tg                                       # fp32, one subtraction per channel
-        torch.cuda.synchronize()
-        want = t.view_grads(up.data_ptr(), skip_opacity_grad=False, **vkw(view, samples))
-        got = t.view_grads(tg.data_ptr(), from_target=True, skip_opacity_grad=False, **vkw(view, samples))
-    assert np.abs(g9(want)).max() > 0
-    assert got.tobytes() == want.tobytes()
+    check_from_target("M", V.VIEWS[k], samples, seed=k + samples)
 
 
 # 4 ---------------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def oracle_case(k, samples, exact_exp):
-    """Oracle side, once per case: the records at the grid size, the upstream gradient of the VIEW and the statistics of the
-    oracle's backward pass from its expansion (pseudo-target method).
-    The upstream is the one the method was pinned with (tests/test_image_grads_cpu.py, tests/test_gpu_image_grads.py): the
-    gradient of the weighted Charbonnier loss of the view against a target of its size -- masked on a third of the columns,
-    signed, and spatially coherent as the gradient of an image loss is.  The last property is what gives bar (b) of grad_bars
-    its meaning: the bar compares the worst scalar of the GPU's sums with the worst scalar of the reference's sequential fp32
-    sums, and the latter grows with the number of like-signed terms of a splat.  Under white noise (the upstream of the byte
-    tests above) every sum cancels, the reference's worst scalar stays near one rounding (1.29e-7 of sum |terms| on v3 x 1)
-    and a splat with a single term, whose few-ulp regrouping error grad_bars' docstring allows, decides the GPU's
-    (1.74e-7): the bar then ranks roundings, not summation."""
-    view = V.VIEWS[k]
-    origin, zoom, fv, (ow, oh) = view
-    rows = V.view_rows(scene("M"), origin, zoom, fv, samples)
-    gw, gh = ow * samples, oh * samples
-    o = O.OracleTrainer(O.synthetic_target(gw, gh), N)
-    o.splats[:] = rows
-    O.lib().s2do_set_exact_exp(1 if exact_exp else 0)
-    try:
-        img = o.forward().copy()
-        up = IG.charbonnier_grad(V.resolve(img, samples), O.synthetic_target(ow, oh), IG.charbonnier_weights(oh, ow))
-        assert (up[..., :3] < 0).any() and (up[..., :3] > 0).any() and not up[:, : ow // 3].any()
-        pseudo = IG.pseudo_target(img, G.expand(up, samples))
-        if samples == 1:
-            up = IG.upstream_of(img, pseudo)                # the bits the oracle forms at main.cpp:616
-        o.ref = np.ascontiguousarray(pseudo)
-        w32, dsum, dabs = o.backward_stats()
-    finally:
-        O.lib().s2do_set_exact_exp(0)
-    return up, w32.view(np.float32).reshape(-1, 9).copy(), dsum, dabs
-
-
+# (the oracle side: view_grad_cases.oracle_case)
 @pytest.mark.parametrize("exact_exp", [False, True], ids=["fp32", "exact_exp"])
 @pytest.mark.parametrize("k,samples", [(0, 2), (2, 1)], ids=["v1_s2", "v3_s1"])
 def test_view_grads_meet_the_oracle_bars(k, samples, exact_exp):

@@ -99,6 +99,57 @@ def test_variant_coverage_names_the_rows_a_trace_never_dispatched(tmp_path):
     assert r.stdout.startswith("# raster kernel variants dispatched: %d of %d " % (len(RV.NAMES), len(RV.NAMES)))
 
 
+def test_variant_coverage_reads_the_view_table_too(tmp_path):
+    """The same tool with --table view and --table all: the rows of tests/view_variants.py, whose template arguments mix flags
+    and a number; a view kernel without a row counts like a missing one; the default stays the raster table."""
+    import raster_variants as RV
+    import view_variants as VV
+    tool = os.path.join(O.ROOT, "tools", "gpu_variant_coverage.py")
+    left_out = [VV.NAMES[5], VV.NAMES[-1]]
+    rows = [["void %s(unsigned int const*, float4 const*)" % n, 10 * k, 10 * k + 5] for k, n in enumerate(VV.NAMES) if n not in left_out]
+    rows.append(["void s2d::view_gradient_kernel<false,1 , false, false,false>(int)", 1, 2])   # a second dispatch, spaced otherwise
+    rows.append(["void s2d::view_transform_kernel(float const*, int)", 3, 4])                  # not a row: information only
+    rows.append(["_ZN3s2d19view_adjoint_kernelEPKfPKhiNS_9ViewXformES1_Pf.kd", 5, 6])
+    rows.append(["void s2d::adam_kernel<true>(int)", 7, 8])
+    p = str(tmp_path / "t" / "p0" / "0_kernel_trace.csv")
+    os.makedirs(os.path.dirname(p))
+    with open(p, "w") as f:
+        w = csv.writer(f)
+        w.writerow(["Kernel_Name", "Start_Timestamp", "End_Timestamp"])
+        w.writerows(rows)
+
+    def run(*table):
+        return subprocess.run([sys.executable, tool] + list(table) + [str(tmp_path / "t")], stdout=subprocess.PIPE, universal_newlines=True)
+
+    r = run("--table", "view")
+    assert r.returncode == 1
+    lines = r.stdout.splitlines()
+    assert lines[0].startswith("# view kernel variants dispatched: %d of %d " % (len(VV.NAMES) - 2, len(VV.NAMES)))
+    got = {l.split(None, 2)[2]: l.split(None, 2)[:2] for l in lines if not l.startswith("#")}
+    assert [n for n, v in got.items() if v[0] == "MISSING"] == left_out
+    assert got["s2d::view_gradient_kernel<false, 1, false, false, false>"] == ["dispatched", "2"]
+    assert got["s2d::view_transform_kernel"] == ["other", "1"] and got["s2d::view_adjoint_kernel"] == ["other", "1"]
+    assert not any("adam" in n for n in got)
+    # every row dispatched: exit status 0; a view kernel that has no row: 1 again
+    with open(p, "a") as f:
+        csv.writer(f).writerows([["void %s()" % n, 0, 1] for n in left_out])
+    r = run("--table", "view")
+    assert r.returncode == 0 and "MISSING" not in r.stdout and "NO ROW" not in r.stdout
+    assert r.stdout.startswith("# view kernel variants dispatched: %d of %d " % (len(VV.NAMES), len(VV.NAMES)))
+    r = run()                                                          # the default is the raster table: none of its rows is here
+    assert r.returncode == 1 and r.stdout.startswith("# raster kernel variants dispatched: 0 of %d " % len(RV.NAMES))
+    r = run("--table", "all")                                          # a section each; the status covers both
+    assert r.returncode == 1
+    heads = [l for l in r.stdout.splitlines() if "kernel variants dispatched" in l]
+    assert len(heads) == 2 and heads[0].startswith("# raster kernel variants dispatched: 0 of ") and \
+        heads[1].startswith("# view kernel variants dispatched: %d of %d " % (len(VV.NAMES), len(VV.NAMES)))
+    with open(p, "a") as f:
+        csv.writer(f).writerows([["void s2d::view_raster_kernel<true, 8, false, false>(int)", 0, 1]])
+    r = run("--table", "view")
+    assert r.returncode == 1 and "NO ROW" in r.stdout and "MISSING" not in r.stdout
+    assert subprocess.run([sys.executable, tool, "--table", "nothing", p], stdout=subprocess.PIPE, stderr=subprocess.PIPE).returncode != 0
+
+
 def test_one_residual_correction_gives_the_ieee_quotient():
     """csrc/s2d_walk_backward.h::div_by_recip: q = S*r; q += (S - den*q)*r with r a 1-ulp reciprocal.  What its comment claims, on
     three operand populations of the backward blend's range incl. den = 1e-15 and quotients placed next to rounding midpoints

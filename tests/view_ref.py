@@ -40,6 +40,20 @@ def scene_a(seed=11):
     return O.random_splats(N_SPLATS, SRC_W, SRC_H, seed)
 
 
+# The short end of the tile lists: scene M's splats shrunk to sx = sy = 2 (as test_far_border_is_background shrinks them), the
+# top left corner of the source at zoom 4 with a border outside it.  At 1, 2 and 4 samples per axis the raster grid (75 x 53,
+# 150 x 106, 300 x 212: partial tiles) has tiles whose lists are empty, hold exactly one entry, fewer than 32 and between 33
+# and 63 -- no list reaches a staging batch of 64 (from the footprints' rectangles: at most 43, 42, 39 entries); the
+# transformed scales are 8, 16 and 32.  tests/test_gpu_view_variants.py asserts all of it on the lists the library builds.
+SPARSE_VIEW = ((-9.5, -7.5), 4.0, 0.0, (75, 53))
+
+
+def scene_sparse():
+    s = scene_m()
+    s["sx"], s["sy"] = 2.0, 2.0
+    return s
+
+
 def view_rows(splats, origin, zoom, filter_var=0.0, samples=1):
     """The records a view rasterises."""
     s = 1 if samples == 0 else int(samples)

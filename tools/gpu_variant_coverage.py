@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
-"""Which raster kernel variants a run dispatched: the measurement that tests/raster_variants.py is true.
+"""Which kernel variants a run dispatched: the measurement that tests/raster_variants.py and tests/view_variants.py are true.
 
     rocprofv3 --kernel-trace --output-format csv -d <dir> -- python -m pytest -m gpu tests/test_gpu_raster_variants.py
-    python tools/gpu_variant_coverage.py <dir or *_kernel_trace.csv> [...] > coverage.txt
+    python tools/gpu_variant_coverage.py [--table raster|view|all] <dir or *_kernel_trace.csv> [...] > coverage.txt
 
 Reads the Kernel_Name column of every *_kernel_trace.csv given (a directory is searched for them; one file per process),
 brings the names into the form tools/kernel_resources.py prints (demangled, no argument list, no `void`), and lists every
-row of the table with the number of its dispatches.  Exit status 1 if a row was never dispatched, or a `s2d::raster_*`
-kernel without a row was.  The kernels of the raster units that are no template instantiations (gather_* of s2d_raster_det.hip,
-reference_* of s2d_raster_reference.hip, sqerr_finalize) are listed for information only.
+row of the table with the number of its dispatches.  --table: `raster` (the default) is tests/raster_variants.py, `view` is
+tests/view_variants.py, `all` is both, a section each.  Exit status 1 if a row of a chosen table was never dispatched, or a
+kernel of its templates (`s2d::raster_*`; `s2d::view_raster_kernel<`, `s2d::view_gradient_kernel<`) without a row was.  The
+kernels of the same units that are no template instantiations (gather_* of s2d_raster_det.hip, reference_* of
+s2d_raster_reference.hip, sqerr_finalize; view_transform_kernel, view_adjoint_kernel) are listed for information only.
 """
 import collections
 import csv
@@ -19,13 +21,17 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INFORMATION = re.compile(r"^s2d::(gather_|reference_|sqerr_finalize)")
+# table: (the helper module of tests/ that holds it, the prefixes of its templates' kernels, the unit's other kernels, what the unit is called)
+TABLES = {
+    "raster": ("raster_variants", ("s2d::raster_",), re.compile(r"^s2d::(gather_|reference_|sqerr_finalize)"), "raster unit"),
+    "view": ("view_variants", ("s2d::view_raster_kernel<", "s2d::view_gradient_kernel<"),
+             re.compile(r"^s2d::view_(transform|adjoint)_kernel"), "view units"),
+}
 
 
-def table():
+def table(which="raster"):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import raster_variants
-    return raster_variants.NAMES
+    return __import__(TABLES[which][0]).NAMES
 
 
 def plain(names):
@@ -66,29 +72,40 @@ def dispatched(files):
     return raw
 
 
-def coverage(files, out=sys.stdout):
+def coverage(files, out=sys.stdout, which="raster"):
+    """Writes the section of one table -> (its rows never dispatched, the dispatched kernels of its templates without a row)."""
     raw = dispatched(files)
     keys = list(raw)
     seen = collections.Counter()
     for key, name in zip(keys, plain(keys)):
         seen[name] += raw[key]
-    names = table()
+    _, prefixes, information, unit = TABLES[which]
+    names = table(which)
     missing = [n for n in names if seen[n] == 0]
-    out.write("# raster kernel variants dispatched: %d of %d (%d trace files, %d dispatches of %d kernels in all)\n"
-              % (len(names) - len(missing), len(names), len(files), sum(raw.values()), len(seen)))
+    out.write("# %s kernel variants dispatched: %d of %d (%d trace files, %d dispatches of %d kernels in all)\n"
+              % (which, len(names) - len(missing), len(names), len(files), sum(raw.values()), len(seen)))
     for n in names:
         out.write("%-10s %8d  %s\n" % ("dispatched" if seen[n] else "MISSING", seen[n], n))
-    unknown = sorted(n for n in seen if n.startswith("s2d::raster_") and n not in set(names))
+    unknown = sorted(n for n in seen if n.startswith(prefixes) and n not in set(names))
     for n in unknown:
         out.write("%-10s %8d  %s\n" % ("NO ROW", seen[n], n))
-    out.write("# the other kernels of the raster unit, for information\n")
-    for n in sorted(n for n in seen if INFORMATION.match(n)):
+    out.write("# the other kernels of the %s, for information\n" % unit)
+    for n in sorted(n for n in seen if information.match(n)):
         out.write("%-10s %8d  %s\n" % ("other", seen[n], n))
     return missing, unknown
 
 
 if __name__ == "__main__":
-    if len(sys.argv) < 2:
+    args = sys.argv[1:]
+    which = "raster"
+    if args[:1] == ["--table"]:
+        if len(args) < 2 or args[1] not in list(TABLES) + ["all"]:
+            sys.exit(__doc__)
+        which, args = args[1], args[2:]
+    if not args:
         sys.exit(__doc__)
-    missing, unknown = coverage(trace_files(sys.argv[1:]))
-    sys.exit(1 if missing or unknown else 0)
+    files, bad = trace_files(args), False
+    for w in (list(TABLES) if which == "all" else [which]):
+        missing, unknown = coverage(files, which=w)
+        bad = bad or bool(missing or unknown)
+    sys.exit(1 if bad else 0)
