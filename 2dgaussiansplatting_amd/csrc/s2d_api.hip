@@ -80,13 +80,7 @@ int s2d_create(const s2d_config* cfg, s2d_ctx** out)
     c->device = cfg->device;
     c->lr = cfg->training_rate > 0.0f ? cfg->training_rate : 0.05f; // main.cpp:715
 
-    Geometry& g = c->g;
-    g.W = cfg->width; g.H = cfg->height;
-    g.row_begin = rb; g.row_end = re;
-    g.tiles_x = (g.W + kTile - 1) / kTile;
-    g.trow0 = rb / kTile;
-    g.tiles_y = (re + kTile - 1) / kTile - g.trow0;
-    g.num_tiles = g.tiles_x * g.tiles_y;
+    const Geometry g = c->g = make_geometry(cfg->width, cfg->height, rb, re);
 
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
@@ -106,16 +100,12 @@ int s2d_create(const s2d_config* cfg, s2d_ctx** out)
     S2D_HIP(c, c->state.create(c->n, c->stream));
     S2D_HIP(c, c->d_grads_own.alloc(n * 9));
     c->d_grads = c->d_grads_own;
-    S2D_HIP(c, c->d_proj.alloc(n));
-    S2D_HIP(c, c->d_rects.alloc(n));
-    S2D_HIP(c, c->d_counts.alloc(n));
-    S2D_HIP(c, c->d_offsets.alloc(n));
     S2D_HIP(c, c->d_scan_temp.alloc(scan_temp_words((int64_t)n)));
-    S2D_HIP(c, c->lists.create(g, n, (cfg->flags & S2D_CFG_GENERIC_BINNING) != 0));
-    c->ranges.create(g, c->stream);
     const bool ref_order = (cfg->flags & S2D_CFG_REFERENCE_ORDER) != 0; // (alone decides the result: deterministic mode is off then)
-    S2D_HIP(c, c->scratch.create(ref_order ? PairScratch::Mode::ReferenceOrder : (cfg->flags & S2D_CFG_DETERMINISTIC) ? PairScratch::Mode::Deterministic
-                                           : PairScratch::Mode::Atomic, g, n, c->stream));
+    S2D_HIP(c, c->surface.create(g, n, (cfg->flags & S2D_CFG_GENERIC_BINNING) != 0,
+                                 ref_order ? PairScratch::Mode::ReferenceOrder : (cfg->flags & S2D_CFG_DETERMINISTIC) ? PairScratch::Mode::Deterministic
+                                           : PairScratch::Mode::Atomic, c->stream));
+    c->ranges.create(g, c->stream);
     c->half_images = (cfg->flags & S2D_CFG_FP16_IMAGES) != 0;
     c->pixel_bytes = c->half_images ? 8 : sizeof(float4);
     S2D_HIP(c, c->d_image0.alloc(px * c->pixel_bytes));
@@ -395,9 +385,9 @@ int s2d_get_stats(s2d_ctx* c, s2d_stats* out)
     out = &full;
     std::memset(out, 0, sizeof(*out));
     out->struct_size = caller_size;
-    out->pairs_binned = c->lists.pairs();
-    out->pairs_capacity = c->lists.capacity();
-    out->rebins = c->lists.builds();
+    out->pairs_binned = c->surface.lists().pairs();
+    out->pairs_capacity = c->surface.lists().capacity();
+    out->rebins = c->surface.lists().builds();
     out->fwd_visited = pc.fwd_visited; out->fwd_active = pc.fwd_active;
     out->bwd_visited = pc.bwd_visited; out->bwd_active = pc.bwd_active;
     out->fwd_staged = pc.fwd_staged; out->bwd_staged = pc.bwd_staged;
@@ -415,7 +405,7 @@ int s2d_get_stats(s2d_ctx* c, s2d_stats* out)
 int s2d_get_rebuild_count(const s2d_ctx* c, uint64_t* rebuilds)
 {
     if (!c || !rebuilds) return S2D_E_INVALID;
-    *rebuilds = c->lists.builds();
+    *rebuilds = c->surface.lists().builds();
     return S2D_OK;
 }
 
@@ -429,12 +419,12 @@ int s2d_debug_get_tile_lists(s2d_ctx* c, int32_t* tiles_x, int32_t* tiles_y, uin
     if (tiles_y) *tiles_y = c->g.tiles_y;
     if (offsets) {
         if (offsets_capacity < c->g.num_tiles + 1) return S2D_E_INVALID;
-        S2D_HIP(c, hipMemcpyAsync(offsets, c->lists.tile_off(), (size_t)(c->g.num_tiles + 1) * sizeof(uint32_t),
+        S2D_HIP(c, hipMemcpyAsync(offsets, c->surface.lists().tile_off(), (size_t)(c->g.num_tiles + 1) * sizeof(uint32_t),
                                   hipMemcpyDeviceToHost, c->stream));
     }
     if (list) {
-        if (list_capacity < (int64_t)c->lists.pairs()) return S2D_E_INVALID;
-        S2D_HIP(c, hipMemcpyAsync(list, c->lists.list(), (size_t)c->lists.pairs() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (list_capacity < (int64_t)c->surface.lists().pairs()) return S2D_E_INVALID;
+        S2D_HIP(c, hipMemcpyAsync(list, c->surface.lists().list(), (size_t)c->surface.lists().pairs() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     }
     S2D_HIP(c, hipStreamSynchronize(c->stream));
     return S2D_OK;

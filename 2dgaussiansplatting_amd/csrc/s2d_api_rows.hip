@@ -23,7 +23,7 @@ int s2d_halo_commit(s2d_ctx* c, const uint32_t* masks_device, int32_t rank, int3
 {
     if (!c || rank < 0 || rank > 31) return S2D_E_INVALID;
     if (int rc = coverage_refused(c, "s2d_halo_commit")) return rc;
-    if (masks_device && c->scratch.reference_order())
+    if (masks_device && c->surface.reference_order())
         return fail(c, S2D_E_INVALID, "reference order (S2D_CFG_REFERENCE_ORDER) has no slab ownership: the chains run over all splats");
     if (masks_device && (c->has_optim || c->has_frozen))
         return fail(c, S2D_E_INVALID, "slab ownership derives its hold margins from the one training_rate: clear s2d_set_optim / s2d_set_frozen first");

@@ -42,17 +42,21 @@ int view_records(s2d_ctx* c, const s2d_view_config* cfg, float** rows)
     return S2D_OK;
 }
 
+// What a pass over the view's lists as they stand works on: lists, records, hand-over and slots, the grid and the kernel variant.
+void view_walk(s2d_ctx* c, const s2d_view_config* cfg, RasterArgs* a)
+{
+    c->view.surface().fill(a, 0, c->n);
+    a->g = view_geometry(cfg->out_width, cfg->out_height, view_samples(cfg->samples));
+    a->exact_exp = (c->cfg.flags & S2D_CFG_EXACT_EXP) != 0;
+}
+
 // The raster kernel over the view's lists as they stand (queued).
 int view_raster(s2d_ctx* c, const s2d_view_config* cfg, void* out)
 {
-    const int s = view_samples(cfg->samples);
-    TileLists& lists = c->view.lists();
     ViewRasterArgs a;
-    a.tile_off = lists.tile_off(); a.list = lists.list(); a.proj = c->view.proj(); a.out = out;
-    a.g = view_geometry(cfg->out_width, cfg->out_height, s);
-    a.out_width = cfg->out_width; a.samples = s; a.rgba8 = cfg->format == S2D_VIEW_RGBA8;
-    a.exact_exp = (c->cfg.flags & S2D_CFG_EXACT_EXP) != 0;
-    a.coverage = coverage(c);
+    view_walk(c, cfg, &a.walk);
+    a.walk.coverage = coverage(c);
+    a.out = out; a.out_width = cfg->out_width; a.samples = view_samples(cfg->samples); a.rgba8 = cfg->format == S2D_VIEW_RGBA8;
     S2D_HIP(c, launch_view_raster(a, c->stream));
     return S2D_OK;
 }
@@ -61,24 +65,21 @@ int view_raster(s2d_ctx* c, const s2d_view_config* cfg, void* out)
 // for the waits of buffers that are replaced.
 int view_lists(s2d_ctx* c, const s2d_view_config* cfg)
 {
-    const int s = view_samples(cfg->samples);
-    const Geometry g = view_geometry(cfg->out_width, cfg->out_height, s);
-    if (int rc = view_alloc(c, c->view.lists_for(g, (size_t)c->n, (c->cfg.flags & S2D_CFG_GENERIC_BINNING) != 0, c->stream), "the lists")) return rc;
+    const Geometry g = view_geometry(cfg->out_width, cfg->out_height, view_samples(cfg->samples));
+    RasterSurface& surface = c->view.surface();
+    const PairScratch::Mode mode = c->surface.deterministic() ? PairScratch::Mode::Deterministic : PairScratch::Mode::Atomic; // (a view has no reference-order pass)
+    if (!surface.on(g))
+        if (int rc = view_alloc(c, surface.create(g, (size_t)c->n, (c->cfg.flags & S2D_CFG_GENERIC_BINNING) != 0, mode, c->stream), "the lists")) return rc;
     float* rows = nullptr;
     if (int rc = view_records(c, cfg, &rows)) return rc;
-    TileLists& lists = c->view.lists();
-    ProjectArgs p; // mode 0, margin 0: the exact rectangles; a dead row gets an empty one
-    p.splats = rows; p.held = c->state.held(); p.n = c->n; p.g = g; p.proj = c->view.proj(); p.counts = c->view.counts();
-    p.row_counts = lists.row_counts();
-    p.check = ContainmentCheck{c->view.rects(), nullptr};
-    S2D_HIP(c, launch_project(p, c->stream));
+    S2D_HIP(c, launch_project(surface.project_args(rows, c->state.held(), c->n, 0.0f), c->stream)); // the exact rectangles; a dead row gets an empty one
     uint64_t total = 0;
-    S2D_HIP(c, lists.count(ListInput{c->view.rects(), c->view.counts(), c->view.offsets(), 0, c->n, c->d_scan_temp}, c->stream, &total));
-    if (total > c->ranges.budget() || total >= 0xFFFF0000ull)
+    S2D_HIP(c, surface.count(0, c->n, c->d_scan_temp, &total));
+    if (total > c->ranges.budget() || total >= kMaxPairs)
         return fail(c, S2D_E_NOMEM, "the view needs %llu (tile, splat) pairs, S2D_CHUNK_PAIRS allows %llu (views are not rendered by index ranges)",
                     (unsigned long long)total, (unsigned long long)c->ranges.budget());
-    if (int rc = view_alloc(c, c->view.pairs_for(total, c->stream), "the (tile, splat) pairs")) return rc;
-    S2D_HIP(c, lists.finish(c->stream));
+    if (int rc = view_alloc(c, surface.ensure_pairs(total, false), "the (tile, splat) pairs")) return rc;
+    S2D_HIP(c, surface.finish());
     return S2D_OK;
 }
 
@@ -98,7 +99,7 @@ int view_gradient_refused(s2d_ctx* c, const s2d_view_config* cfg, const float* s
     if ((uintptr_t)src & 15u) return fail(c, S2D_E_INVALID, "%s: the image gradient (or target) must be 16-byte aligned", who);
     if (flags & ~(S2D_VIEW_BWD_FROM_TARGET | S2D_BWD_SKIP_OPACITY_GRAD)) return fail(c, S2D_E_INVALID, "%s: unknown flags %#x", who, flags);
     if (c->cfg.flags & S2D_CFG_COUNT_PAIRS) return fail(c, S2D_E_INVALID, "%s: not available with S2D_CFG_COUNT_PAIRS", who);
-    if (c->scratch.reference_order()) return fail(c, S2D_E_INVALID, "%s: not available with S2D_CFG_REFERENCE_ORDER", who);
+    if (c->surface.reference_order()) return fail(c, S2D_E_INVALID, "%s: not available with S2D_CFG_REFERENCE_ORDER", who);
     return coverage_refused(c, who); // (the view gradient kernels carry no coverage)
 }
 
@@ -107,19 +108,18 @@ int view_gradient_refused(s2d_ctx* c, const s2d_view_config* cfg, const float* s
 int view_record_grads(s2d_ctx* c, const s2d_view_config* cfg, const float* src, uint32_t flags, float** grads)
 {
     if (int rc = view_lists(c, cfg)) return rc;
-    const int s = view_samples(cfg->samples);
-    TileLists& lists = c->view.lists();
+    RasterSurface& surface = c->view.surface();
+    if (int rc = view_alloc(c, c->view.grads((size_t)c->n, c->stream, grads), "the gradient pass")) return rc;
+    if (int rc = view_alloc(c, surface.ensure_pairs(surface.lists().capacity(), true), "the gradient pass")) return rc; // the scratch, first time on these lists
     ViewGradientArgs a;
-    if (int rc = view_alloc(c, c->view.gradient_for((size_t)c->n, c->scratch.deterministic(), c->stream, &a), "the gradient pass")) return rc;
-    a.tile_off = lists.tile_off(); a.list = lists.list(); a.proj = c->view.proj();
+    view_walk(c, cfg, &a.walk);
+    a.walk.grads = *grads;
+    a.walk.need_opacity_grad = !(flags & S2D_BWD_SKIP_OPACITY_GRAD);
+    surface.backward_walk(&a.walk);
     a.src = reinterpret_cast<const float4*>(src);
-    a.g = view_geometry(cfg->out_width, cfg->out_height, s);
-    a.out_width = cfg->out_width; a.samples = s;
-    a.exact_exp = (c->cfg.flags & S2D_CFG_EXACT_EXP) != 0;
-    a.need_opacity_grad = !(flags & S2D_BWD_SKIP_OPACITY_GRAD);
+    a.out_width = cfg->out_width; a.samples = view_samples(cfg->samples);
     a.from_target = (flags & S2D_VIEW_BWD_FROM_TARGET) != 0;
     S2D_HIP(c, launch_view_gradient(a, c->stream));
-    *grads = a.grads;
     return S2D_OK;
 }
 

@@ -1,13 +1,16 @@
-// s2d_context.h -- three owners of context state whose rules used to be kept by hand across the API file (now s2d_sequence.hip): the raster's
-// scratch that is sized like the tile lists (PairScratch), the cut and the progress of a pass over index ranges
-// (IndexRanges), and the schedule and the stamps of list re-use (ListReuse).
+// s2d_context.h -- four owners of context state whose rules used to be kept by hand across the API file (now s2d_sequence.hip): the raster's
+// scratch that is sized like the tile lists (PairScratch), everything a raster grid derives from a set of records (RasterSurface),
+// the cut and the progress of a pass over index ranges (IndexRanges), and the schedule and the stamps of list re-use (ListReuse).
 // Host code only (s2d_context.hip holds no kernel); each works on the context's stream, handed over once.
 #pragma once
 
+#include <memory>
 #include <vector>
 
 #include "s2d_device.h"
+#include "s2d_lists.h"
 #include "s2d_owned.h"
+#include "s2d_ranges.h"
 
 namespace s2d {
 
@@ -15,9 +18,8 @@ namespace s2d {
 // mode, and the slots of the two modes that replace float atomics.  Both modes number their slots alike (offsets[splat] +
 // position of the tile in the splat's binned rectangle) and stamp a slot with the epoch of the backward walk that wrote
 // it, so one stamp array and one epoch counter serve whichever is on; a slot of an earlier walk, or one never written
-// (stamp 0), matches no epoch handed out here.
-// Growing is sequenced by its one caller together with TileLists (s2d_lists.h): admit() before anything happens, then,
-// with the stream idle, release() of both and alloc() of both.
+// (stamp 0), matches no epoch handed out here.  The epoch counts on for as long as the object lives, whatever becomes of the
+// slots (alloc() clears their stamps, create() for another grid releases them): no stamp meets an epoch that restarted.
 class S2D_LOCAL PairScratch {
 public:
     enum class Mode {
@@ -27,6 +29,7 @@ public:
     };
     // n: splats (>= 1); the per-tile and per-splat words are allocated and set here, the pair-sized arrays by alloc().
     // Reference order reads S2D_REFERENCE_ORDER_MAX_BYTES, the bound on its term scratch (default 32 GiB).
+    // Again, for another grid of the same splats (the caller has made the stream idle): the pair-sized arrays go.
     hipError_t create(Mode mode, const Geometry& g, size_t n, hipStream_t stream);
     bool deterministic() const { return mode_ == Mode::Deterministic; }
     bool reference_order() const { return mode_ == Mode::ReferenceOrder; }
@@ -39,6 +42,7 @@ public:
     };
     Grant admit(uint64_t need, uint64_t cap) const;
     uint64_t max_bytes() const { return max_bytes_; }
+    uint64_t capacity() const { return capacity_; } // slots allocated: 0, or what the lists have room for
     void release();
     hipError_t alloc(uint64_t slots); // stamps cleared (queued); capacity 0 is what is left if an allocation fails
 
@@ -69,6 +73,53 @@ private:
     uint64_t max_bytes_ = 32ull << 30;
     DevBuf<float> ref_terms_;               // reference order: [capacity][kRefTermsStride]
     DevBuf<float> pixel_sqerr_;
+};
+
+// Everything a raster grid derives from a set of n x 9 records: the per-splat arrays the projection writes and a list build
+// scans, the per-tile lists, and the raster's scratch.  The context has one for its training image, with its scratch from
+// the start; its views share one (ViewScratch, s2d_view.h), whose scratch arrives with the first gradient pass.
+class S2D_LOCAL RasterSurface {
+public:
+    // n: splats (>= 1).  Again, for a grid of another size: the per-splat arrays stay, what is per tile and per pair goes, behind an idle stream.
+    hipError_t create(const Geometry& g, size_t n, bool generic, PairScratch::Mode mode, hipStream_t stream);
+    bool allocated() const { return created_ || proj_; }
+    bool on(const Geometry& g) const { return created_ && g.W == g_.W && g.H == g_.H; } // ... for a grid of this size
+
+    // Mode 0 of the projection over these arrays: rectangles inflated by `margin`, pair and row counts for a build.
+    ProjectArgs project_args(const float* splats, const uint8_t* held, int n, float margin) const;
+    // A list build over the splats [first, first + n) (TileLists::count / finish; scan_temp: scan_temp_words(n) words, lent).
+    hipError_t count(int first, int n, uint32_t* scan_temp, uint64_t* pairs);
+    hipError_t finish() { return lists_->finish(stream_); }
+    // The one place where pair-sized memory grows: room for `need` (< kMaxPairs) pairs in the lists, and with_scratch: a scratch
+    // of the lists' capacity (it has that or none at all).  Nothing is allocated when both are there.  Otherwise admit() first -- a
+    // refusal (hipErrorOutOfMemory, *refused says why) comes before anything is released or launched -- then, with the stream idle,
+    // what is replaced goes before the first is allocated again.
+    hipError_t ensure_pairs(uint64_t need, bool with_scratch, PairScratch::Grant* refused = nullptr);
+
+    // What a raster pass over the lists of the splats [first, first + count) works on: lists, records and PairScratch::fill.
+    void fill(RasterArgs* a, int first, int count) const;
+    void backward_walk(RasterArgs* a) { scratch_.backward_walk(a); } // a fresh epoch for the pass's slots
+    RefOrder reference_walk(const float* splats, int n) { return scratch_.reference_walk(splats, rects_, offsets_, counts_, n); }
+
+    const TileLists& lists() const { return *lists_; }
+    ProjRec* proj() const { return proj_; }
+    TileRect* rects() const { return rects_; }
+    uint32_t* counts() const { return counts_; }
+    uint32_t* offsets() const { return offsets_; }
+    bool deterministic() const { return scratch_.deterministic(); }
+    bool reference_order() const { return scratch_.reference_order(); }
+    float* pixel_sqerr() const { return scratch_.pixel_sqerr(); }
+    uint64_t max_bytes() const { return scratch_.max_bytes(); }
+
+private:
+    Geometry g_{};
+    hipStream_t stream_ = nullptr;
+    DevBuf<ProjRec> proj_;
+    DevBuf<TileRect> rects_;
+    DevBuf<uint32_t> counts_, offsets_;
+    std::unique_ptr<TileLists> lists_{new TileLists()}; // (replaced whole with the grid)
+    PairScratch scratch_;
+    bool created_ = false;
 };
 
 // Index-range ("chunked") rendering: when the (tile, splat) pairs of a scene exceed budget() -- at the latest 2^32 - 65536,

@@ -1,15 +1,16 @@
-// s2d_context.hip -- PairScratch, IndexRanges and ListReuse (s2d_context.h).  Host code only; it queues memsets and copies.
+// s2d_context.hip -- PairScratch, RasterSurface, IndexRanges and ListReuse (s2d_context.h).  Host code only; it queues memsets and copies.
 #include "s2d_context.h"
 
 #include <climits>
 #include <cstdlib>
 
-#include "s2d_ranges.h"
-
 namespace s2d {
 
+// (The two memsets are the blocking ones, on the null stream, which `stream` -- non-blocking -- does not wait for: what makes
+// them safe is that hipMemset of device memory has completed when it returns.)
 hipError_t PairScratch::create(Mode mode, const Geometry& g, size_t n, hipStream_t stream)
 {
+    release();
     mode_ = mode, stream_ = stream;
     if (reference_order()) {
         if (const char* e = getenv("S2D_REFERENCE_ORDER_MAX_BYTES")) {
@@ -18,7 +19,7 @@ hipError_t PairScratch::create(Mode mode, const Geometry& g, size_t n, hipStream
         }
         S2D_TRY(pixel_sqerr_.alloc((size_t)g.W * (size_t)(g.row_end - g.row_begin)));
     }
-    if (deterministic()) {
+    if (deterministic() && !det_touched_) { // (per splat, zero between passes: it outlives a grid)
         S2D_TRY(det_touched_.alloc(n));
         S2D_TRY(hipMemset(det_touched_, 0, n * sizeof(uint32_t)));
     }
@@ -79,12 +80,78 @@ RefOrder PairScratch::reference_walk(const float* splats, const TileRect* rects,
     return ro;
 }
 
+hipError_t RasterSurface::create(const Geometry& g, size_t n, bool generic, PairScratch::Mode mode, hipStream_t stream)
+{
+    if (created_) {
+        S2D_TRY(hipStreamSynchronize(stream));
+        created_ = false;
+        lists_.reset(new TileLists()); // (the old grid's go before the new one's come; none of this grid until all of create() succeeded)
+    }
+    if (!proj_) {
+        S2D_TRY(proj_.alloc(n));
+        S2D_TRY(rects_.alloc(n));
+        S2D_TRY(counts_.alloc(n));
+        S2D_TRY(offsets_.alloc(n));
+    }
+    std::unique_ptr<TileLists> fresh(new TileLists()); // a failure keeps nothing of it: the next attempt may be for another grid and builder
+    S2D_TRY(fresh->create(g, n, generic));
+    S2D_TRY(scratch_.create(mode, g, n, stream));
+    lists_ = std::move(fresh);
+    g_ = g, stream_ = stream, created_ = true;
+    return hipSuccess;
+}
+
+ProjectArgs RasterSurface::project_args(const float* splats, const uint8_t* held, int n, float margin) const
+{
+    ProjectArgs a;
+    a.splats = splats; a.held = held; a.n = n; a.g = g_; a.margin = margin; a.proj = proj_; a.counts = counts_;
+    a.row_counts = lists_->row_counts();
+    a.check = ContainmentCheck{rects_, nullptr};
+    return a;
+}
+
+hipError_t RasterSurface::count(int first, int n, uint32_t* scan_temp, uint64_t* pairs)
+{
+    return lists_->count(ListInput{rects_ + first, counts_ + first, offsets_ + first, first, n, scan_temp}, stream_, pairs);
+}
+
+hipError_t RasterSurface::ensure_pairs(uint64_t need, bool with_scratch, PairScratch::Grant* refused)
+{
+    const bool grow = lists_->capacity() == 0 || need > lists_->capacity(); // (the buffers exist from the first call on, also for no pair)
+    const bool scratch = with_scratch && (grow || scratch_.capacity() != lists_->capacity());
+    if (!grow && !scratch) return hipSuccess;
+    if (need >= kMaxPairs) return hipErrorInvalidValue;
+    uint64_t cap = grow ? pair_capacity(need) : lists_->capacity();
+    if (scratch) {
+        const PairScratch::Grant grant = scratch_.admit(grow ? need : cap, cap);
+        if (!grant.slots) {
+            if (refused) *refused = grant;
+            return hipErrorOutOfMemory;
+        }
+        cap = grant.slots;
+    }
+    S2D_TRY(hipStreamSynchronize(stream_));
+    if (grow) lists_->release_pairs();
+    scratch_.release();
+    if (grow) S2D_TRY(lists_->alloc_pairs(cap));
+    if (!scratch) return hipSuccess;
+    const hipError_t e = scratch_.alloc(cap);
+    if (e != hipSuccess && grow) lists_->release_pairs(); // (capacity 0 is what is left if an allocation fails)
+    return e;
+}
+
+void RasterSurface::fill(RasterArgs* a, int first, int count) const
+{
+    a->tile_off = lists_->tile_off(), a->list = lists_->list(), a->proj = proj_ + first;
+    scratch_.fill(a, rects_, offsets_, counts_, first, count);
+}
+
 void IndexRanges::create(const Geometry& g, hipStream_t stream)
 {
     g_ = g, stream_ = stream;
     if (const char* e = getenv("S2D_CHUNK_PAIRS")) { // (never beyond 32-bit positions)
         const unsigned long long v = strtoull(e, nullptr, 10);
-        if (v > 0) budget_ = std::min<unsigned long long>(v, 0xFFFF0000ull - 1);
+        if (v > 0) budget_ = std::min<unsigned long long>(v, kMaxPairs - 1);
     }
 }
 

@@ -33,13 +33,8 @@ struct s2d_ctx {
     DevBuf<float> d_grads_own;   // gradients (AoS, the reference's layout)
     float* d_grads = nullptr;    // buffer in use (own or bound)
     // projection + binning
-    DevBuf<ProjRec> d_proj;
-    DevBuf<TileRect> d_rects;
-    DevBuf<uint32_t> d_counts;
-    DevBuf<uint32_t> d_offsets;
-    DevBuf<uint32_t> d_scan_temp;               // lent to the list builds and to s2d_halo_commit
-    TileLists lists;                            // the per-tile lists and everything only their builds use
-    PairScratch scratch;                        // the raster's hand-over and slots, sized like the lists (s2d_context.h)
+    DevBuf<uint32_t> d_scan_temp;               // lent to the list builds (the views' too) and to s2d_halo_commit
+    RasterSurface surface;                      // the training image's projection, rectangles, lists and raster scratch (s2d_context.h)
     IndexRanges ranges;                         // scenes beyond one set of lists: the cut, the carry, the progress of a pass
     Freshness fresh;         // which of target, frames, projection and lists are current (s2d_sequence.h)
     ListReuse reuse;         // when lists are rebuilt on schedule, and the stamped containment check (s2d_context.h)
@@ -137,7 +132,7 @@ S2D_LOCAL inline int whole_scene_refused(s2d_ctx* c, const char* who, bool has_r
     if (c->g.row_begin != 0 || c->g.row_end != c->g.H) return fail(c, S2D_E_INVALID, "%s: the whole image is needed, this context owns a row slab", who);
     if (c->state.kind() == SplatState::Subset::Slab) // (an alive set is no obstacle: a dead row does not exist for the passes)
         return fail(c, S2D_E_INVALID, "%s: every splat is needed, this context holds a subset (s2d_halo_commit)", who);
-    if (!has_reference_order && c->scratch.reference_order()) return fail(c, S2D_E_INVALID, "%s: not available with S2D_CFG_REFERENCE_ORDER", who);
+    if (!has_reference_order && c->surface.reference_order()) return fail(c, S2D_E_INVALID, "%s: not available with S2D_CFG_REFERENCE_ORDER", who);
     return S2D_OK;
 }
 

@@ -34,6 +34,18 @@ struct Geometry {
     int tiles_y;        // tile rows in the slab
     int num_tiles;      // tiles_x * tiles_y
 };
+// The raster grid of the rows [row_begin, row_end) of a W x H image (row_begin % kTile == 0); a view's is whole: rows [0, H).
+inline Geometry make_geometry(int W, int H, int row_begin, int row_end)
+{
+    Geometry g{};
+    g.W = W, g.H = H;
+    g.row_begin = row_begin, g.row_end = row_end;
+    g.tiles_x = (W + kTile - 1) / kTile;
+    g.trow0 = row_begin / kTile;
+    g.tiles_y = (row_end + kTile - 1) / kTile - g.trow0;
+    g.num_tiles = g.tiles_x * g.tiles_y;
+    return g;
+}
 
 struct PairCounters {
     unsigned long long fwd_visited, fwd_active, bwd_visited, bwd_active, fwd_staged, bwd_staged, fwd_wave_execs,

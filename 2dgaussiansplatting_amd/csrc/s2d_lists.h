@@ -25,8 +25,7 @@ struct ListInput {
 //
 // A build has two phases, because its caller decides between them what to do with the pair count (render by index
 // ranges, refuse, grow): count() queues the scans and a speculative emission and waits for the scans only; finish()
-// runs the builder.  Growing is the caller's to sequence, since the raster's scratch (PairScratch, s2d_context.h) has the
-// same size: with the stream idle, release_pairs() here and release() there, then alloc_pairs() here and alloc() there.
+// runs the builder.  The pair buffers are sized by RasterSurface::ensure_pairs() (s2d_context.h) alone.
 class S2D_LOCAL TileLists {
 public:
     // n: splats (>= 1).  The pair buffers come with the first alloc_pairs().

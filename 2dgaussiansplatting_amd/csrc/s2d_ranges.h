@@ -1,5 +1,6 @@
-// s2d_ranges.h -- where index-range rendering (IndexRanges, s2d_context.h) cuts the splats.  A pure function of its
-// arguments: no HIP, no state; compiled by hipcc into the library and by g++ into the tests' shim, like s2d_density.h.
+// s2d_ranges.h -- where index-range rendering (IndexRanges, s2d_context.h) cuts the splats, and how many (tile, splat) pairs
+// the buffers of a raster surface get room for.  Pure functions of their arguments: no HIP, no state; compiled by hipcc
+// into the library and by g++ into the tests' shim, like s2d_density.h.
 #pragma once
 
 #include <cstddef>
@@ -7,6 +8,16 @@
 #include <vector>
 
 namespace s2d {
+
+// What 32-bit list positions address: a set of lists holds fewer pairs than this, and no buffer has room for more.
+constexpr uint64_t kMaxPairs = 0xFFFF0000ull;
+
+// Room to allocate when `need` pairs no longer fit: a quarter to spare (growing waits for the stream), 2^16 at least, kMaxPairs at most.
+static inline uint64_t pair_capacity(uint64_t need)
+{
+    const uint64_t cap = need + need / 4 + 4096;
+    return cap < (1u << 16) ? (1u << 16) : cap > kMaxPairs ? kMaxPairs : cap;
+}
 
 // counts[i]: the (tile, splat) pairs of splat i.  Returns r with r[0] = 0 and r.back() = n: range k holds the splats
 // [r[k], r[k+1]), cut in front of the splat with which the running pair count would pass `budget`.  A range is never

@@ -25,7 +25,7 @@ public:
     bool target() const { return target_; }         // imageRef holds a target
     bool forward() const { return forward_; }       // image0 holds the framebuffer of the CURRENT parameters
     bool backward() const { return backward_; }     // ... and the gradient buffer their gradients
-    bool projection() const { return projection_; } // d_proj and d_status->rebin_needed describe the CURRENT parameters
+    bool projection() const { return projection_; } // surface.proj() and d_status->rebin_needed describe the CURRENT parameters
     bool lists() const { return lists_; }           // the tile lists are the scene's, built from the held splats
     void invalidate(Stale reach)
     {
@@ -47,7 +47,7 @@ private:
 constexpr s2d::DeviceStatus kFreshStatus{0, INT_MAX, 0, 0}; // rebin_needed 0 matches no check (sequence numbers start at 1)
 
 // ---- passes (each queues on the context's stream; the context's device is current) -----------------------------------
-// The single place where pair capacity grows (s2d_create asks for the first).
+// Room for `need` pairs in the training image's lists and scratch, or the context's error (s2d_create asks for the first).
 S2D_LOCAL int ensure_pair_capacity(s2d_ctx* c, uint64_t need);
 S2D_LOCAL int queue_forward(s2d_ctx* c);
 // upstream != nullptr: the walk starts from that dL/d(image0) instead of image0 - imageRef, and no squared error is

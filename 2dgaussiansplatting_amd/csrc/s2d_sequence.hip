@@ -15,27 +15,17 @@
 #include <cmath>
 #include <vector>
 
-// The single place where pair capacity grows: the pair buffers of the lists and the raster's scratch have one size.
-// Every one of them is released, with the stream idle, before the first is allocated again.
+// Room for `need` pairs in the training image's lists and scratch (RasterSurface::ensure_pairs), in the context's words.
 int ensure_pair_capacity(s2d_ctx* c, uint64_t need)
 {
-    if (need <= c->lists.capacity()) return S2D_OK;
-    if (need >= 0xFFFF0000ull) return fail(c, S2D_E_NOMEM, "tile lists need %llu pairs (> 2^32)", (unsigned long long)need);
-    uint64_t cap = std::max<uint64_t>(need + need / 4 + 4096, 1 << 16);
-    if (cap > 0xFFFF0000ull) cap = 0xFFFF0000ull;
-    const PairScratch::Grant grant = c->scratch.admit(need, cap); // refused before anything is released or launched
-    if (!grant.slots)
+    if (need >= kMaxPairs) return fail(c, S2D_E_NOMEM, "tile lists need %llu pairs (> 2^32)", (unsigned long long)need);
+    PairScratch::Grant refused{};
+    const hipError_t e = c->surface.ensure_pairs(need, true, &refused);
+    if (refused.refused)
         return fail(c, S2D_E_NOMEM, "the term scratch of S2D_CFG_REFERENCE_ORDER needs %llu bytes for %llu (tile, splat) pairs, "
-                    "S2D_REFERENCE_ORDER_MAX_BYTES allows %llu", (unsigned long long)grant.bytes, (unsigned long long)grant.refused,
-                    (unsigned long long)c->scratch.max_bytes());
-    cap = grant.slots;
-    S2D_HIP(c, hipStreamSynchronize(c->stream));
-    c->lists.release_pairs();
-    c->scratch.release();
-    S2D_HIP(c, c->lists.alloc_pairs(cap));
-    const hipError_t scratch_alloc = c->scratch.alloc(cap);
-    if (scratch_alloc != hipSuccess) c->lists.release_pairs(); // (capacity 0 is what is left if an allocation fails)
-    S2D_HIP(c, scratch_alloc);
+                    "S2D_REFERENCE_ORDER_MAX_BYTES allows %llu", (unsigned long long)refused.bytes, (unsigned long long)refused.refused,
+                    (unsigned long long)c->surface.max_bytes());
+    if (e != hipSuccess) return fail(c, S2D_E_HIP, "growing the pair buffers to %llu pairs failed: %s", (unsigned long long)need, hipGetErrorString(e));
     return S2D_OK;
 }
 
@@ -50,14 +40,13 @@ int rebuild_lists(s2d_ctx* c, int first = 0, int count = -1, bool* need_ranges =
     const int n = count < 0 ? c->n : count;
     uint64_t total = 0;
     c->fresh.lists_in_the_making();
-    S2D_HIP(c, c->lists.count(ListInput{c->d_rects + first, c->d_counts + first, c->d_offsets + first, first, n, c->d_scan_temp},
-                              c->stream, &total));
+    S2D_HIP(c, c->surface.count(first, n, c->d_scan_temp, &total));
     if (need_ranges) *need_ranges = total > c->ranges.budget();
     if (need_ranges && *need_ranges) return S2D_OK;
-    if (total >= 0xFFFF0000ull)
+    if (total >= kMaxPairs)
         return fail(c, S2D_E_NOMEM, "the tile lists of splats %d..%d need more than 2^32 - 65536 (tile, splat) pairs", first, first + n - 1);
     if (int rc = ensure_pair_capacity(c, total)) return rc;
-    S2D_HIP(c, c->lists.finish(c->stream));
+    S2D_HIP(c, c->surface.finish());
     c->fresh.lists_built(count < 0);
     return S2D_OK;
 }
@@ -68,11 +57,10 @@ RasterArgs raster_args(const s2d_ctx* c, int range = -1)
 {
     const int first = range < 0 ? 0 : c->ranges.first(range), count = range < 0 ? c->n : c->ranges.size(range);
     RasterArgs a;
-    a.tile_off = c->lists.tile_off(); a.list = c->lists.list();
-    a.proj = c->d_proj + first; a.grads = c->d_grads + (size_t)first * 9;
+    c->surface.fill(&a, first, count);
+    a.grads = c->d_grads + (size_t)first * 9;
     a.image0 = c->d_image0; a.image_ref = c->d_ref; a.tile_sqerr = c->trace.tile_sqerr();
     a.g = c->g; a.status = c->d_status; a.iteration = c->iterations; a.counters = c->d_counters;
-    c->scratch.fill(&a, c->d_rects, c->d_offsets, c->d_counts, first, count);
     c->ranges.fill(&a, range);
     a.half_images = c->half_images; a.count = (c->cfg.flags & S2D_CFG_COUNT_PAIRS) != 0; a.exact_exp = (c->cfg.flags & S2D_CFG_EXACT_EXP) != 0;
     a.coverage = coverage(c);
@@ -83,10 +71,9 @@ RasterArgs raster_args(const s2d_ctx* c, int range = -1)
 // counts for a list build; otherwise (mode 1): that containment check against those rectangles.
 ProjectArgs project_args(const s2d_ctx* c, const float* splats, const ContainmentCheck* check)
 {
-    ProjectArgs a;
-    a.splats = splats; a.held = c->state.held(); a.n = c->n; a.g = c->g; a.mode = check ? 1 : 0; a.proj = c->d_proj; a.counts = c->d_counts;
-    a.check = check ? *check : ContainmentCheck{c->d_rects, c->d_status};
-    if (!check) a.margin = c->reuse.margin(), a.row_counts = c->lists.row_counts();
+    ProjectArgs a = c->surface.project_args(splats, c->state.held(), c->n, check ? 0.0f : c->reuse.margin());
+    a.check.status = c->d_status;
+    if (check) a.mode = 1, a.row_counts = nullptr, a.check = *check;
     return a;
 }
 
@@ -99,9 +86,9 @@ AdamArgs adam_args(s2d_ctx* c, uint32_t flags, bool project)
     a.held_ids = st.held_ids; a.held_count = st.held_count; a.dormant = st.dormant; a.n = c->n; a.g = c->g;
     a.beta1t = c->beta1t; a.beta2t = c->beta2t; a.lr = c->lr; a.iteration = c->iterations;
     a.mode = ((flags & S2D_STEP_OPTIMIZE_OPACITY) ? 1 : 0) | ((c->cfg.flags & S2D_CFG_ADAM_FP32) ? 2 : 0);
-    a.proj = project ? (ProjRec*)c->d_proj : nullptr;
+    a.proj = project ? c->surface.proj() : nullptr;
     a.proj_current = c->fresh.projection(); // (every event that replaces parameters clears it)
-    a.check = project ? c->reuse.next_check(c->d_rects, c->d_status) : c->reuse.idle_check(c->d_rects, c->d_status);
+    a.check = project ? c->reuse.next_check(c->surface.rects(), c->d_status) : c->reuse.idle_check(c->surface.rects(), c->d_status);
     a.sq = c->trace.take_for_adam();
     if (c->has_optim || c->has_frozen) { // the second instantiation: the nine per-field rates of this iteration, the mask
         float group[kOptimGroups];
@@ -114,7 +101,7 @@ AdamArgs adam_args(s2d_ctx* c, uint32_t flags, bool project)
 }
 
 // The pass has a backward walk (deterministic mode: with a fresh stamp for its slots).
-void with_backward_walk(s2d_ctx* c, RasterArgs& a, bool need_opacity_grad) { a.need_opacity_grad = need_opacity_grad, c->scratch.backward_walk(&a); }
+void with_backward_walk(s2d_ctx* c, RasterArgs& a, bool need_opacity_grad) { a.need_opacity_grad = need_opacity_grad, c->surface.backward_walk(&a); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Index-range ("chunked") rendering.  The reference's loops have no limit on the number of (pixel, splat) pairs
@@ -216,7 +203,7 @@ int queue_raster(s2d_ctx* c, const RasterJob& job)
     bool stored_image0 = !job.fused || job.write_image; // a fused launch told not to store image0 leaves an older frame there
     if (!scheduled) {
         if (!c->fresh.projection()) { // parameters changed without a fused projection: project + check now
-            const ContainmentCheck check = c->reuse.next_check(c->d_rects, c->d_status);
+            const ContainmentCheck check = c->reuse.next_check(c->surface.rects(), c->d_status);
             if (int rc = queue_project(c, &check)) return rc;
             S2D_HIP(c, c->reuse.check_queued());
             c->fresh.projected();
@@ -236,14 +223,14 @@ int queue_raster(s2d_ctx* c, const RasterJob& job)
         if (need_ranges && coverage(c))
             return fail(c, S2D_E_NOMEM, "the coverage channel (S2D_CFG_COVERAGE) is not available for scenes beyond %llu (tile, splat) pairs",
                         (unsigned long long)c->ranges.budget());
-        if (need_ranges && c->scratch.reference_order())
+        if (need_ranges && c->surface.reference_order())
             return fail(c, S2D_E_NOMEM, "reference order (S2D_CFG_REFERENCE_ORDER) is not available for scenes beyond %llu (tile, splat) pairs",
                         (unsigned long long)c->ranges.budget());
         c->fresh.projected();
         c->reuse.lists_rebuilt();
         if (need_ranges) {
             // more pairs than one set of lists may hold: render by index ranges (every pass rebuilds: the last range's lists are no lists of the scene)
-            S2D_HIP(c, c->ranges.plan(c->d_counts, c->n));
+            S2D_HIP(c, c->ranges.plan(c->surface.counts(), c->n));
             if ((rc = chunked_forward(c)) != S2D_OK) return rc;
             if (job.fused && (rc = chunked_backward(c, job.need_opacity_grad)) != S2D_OK) return rc;
             stored_image0 = true; // the forward pass over the ranges always stores it
@@ -278,10 +265,10 @@ static int queue_backward_reference(s2d_ctx* c, bool need_opacity_grad, const fl
     a.need_opacity_grad = need_opacity_grad;
     SplatState::Arrays now;
     S2D_HIP(c, c->state.current(&now));
-    const RefOrder ro = c->scratch.reference_walk(now.splats, c->d_rects, c->d_offsets, c->d_counts, c->n);
+    const RefOrder ro = c->surface.reference_walk(now.splats, c->n);
     S2D_HIP(c, launch_reference_backward(a, ro, c->stream));
     if (upstream) return backward_queued(c, SqerrBy::NoLoss);
-    S2D_HIP(c, launch_reference_sqerr(c->scratch.pixel_sqerr(), (size_t)c->g.W * (size_t)(c->g.row_end - c->g.row_begin),
+    S2D_HIP(c, launch_reference_sqerr(c->surface.pixel_sqerr(), (size_t)c->g.W * (size_t)(c->g.row_end - c->g.row_begin),
                                       c->trace.job(c->iterations).out, c->d_status, c->iterations, c->stream));
     return backward_queued(c, SqerrBy::PassItself);
 }
@@ -293,7 +280,7 @@ int parse_walk_flags(s2d_ctx* c, uint32_t flags, bool step, WalkFlags* out)
 {
     out->need_opacity_grad = step ? (flags & S2D_STEP_OPTIMIZE_OPACITY) != 0 : !(flags & S2D_BWD_SKIP_OPACITY_GRAD);
     out->density = (flags & (step ? S2D_STEP_DENSITY_STATS : S2D_BWD_DENSITY_STATS)) != 0;
-    if (out->density && ((c->cfg.flags & (S2D_CFG_COUNT_PAIRS | S2D_CFG_EXACT_EXP | S2D_CFG_COVERAGE)) || c->scratch.reference_order()))
+    if (out->density && ((c->cfg.flags & (S2D_CFG_COUNT_PAIRS | S2D_CFG_EXACT_EXP | S2D_CFG_COVERAGE)) || c->surface.reference_order()))
         return fail(c, S2D_E_INVALID, "density statistics are not available with S2D_CFG_COUNT_PAIRS, S2D_CFG_EXACT_EXP, "
                     "S2D_CFG_REFERENCE_ORDER or S2D_CFG_COVERAGE");
     return S2D_OK;
@@ -306,7 +293,7 @@ int parse_walk_flags(s2d_ctx* c, uint32_t flags, bool step, WalkFlags* out)
 int queue_backward(s2d_ctx* c, bool need_opacity_grad, const float4* upstream, bool density)
 {
     if (!c->fresh.forward()) return fail(c, S2D_E_STATE, "the backward pass needs s2d_forward on the current parameters");
-    if (c->scratch.reference_order()) return queue_backward_reference(c, need_opacity_grad, upstream);
+    if (c->surface.reference_order()) return queue_backward_reference(c, need_opacity_grad, upstream);
     if (density && c->ranges.active())
         return fail(c, S2D_E_NOMEM, "density statistics are not available for scenes beyond %llu (tile, splat) pairs (index-range rendering)",
                     (unsigned long long)c->ranges.budget());
@@ -327,7 +314,7 @@ int queue_backward(s2d_ctx* c, bool need_opacity_grad, const float4* upstream, b
 // separate ones (image0 stored every time, whatever write_image says).
 int queue_forward_backward(s2d_ctx* c, bool need_opacity_grad, bool write_image)
 {
-    if ((c->cfg.flags & S2D_CFG_COUNT_PAIRS) || c->scratch.reference_order() || coverage(c)) { // (reference order: its backward pass is a launch of its own)
+    if ((c->cfg.flags & S2D_CFG_COUNT_PAIRS) || c->surface.reference_order() || coverage(c)) { // (reference order: its backward pass is a launch of its own)
         if (int rc = queue_forward(c)) return rc;
         return queue_backward(c, need_opacity_grad);
     }

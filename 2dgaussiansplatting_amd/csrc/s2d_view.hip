@@ -149,20 +149,21 @@ namespace {
 template <bool EXACT, int S>
 void launch_view_format(const ViewRasterArgs& a, hipStream_t stream)
 {
-    const dim3 grid((unsigned)a.g.num_tiles), block(256);
+    const RasterArgs& w = a.walk;
+    const dim3 grid((unsigned)w.g.num_tiles), block(256);
     if constexpr (!EXACT) { // (the coverage kernels exist with exp_approx alone: launch_view_raster)
-        if (a.coverage) {
+        if (w.coverage) {
             if (a.rgba8)
-                hipLaunchKernelGGL((view_raster_kernel<false, S, true, true>), grid, block, 0, stream, a.tile_off, a.list, a.proj, a.out, a.g, a.out_width);
+                hipLaunchKernelGGL((view_raster_kernel<false, S, true, true>), grid, block, 0, stream, w.tile_off, w.list, w.proj, a.out, w.g, a.out_width);
             else
-                hipLaunchKernelGGL((view_raster_kernel<false, S, false, true>), grid, block, 0, stream, a.tile_off, a.list, a.proj, a.out, a.g, a.out_width);
+                hipLaunchKernelGGL((view_raster_kernel<false, S, false, true>), grid, block, 0, stream, w.tile_off, w.list, w.proj, a.out, w.g, a.out_width);
             return;
         }
     }
     if (a.rgba8)
-        hipLaunchKernelGGL((view_raster_kernel<EXACT, S, true>), grid, block, 0, stream, a.tile_off, a.list, a.proj, a.out, a.g, a.out_width);
+        hipLaunchKernelGGL((view_raster_kernel<EXACT, S, true>), grid, block, 0, stream, w.tile_off, w.list, w.proj, a.out, w.g, a.out_width);
     else
-        hipLaunchKernelGGL((view_raster_kernel<EXACT, S, false>), grid, block, 0, stream, a.tile_off, a.list, a.proj, a.out, a.g, a.out_width);
+        hipLaunchKernelGGL((view_raster_kernel<EXACT, S, false>), grid, block, 0, stream, w.tile_off, w.list, w.proj, a.out, w.g, a.out_width);
 }
 
 template <bool EXACT>
@@ -181,9 +182,9 @@ hipError_t launch_view_samples(const ViewRasterArgs& a, hipStream_t stream)
 
 hipError_t launch_view_raster(const ViewRasterArgs& a, hipStream_t stream)
 {
-    if (a.g.num_tiles <= 0) return hipErrorInvalidValue;
-    if (a.coverage && a.exact_exp) return hipErrorInvalidValue; // a missing kernel is an error
-    return a.exact_exp ? launch_view_samples<true>(a, stream) : launch_view_samples<false>(a, stream);
+    if (a.walk.g.num_tiles <= 0) return hipErrorInvalidValue;
+    if (a.walk.coverage && a.walk.exact_exp) return hipErrorInvalidValue; // a missing kernel is an error
+    return a.walk.exact_exp ? launch_view_samples<true>(a, stream) : launch_view_samples<false>(a, stream);
 }
 
 } // namespace s2d

@@ -122,12 +122,13 @@ namespace {
 template <bool EXACT, int S>
 hipError_t launch_view_gradient_flags(const ViewGradientArgs& a, hipStream_t stream)
 {
-    const dim3 grid((unsigned)a.g.num_tiles), block(256);
+    const RasterArgs& w = a.walk;
+    const dim3 grid((unsigned)w.g.num_tiles), block(256);
     const std::false_type no; // flags the view has no variants of: pair counting, fp16 images
     return with_variant([&](auto, auto, auto, auto op, auto d, auto ft) {
-        hipLaunchKernelGGL((view_gradient_kernel<EXACT, S, op, d, ft>), grid, block, 0, stream, a.tile_off, a.list, a.proj, a.src,
-                           a.wave_masks, a.exec_list, a.tile_exec, a.retire_hint, a.grads, a.g, a.out_width, det_slots(a.det));
-    }, std::bool_constant<EXACT>{}, no, no, a.need_opacity_grad, a.det.now != 0u, a.from_target);
+        hipLaunchKernelGGL((view_gradient_kernel<EXACT, S, op, d, ft>), grid, block, 0, stream, w.tile_off, w.list, w.proj, a.src,
+                           w.wave_masks, w.exec_list, w.tile_exec, w.retire_hint, w.grads, w.g, a.out_width, det_slots(w.det));
+    }, std::bool_constant<EXACT>{}, no, no, w.need_opacity_grad, w.det.now != 0u, a.from_target);
 }
 
 template <bool EXACT>
@@ -145,13 +146,10 @@ hipError_t launch_view_gradient_samples(const ViewGradientArgs& a, hipStream_t s
 
 hipError_t launch_view_gradient(const ViewGradientArgs& a, hipStream_t stream)
 {
-    if (a.g.num_tiles <= 0) return hipErrorInvalidValue;
-    const hipError_t e = a.exact_exp ? launch_view_gradient_samples<true>(a, stream) : launch_view_gradient_samples<false>(a, stream);
+    if (a.walk.g.num_tiles <= 0) return hipErrorInvalidValue;
+    const hipError_t e = a.walk.exact_exp ? launch_view_gradient_samples<true>(a, stream) : launch_view_gradient_samples<false>(a, stream);
     if (e != hipSuccess) return e;
-    RasterArgs gather; // deterministic mode: the slots of the view's rectangles, summed in slot order into a.grads
-    gather.grads = a.grads;
-    gather.det = a.det;
-    return launch_det_gather(gather, stream);
+    return launch_det_gather(a.walk, stream); // deterministic mode: the slots of the view's rectangles, summed in slot order into walk.grads
 }
 
 hipError_t launch_view_adjoint(const float* splats, const uint8_t* held, int n, ViewXform x, const float* view_grads, float* grads,

@@ -10,3 +10,7 @@ extern "C" int ir_cut(const uint32_t* counts, int n, uint64_t budget, int32_t* o
     for (size_t k = 0; k < r.size(); k++) out[k] = r[k];
     return (int)r.size();
 }
+
+// The growth rule of pair-sized memory (RasterSurface::ensure_pairs) and the bound it clamps at.
+extern "C" uint64_t ir_pair_capacity(uint64_t need) { return s2d::pair_capacity(need); }
+extern "C" uint64_t ir_max_pairs(void) { return s2d::kMaxPairs; }

@@ -28,7 +28,7 @@ import test_image_grads_cpu as IG
 import view_grad_ref as G
 import view_ref as V
 from view_grad_cases import (_torch, assert_pinned, check_against_second_context, check_from_target, context, dev, g9, oracle_case,
-                             scene, vkw)
+                             scene, second_context_list_lengths, vkw)
 
 pytestmark = pytest.mark.gpu
 
@@ -392,3 +392,57 @@ def test_release_and_calls_of_changing_size():
         assert [grads(0, 4), grads(4, 2), grads(5, 1), grads(2, 2)] == others
         t.view_release()
         t.view_release()                                                 # nothing to free: fine
+
+
+# 10 --------------------------------------------------------------------------------------------------------------------------
+def test_the_scratch_arrives_after_the_lists_and_follows_their_growth():
+    """The seam between a view's lists and its raster scratch (RasterSurface::ensure_pairs): a render allocates lists alone, the
+    first gradient pass on them brings the scratch to their capacity, lists that grow release it and the next gradient pass
+    makes it follow.  One deterministic context on scene M goes through
+      (a) render view 1 x 1        (b) view_grads of it: the scratch arrives at an unchanged list capacity
+      (c) render view 1 x 4        (d) view_grads of it
+    -- each of these is a call on a grid of another size, which creates lists and scratch anew -- and then, on ONE grid (160 x 96
+    at 4 samples, the origin of view 6), where lists and scratch live on from call to call:
+      (g) view_grads at zoom 0.5: fewer than 65536 pairs, lists of the first capacity and a scratch of it
+      (h) render at zoom 16 (view 6): more than 65536 pairs, the lists grow and the scratch goes
+      (i) view_grads at zoom 16: the scratch follows the lists
+      (j) view_grads at zoom 0.5 again: nothing grows, few pairs in lists and scratch of the large capacity
+    and back:
+      (e) view_grads of view 1 x 1 again
+      (f) step(2)
+    Every view call returns the bytes of the same call made first in a fresh context, and (f) leaves the trace, the splats, the
+    Adam state and the image of a twin that never drew a view.  No tolerance anywhere.  The pair counts are printed and the two of
+    the shared grid asserted to lie on either side of 65536, from the lists a second context builds for the same records and grid
+    (view 1 x 4 stays below it: by themselves (a) to (d) grow nothing)."""
+    v1, far, near = V.VIEWS[0], (V.VIEWS[5][0], 0.5, 0.0, V.VIEWS[5][3]), V.VIEWS[5]
+    pairs = [int(second_context_list_lengths("M", v, s).sum()) for v, s in ((v1, 1), (v1, 4), (far, 4), (near, 4))]
+    print("\n[scratch seam] (tile, splat) pairs: view 1 x 1 %d, view 1 x 4 %d; 160 x 96 x 4 at zoom 0.5 %d, at zoom 16 %d" % tuple(pairs))
+    assert 0 < pairs[2] <= 1 << 16 < pairs[3]
+    ups = {size: dev(G.signed_upstream(size[1], size[0], seed=3)) for size in (v1[3], near[3])}
+
+    def render(t, view, samples):
+        return t.render_view(**vkw(view, samples)).tobytes()
+
+    def grads(t, view, samples):
+        return t.view_grads(ups[view[3]].data_ptr(), skip_opacity_grad=False, **vkw(view, samples)).tobytes()
+
+    def state(t):
+        ad = t.get_adam()
+        return (t.get_splats().tobytes(), ad[0].tobytes(), (float(ad[1]), float(ad[2]), ad[3]), t.get_image().tobytes())
+
+    calls = [(render, v1, 1), (grads, v1, 1), (render, v1, 4), (grads, v1, 4),
+             (grads, far, 4), (render, near, 4), (grads, near, 4), (grads, far, 4), (grads, v1, 1)]
+    want = {}
+    for call in calls:                                        # (two of the nine are repeated)
+        if call not in want:
+            with context(scene("M"), deterministic=True) as fresh:
+                want[call] = call[0](fresh, *call[1:])
+    assert len(want) == 7 and all(np.frombuffer(w, dtype=F).any() for w in want.values())
+    assert want[(grads, far, 4)] != want[(grads, near, 4)]
+    with context(scene("M"), deterministic=True) as t, context(scene("M"), deterministic=True) as twin:
+        for k, call in enumerate(calls):
+            assert call[0](t, *call[1:]) == want[call], (k, call[0].__name__, call[1][1], call[2])
+        a, b = t.step(2), twin.step(2)
+        assert a.tobytes() == b.tobytes() and np.isfinite(a).all()
+        assert state(t) == state(twin)
+        assert t.get_splats().tobytes() != scene("M").tobytes()

@@ -37,6 +37,9 @@ def cut(counts, budget):
         _shim = C.CDLL(so)
         _shim.ir_cut.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p]
         _shim.ir_cut.restype = C.c_int
+        _shim.ir_pair_capacity.argtypes = [C.c_uint64]
+        _shim.ir_pair_capacity.restype = C.c_uint64
+        _shim.ir_max_pairs.restype = C.c_uint64
     c = np.ascontiguousarray(counts, dtype=np.uint32)
     out = np.full(len(c) + 3, -1, dtype=np.int32)
     k = _shim.ir_cut(c.ctypes.data_as(C.c_void_p), len(c), int(budget), out.ctypes.data_as(C.c_void_p))
@@ -113,3 +116,39 @@ def test_cut_index_ranges_under_address_and_undefined_behaviour_sanitizers(tmp_p
         raw = open(dst, "rb").read()
         k = struct.unpack_from("<i", raw)[0]
         assert np.frombuffer(raw[4:], dtype="<i4").tolist() == cut(counts, budget) and k * 4 + 4 == len(raw), name
+
+
+# ---- the growth rule of pair-sized memory (s2d_ranges.h pair_capacity, kMaxPairs) ---------------------------------------------
+MAX_PAIRS = 0xFFFF0000
+
+
+def parent_capacity(need):
+    """The expression that stood at each place where pair-sized memory grew before there was one function for it (the context's
+    lists and scratch, a view's lists): cap = max(need + need / 4 + 4096, 1 << 16); if (cap > 0xFFFF0000) cap = 0xFFFF0000."""
+    return min(max(need + need // 4 + 4096, 1 << 16), 0xFFFF0000)
+
+
+def pair_capacity(need):
+    cut([], 1)  # (loads the shim)
+    return int(_shim.ir_pair_capacity(int(need)))
+
+
+# need -> capacity; 65536 -> 86016 is the first growth of a context that starts with 2^16 pairs (profiles/r08/README.md)
+GROWTH_ROWS = [(0, 65536), (1, 65536), (49152, 65536), (49153, 65537), (65536, 86016), (0xFFFF0000 - 1, 0xFFFF0000)]
+
+
+@pytest.mark.parametrize("need,capacity", GROWTH_ROWS, ids=[str(n) for n, _ in GROWTH_ROWS])
+def test_pair_capacity_rows(need, capacity):
+    assert parent_capacity(need) == capacity      # the table is the old expression's
+    assert pair_capacity(need) == capacity
+    assert int(_shim.ir_max_pairs()) == MAX_PAIRS
+
+
+def test_pair_capacity_is_the_old_expression_monotone_and_sufficient():
+    """Powers of two +- 1 up to the bound: the old expression's value, capacity >= need, never beyond the bound, never falling."""
+    needs = sorted({min(max((1 << k) + d, 0), MAX_PAIRS - 1) for k in range(33) for d in (-1, 0, 1)} | {49152, 49153, MAX_PAIRS - 1})
+    caps = [pair_capacity(n) for n in needs]
+    assert caps == [parent_capacity(n) for n in needs]
+    assert all(n <= c <= MAX_PAIRS for n, c in zip(needs, caps))
+    assert all(a <= b for a, b in zip(caps, caps[1:]))
+    assert caps[0] == 1 << 16 and caps[-1] == MAX_PAIRS
