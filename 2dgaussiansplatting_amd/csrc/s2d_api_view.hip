@@ -9,8 +9,8 @@
 
 #include "../../include/splat2d_test.h"
 
-namespace {
-
+// (view_alloc, view_lists, the two view_pass_*_refused, view_backward_prepare and view_adjoint are shared with
+// s2d_api_coarse.hip: s2d_ctx.h)
 // A failed allocation of the view's scratch: S2D_E_NOMEM when the device is out of memory, S2D_E_HIP otherwise.
 int view_alloc(s2d_ctx* c, hipError_t e, const char* what)
 {
@@ -19,6 +19,8 @@ int view_alloc(s2d_ctx* c, hipError_t e, const char* what)
     if (e == hipErrorOutOfMemory) return fail(c, S2D_E_NOMEM, "no device memory for %s of the view", what);
     return fail(c, S2D_E_HIP, "allocating %s of the view failed: %s", what, hipGetErrorString(e));
 }
+
+namespace {
 
 // Everything the view calls (`who`) refuse for the configuration or the context, before any device work (S2D_E_INVALID).
 int view_refused(s2d_ctx* c, const s2d_view_config* cfg, const char* who)
@@ -61,6 +63,8 @@ int view_raster(s2d_ctx* c, const s2d_view_config* cfg, void* out)
     return S2D_OK;
 }
 
+} // namespace
+
 // The records, the projection and the lists of the view.  Queued, but for the one wait of a list build (the pair count) and
 // for the waits of buffers that are replaced.
 int view_lists(s2d_ctx* c, const s2d_view_config* cfg)
@@ -83,6 +87,50 @@ int view_lists(s2d_ctx* c, const s2d_view_config* cfg)
     return S2D_OK;
 }
 
+// What the passes with a backward walk through a view (`who`) refuse, before any device work (S2D_E_INVALID): for the
+// configuration, and for the context.
+int view_pass_config_refused(s2d_ctx* c, const s2d_view_config* cfg, const char* who)
+{
+    if (int rc = view_refused(c, cfg, who)) return rc;
+    if (cfg->format != S2D_VIEW_RGBA32F) return fail(c, S2D_E_INVALID, "%s: the gradient of a view is RGBA32F (format S2D_VIEW_RGBA32F)", who);
+    return S2D_OK;
+}
+
+int view_pass_context_refused(s2d_ctx* c, const char* who)
+{
+    if (c->cfg.flags & S2D_CFG_COUNT_PAIRS) return fail(c, S2D_E_INVALID, "%s: not available with S2D_CFG_COUNT_PAIRS", who);
+    if (c->surface.reference_order()) return fail(c, S2D_E_INVALID, "%s: not available with S2D_CFG_REFERENCE_ORDER", who);
+    return coverage_refused(c, who); // (the view gradient kernels carry no coverage)
+}
+
+// What every pass with a backward walk through a view starts with (queued behind the list build): records, projection, lists,
+// the zeroed n x 9 gradients of the view's records (*grads), the raster scratch of the lists, and `walk` filled for the launch.
+int view_backward_prepare(s2d_ctx* c, const s2d_view_config* cfg, bool need_opacity_grad, RasterArgs* walk, float** grads)
+{
+    if (int rc = view_lists(c, cfg)) return rc;
+    RasterSurface& surface = c->view.surface();
+    if (int rc = view_alloc(c, c->view.grads((size_t)c->n, c->stream, grads), "the gradient pass")) return rc;
+    if (int rc = view_alloc(c, surface.ensure_pairs(surface.lists().capacity(), true), "the gradient pass")) return rc; // the scratch, first time on these lists
+    view_walk(c, cfg, walk);
+    walk->grads = *grads;
+    walk->need_opacity_grad = need_opacity_grad;
+    surface.backward_walk(walk);
+    return S2D_OK;
+}
+
+// The gradients of the view's records, taken back through the record transform, ADDED into the context's gradient buffer (queued).
+int view_adjoint(s2d_ctx* c, const s2d_view_config* cfg, const float* record_grads)
+{
+    SplatState::Arrays now;
+    S2D_HIP(c, c->state.current(&now));
+    S2D_HIP(c, launch_view_adjoint(now.splats, c->state.held(), c->n,
+                                   view_xform(cfg->origin_x, cfg->origin_y, cfg->zoom, cfg->filter_var, cfg->samples), record_grads,
+                                   c->d_grads, c->stream));
+    return S2D_OK;
+}
+
+namespace {
+
 // The whole view into `out` (device memory): records, projection, lists, raster.
 int view_render(s2d_ctx* c, const s2d_view_config* cfg, void* out)
 {
@@ -93,29 +141,19 @@ int view_render(s2d_ctx* c, const s2d_view_config* cfg, void* out)
 // Everything the gradient calls (`who`) refuse, before any device work (S2D_E_INVALID).
 int view_gradient_refused(s2d_ctx* c, const s2d_view_config* cfg, const float* src, uint32_t flags, const char* who)
 {
-    if (int rc = view_refused(c, cfg, who)) return rc;
-    if (cfg->format != S2D_VIEW_RGBA32F) return fail(c, S2D_E_INVALID, "%s: the gradient of a view is RGBA32F (format S2D_VIEW_RGBA32F)", who);
+    if (int rc = view_pass_config_refused(c, cfg, who)) return rc;
     if (!src) return fail(c, S2D_E_INVALID, "%s: NULL image gradient (or target)", who);
     if ((uintptr_t)src & 15u) return fail(c, S2D_E_INVALID, "%s: the image gradient (or target) must be 16-byte aligned", who);
     if (flags & ~(S2D_VIEW_BWD_FROM_TARGET | S2D_BWD_SKIP_OPACITY_GRAD)) return fail(c, S2D_E_INVALID, "%s: unknown flags %#x", who, flags);
-    if (c->cfg.flags & S2D_CFG_COUNT_PAIRS) return fail(c, S2D_E_INVALID, "%s: not available with S2D_CFG_COUNT_PAIRS", who);
-    if (c->surface.reference_order()) return fail(c, S2D_E_INVALID, "%s: not available with S2D_CFG_REFERENCE_ORDER", who);
-    return coverage_refused(c, who); // (the view gradient kernels carry no coverage)
+    return view_pass_context_refused(c, who);
 }
 
 // The gradients of the view's records from `src` (dL/d(view), or the target with S2D_VIEW_BWD_FROM_TARGET) into the scratch's
 // n x 9 buffer (queued behind the list build): records, projection, lists, view_gradient_kernel, deterministic mode's gather.
 int view_record_grads(s2d_ctx* c, const s2d_view_config* cfg, const float* src, uint32_t flags, float** grads)
 {
-    if (int rc = view_lists(c, cfg)) return rc;
-    RasterSurface& surface = c->view.surface();
-    if (int rc = view_alloc(c, c->view.grads((size_t)c->n, c->stream, grads), "the gradient pass")) return rc;
-    if (int rc = view_alloc(c, surface.ensure_pairs(surface.lists().capacity(), true), "the gradient pass")) return rc; // the scratch, first time on these lists
     ViewGradientArgs a;
-    view_walk(c, cfg, &a.walk);
-    a.walk.grads = *grads;
-    a.walk.need_opacity_grad = !(flags & S2D_BWD_SKIP_OPACITY_GRAD);
-    surface.backward_walk(&a.walk);
+    if (int rc = view_backward_prepare(c, cfg, !(flags & S2D_BWD_SKIP_OPACITY_GRAD), &a.walk, grads)) return rc;
     a.src = reinterpret_cast<const float4*>(src);
     a.out_width = cfg->out_width; a.samples = view_samples(cfg->samples);
     a.from_target = (flags & S2D_VIEW_BWD_FROM_TARGET) != 0;
@@ -173,12 +211,7 @@ int s2d_view_backward_device(s2d_ctx* c, const s2d_view_config* cfg, const float
     if (int rc = use_device(c)) return rc;
     float* record_grads = nullptr;
     if (int rc = view_record_grads(c, cfg, dview_or_target_device, flags, &record_grads)) return rc;
-    SplatState::Arrays now;
-    S2D_HIP(c, c->state.current(&now));
-    S2D_HIP(c, launch_view_adjoint(now.splats, c->state.held(), c->n,
-                                   view_xform(cfg->origin_x, cfg->origin_y, cfg->zoom, cfg->filter_var, cfg->samples), record_grads,
-                                   c->d_grads, c->stream));
-    return S2D_OK;
+    return view_adjoint(c, cfg, record_grads);
 }
 
 int s2d_view_grads(s2d_ctx* c, const s2d_view_config* cfg, const float* dview_or_target_device, uint32_t flags, s2d_splat* dview_records_host)

@@ -136,6 +136,19 @@ S2D_LOCAL inline int whole_scene_refused(s2d_ctx* c, const char* who, bool has_r
     return S2D_OK;
 }
 
+// ---- what s2d_api_view.hip shares with s2d_api_coarse.hip (s2d_step_view runs a view's pass per iteration) -----------------
+// A failed allocation of the view's scratch as the context's error (hipSuccess: S2D_OK).
+S2D_LOCAL int view_alloc(s2d_ctx* c, hipError_t e, const char* what);
+// What a pass with a backward walk through a view (`who`) refuses (S2D_E_INVALID): for the configuration, for the context.
+S2D_LOCAL int view_pass_config_refused(s2d_ctx* c, const s2d_view_config* cfg, const char* who);
+S2D_LOCAL int view_pass_context_refused(s2d_ctx* c, const char* who);
+// The records, the projection and the lists of the view (queued, but for the one wait of a list build).
+S2D_LOCAL int view_lists(s2d_ctx* c, const s2d_view_config* cfg);
+// What every such pass starts with: the lists, the zeroed gradients of the view's records, the raster scratch, `walk` filled.
+S2D_LOCAL int view_backward_prepare(s2d_ctx* c, const s2d_view_config* cfg, bool need_opacity_grad, RasterArgs* walk, float** grads);
+// ... and ends with: those gradients through the adjoint of the record transform, added into the context's gradient buffer.
+S2D_LOCAL int view_adjoint(s2d_ctx* c, const s2d_view_config* cfg, const float* record_grads);
+
 // ---- what s2d_api_placement.hip shares with s2d_api_alive.hip (s2d_grow seeds the rows it brings to life) ---------------
 // Everything the seeding calls (`who`) refuse for the configuration or the context, before any device work (S2D_E_INVALID),
 // then what they refuse for the order of calls (S2D_E_STATE).

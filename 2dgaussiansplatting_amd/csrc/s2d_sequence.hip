@@ -453,6 +453,7 @@ void target_replaced(s2d_ctx* c)
 {
     c->fresh.target_set();
     c->fresh.invalidate(Stale::Frames);
+    c->view.target_stale(); // (the views' own resampled target, s2d_step_view: derived from the one replaced)
 }
 
 // Every splat is new (init / set_splats): the lists are none of theirs, and a non-finite event of the old ones no longer

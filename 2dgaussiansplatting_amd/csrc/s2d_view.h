@@ -65,10 +65,72 @@ hipError_t launch_view_gradient(const ViewGradientArgs& a, hipStream_t stream);
 hipError_t launch_view_adjoint(const float* splats, const uint8_t* held, int n, ViewXform x, const float* view_grads, float* grads,
                                hipStream_t stream);
 
+// Coarse-to-fine fitting (include/splat2d_coarse.h; s2d_view_fit.hip).
+struct ViewFitArgs {
+    // as ViewGradientArgs::walk, and tile_sqerr (one double per tile of g: every tile's is stored)
+    RasterArgs walk;
+    const float4* target = nullptr; // out_height * out_width RGBA32F, .w ignored
+    int out_width = 0;
+    int samples = 1;                // 1, 2 or 4 per axis
+};
+// view_gradient_kernel's pass from a target, with the view's squared error per tile (and deterministic mode's gather).
+hipError_t launch_view_fit(const ViewFitArgs& a, hipStream_t stream);
+// out[j][i] = view_target_pixel (s2d_view_target_math.h) of the W x H image at ref (half_images: 4 x fp16 per pixel, else RGBA32F).
+hipError_t launch_view_target(const void* ref, bool half_images, int W, int H, float origin_x, float origin_y, float zoom, int out_width,
+                              int out_height, float4* out, hipStream_t stream);
+
+// The window of a view's own target: what s2d_view_target_device depends on besides the context's target.
+struct ViewWindow {
+    int out_width = 0, out_height = 0;
+    float origin_x = 0.0f, origin_y = 0.0f, zoom = 0.0f;
+    bool operator==(const ViewWindow& o) const
+    {
+        return out_width == o.out_width && out_height == o.out_height && origin_x == o.origin_x && origin_y == o.origin_y && zoom == o.zoom;
+    }
+};
+
 // What views allocate, on first use, and keep between calls (a context that never renders a view pays nothing): the n x 9 records and
-// their gradients, the device image behind s2d_render_view, and one RasterSurface for the raster grid of the latest call.
+// their gradients, the device image behind s2d_render_view, one RasterSurface for the raster grid of the latest call, and for
+// s2d_step_view the tile errors, the ring of their sums and the library's own target of the latest window.
 class S2D_LOCAL ViewScratch {
 public:
+    static constexpr int kFitRing = 256; // iterations of s2d_step_view queued between two reads of their squared errors
+
+    // The tile errors of a view_fit pass over `num_tiles` tiles, with the zeroed scratch sqerr_reduce expects behind them (the
+    // reduction leaves it zero), and the ring of per-iteration sums.
+    hipError_t fit_errors(int num_tiles, hipStream_t stream, SqerrJob* job, double** tile_sqerr)
+    {
+        const size_t want = (size_t)num_tiles + kSqerrScratchDoubles;
+        if (fit_tiles_ != num_tiles || !tile_sqerr_) {
+            if (tile_sqerr_) (void)hipStreamSynchronize(stream);
+            fit_tiles_ = 0;
+            S2D_TRY(tile_sqerr_.alloc(want));
+            S2D_TRY(hipMemsetAsync(tile_sqerr_, 0, want * sizeof(double), stream));
+            fit_tiles_ = num_tiles;
+        }
+        if (!fit_ring_) S2D_TRY(fit_ring_.alloc(kFitRing));
+        *tile_sqerr = tile_sqerr_;
+        *job = SqerrJob{tile_sqerr_, num_tiles, fit_ring_, tile_sqerr_ + num_tiles}; // (out: the ring's first slot; the caller picks its own)
+        return hipSuccess;
+    }
+    // The library's own target of window `w` (out_height x out_width RGBA32F); *current: it holds that window of the context's
+    // target as it stands, otherwise the caller fills it (queued) and says own_target_built().
+    hipError_t own_target(const ViewWindow& w, hipStream_t stream, float4** out, bool* current)
+    {
+        const size_t pixels = (size_t)w.out_width * (size_t)w.out_height;
+        if (pixels > target_.capacity()) {
+            if (target_) (void)hipStreamSynchronize(stream);
+            target_current_ = false;
+            S2D_TRY(target_.alloc(pixels));
+        }
+        *current = target_current_ && window_ == w;
+        if (!*current) target_current_ = false, window_ = w;
+        *out = target_;
+        return hipSuccess;
+    }
+    void own_target_built() { target_current_ = true; }
+    void target_stale() { target_current_ = false; } // the context's target was replaced (target_replaced, s2d_sequence.hip)
+
     // The n x 9 records of the view.
     hipError_t rows(size_t n, float** out)
     {
@@ -95,9 +157,11 @@ public:
         (void)hipStreamSynchronize(stream);
         surface_ = RasterSurface();
         splats_.release(), image_.release(), grads_.release();
+        tile_sqerr_.release(), fit_ring_.release(), target_.release();
+        fit_tiles_ = 0, target_current_ = false;
     }
     bool has_lists(const Geometry& g) const { return surface_.on(g) && surface_.lists().list() != nullptr; }
-    bool allocated() const { return surface_.allocated() || splats_ || image_ || grads_; }
+    bool allocated() const { return surface_.allocated() || splats_ || image_ || grads_ || tile_sqerr_ || fit_ring_ || target_; }
     RasterSurface& surface() { return surface_; } // of the latest call's grid; whoever calls on another creates it again
 
 private:
@@ -105,6 +169,12 @@ private:
     DevBuf<uint4> image_;
     DevBuf<float> grads_; // [n][9]: gradients of the view's records
     RasterSurface surface_;
+    DevBuf<double> tile_sqerr_; // [fit_tiles_ + kSqerrScratchDoubles]
+    DevBuf<double> fit_ring_;   // [kFitRing]
+    int fit_tiles_ = 0;
+    DevBuf<float4> target_;     // the library's own target of window_
+    ViewWindow window_;
+    bool target_current_ = false;
 };
 
 } // namespace s2d

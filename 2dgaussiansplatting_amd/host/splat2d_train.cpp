@@ -17,16 +17,19 @@
 // boundary splat swap its gradient rows by peer-to-peer copies (slab ownership, default) or RCCL all-reduces all
 // N x 9 gradients over xGMI (--exchange dense, north_star's scheme) -- all inside the library.
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "image_io.h"
 #include "overlay.h"
 #include "splat2d.h"
+#include "splat2d_coarse.h"
 
 namespace {
 
@@ -107,6 +110,15 @@ struct Options {
     // alpha (a file without alpha, or --synthetic: alpha 1); --out-image is written as an RGBA8 PNG with straight alpha, rgb / A
     // where A > 0, otherwise 0.  One context only, the squared error only, and nothing that needs the density statistics.
     bool coverage = false;
+    // --coarse Z:K[,Z:K...]: coarse-to-fine (splat2d_coarse.h).  Stage s runs K_s iterations of s2d_step_view on the whole image
+    // at zoom Z_s -- output ceil(W Z) x ceil(H Z), origin 0, the library's own resampled target -- and prints the view's MSE in
+    // the reference's trace line; the stages cover iterations 0 .. sum K - 1 of the run (they count towards --iters, and a
+    // checkpoint loaded inside a stage continues it), s2d_view_release follows the last, the rest runs at full size as ever.
+    // --coarse-samples S: samples per axis of the views (1, 2 or 4).  One context, the squared error, and nothing that gathers
+    // density statistics.  The schedule has no defaults worth the name: which zooms and how long is provisional.
+    std::vector<std::pair<float, int>> coarse;
+    bool coarse_malformed = false;
+    int coarse_samples = 1;
     bool replicated = false;    // --exchange dense: replicated state + RCCL all-reduce of all gradients (default: slab ownership)
                                 // (RCCL takes one rank per GPU): a rehearsal of the N-rank host logic on a box with fewer GPUs
 };
@@ -169,7 +181,32 @@ int usage()
                  "  --coverage: fit the image's alpha as well (a cut-out, a sprite, a layer): the target is the file's colour times its\n"
                  "    alpha, with the alpha as a fourth channel; --out-image file.png is written as RGBA with straight alpha.  One GPU\n"
                  "    only; not with --loss-weights, --reference-order, --relocate-every, --reseed-every or --prune-every.\n");
+    std::fprintf(stderr,
+                 "  --coarse Z:K[,Z:K...] [--coarse-samples S]: coarse-to-fine, e.g. --coarse 0.25:100,0.5:100 --iters 500: the first K\n"
+                 "    iterations train a view of the whole image at zoom Z (ceil(W Z) x ceil(H Z) pixels) against the target resampled to\n"
+                 "    that size, then the next stage, then full size; the trace prints the view's MSE.  The stages count towards --iters.\n"
+                 "    One GPU only; not with --coverage, --reference-order, --loss-weights or the options that gather density\n"
+                 "    statistics (--relocate-every, --reseed-every, --prune-every, --grow-every).  The schedule is provisional.\n");
     return 2;
+}
+
+// "Z:K[,Z:K...]" -> stages; false: malformed (an empty list, a missing part, trailing characters).
+bool parse_coarse(const char* text, std::vector<std::pair<float, int>>* out)
+{
+    out->clear();
+    const char* p = text;
+    while (true) {
+        char* end = nullptr;
+        const float z = std::strtof(p, &end);
+        if (end == p || *end != ':') return false;
+        p = end + 1;
+        const long k = std::strtol(p, &end, 10);
+        if (end == p) return false;
+        out->push_back({z, (int)k});
+        if (*end == '\0') return true;
+        if (*end != ',') return false;
+        p = end + 1;
+    }
 }
 
 // One context, or a multi-device handle, behind the same calls: what main() below talks to.
@@ -334,6 +371,8 @@ int main(int argc, char** argv)
         else if (a == "--prune-min-weight") o.prune_min_weight = (float)std::atof(next("--prune-min-weight"));
         else if (a == "--prune-window") o.prune_window = std::atoi(next("--prune-window"));
         else if (a == "--coverage") o.coverage = true;
+        else if (a == "--coarse") o.coarse_malformed = !parse_coarse(next("--coarse"), &o.coarse);
+        else if (a == "--coarse-samples") o.coarse_samples = std::atoi(next("--coarse-samples"));
         else return usage();
     }
     if (!o.convert_in.empty()) { // file conversion between .s2di / .ppm / .png; touches no GPU
@@ -458,6 +497,48 @@ int main(int argc, char** argv)
             return 2;
         }
     }
+    if (o.coarse_malformed || !o.coarse.empty() || o.coarse_samples != 1) { // (all of it before the device is touched)
+        if (o.coarse_malformed || o.coarse.empty()) {
+            std::fprintf(stderr, "--coarse takes a list of stages Z:K[,Z:K...] (zoom:iterations), e.g. 0.25:100,0.5:100%s\n",
+                         o.coarse_malformed ? "" : "; --coarse-samples goes with it");
+            return 2;
+        }
+        for (const auto& st : o.coarse) {
+            if (!(st.first >= 1.0f / 256.0f) || !(st.first <= 65536.0f) || st.second < 0 || st.second > (1 << 24)) { // (the library resamples no target below 1/256)
+                std::fprintf(stderr, "--coarse %g:%d: the zoom must be at least 1/256 and the iteration count >= 0\n", (double)st.first, st.second);
+                return 2;
+            }
+        }
+        if (o.coarse_samples != 1 && o.coarse_samples != 2 && o.coarse_samples != 4) {
+            std::fprintf(stderr, "--coarse-samples must be 1, 2 or 4\n");
+            return 2;
+        }
+        if (o.gpus > 1 || std::getenv("S2D_TRAIN_FORCE_MULTI")) {
+            std::fprintf(stderr, "--coarse works on one context: the multi-device handle has no views\n");
+            return 2;
+        }
+        if (o.coverage || o.reference_order || o.have_loss) {
+            std::fprintf(stderr, "--coarse trains views with the squared error: not together with --coverage, --reference-order or --loss-weights\n");
+            return 2;
+        }
+        if (o.relocate_every > 0 || o.reseed_every > 0 || o.prune_every > 0 || o.grow_every > 0) {
+            std::fprintf(stderr, "--coarse gathers no density statistics: not together with --relocate-every, --reseed-every, --prune-every or --grow-every\n");
+            return 2;
+        }
+    }
+    // The stage iteration `it` lies in (nullptr: none, full size), and where it ends.
+    auto coarse_stage_at = [&](int it, int* end) -> const std::pair<float, int>* {
+        int begin = 0;
+        for (const auto& st : o.coarse) {
+            if (it >= begin && it < begin + st.second) {
+                *end = begin + st.second;
+                return &st;
+            }
+            begin += st.second;
+        }
+        return nullptr;
+    };
+    bool views_held = false; // a stage ran and s2d_view_release has not followed yet
     Session S;
     CK(S.create(o, W, H));
     if (have_optim) { // (groups without a rate of their own: the one --lr)
@@ -643,7 +724,25 @@ int main(int argc, char** argv)
             if (iterations + k > next_grow) k = next_grow - iterations;
         }
         const uint32_t step_flags = (opacity_now ? S2D_STEP_OPTIMIZE_OPACITY : 0u) | density;
-        if (o.have_loss) CK(s2d_step_loss(S.ctx, k, step_flags, &o.loss, loss.data(), mse.data()));
+        int stage_end = 0;
+        const std::pair<float, int>* stage = coarse_stage_at(iterations, &stage_end);
+        if (!stage && views_held) { // behind the last stage: what the views allocated goes
+            CK(s2d_view_release(S.ctx));
+            views_held = false;
+        }
+        if (stage) { // k iterations at the stage's zoom, against the library's own resampled target
+            if (iterations + k > stage_end) k = stage_end - iterations;
+            s2d_view_config vc;
+            std::memset(&vc, 0, sizeof(vc));
+            vc.struct_size = sizeof(vc);
+            vc.out_width = (int32_t)std::ceil((double)W * (double)stage->first);
+            vc.out_height = (int32_t)std::ceil((double)H * (double)stage->first);
+            vc.zoom = stage->first;
+            vc.samples = o.coarse_samples;
+            vc.format = S2D_VIEW_RGBA32F;
+            CK(s2d_step_view(S.ctx, &vc, nullptr, k, step_flags, mse.data()));
+            views_held = true;
+        } else if (o.have_loss) CK(s2d_step_loss(S.ctx, k, step_flags, &o.loss, loss.data(), mse.data()));
         else CK(S.step(k, step_flags, mse.data()));
         if (!o.quiet)
             for (int j = 0; j < k; j++) {
@@ -654,6 +753,7 @@ int main(int argc, char** argv)
         iterations += k; // main.cpp:809
         frames += k;
     }
+    if (views_held) CK(s2d_view_release(S.ctx)); // (the stages reached the end of the run)
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::fprintf(stderr, "%d iterations in %.3f s = %.2f it/s (%dx%d, %d splats%s)\n", frames, secs,
                  secs > 0 ? frames / secs : 0.0, W, H, o.n_splats, S.exchange_summary(o).c_str());
