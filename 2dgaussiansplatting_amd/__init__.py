@@ -8,8 +8,8 @@ but every compute call needs the built library and a gfx950 device and raises ot
 
 One module per concern, re-exported here: _abi (constants, structures, the signature table of the C ABI), _runtime (loading the
 library, one HIP runtime per process), _handle (what the two handles share), trainer (Trainer), multi (MultiTrainer), coarse
-(CoarseTrainer: include/splat2d_coarse.h, with the signatures of its two symbols); torch_op and distributed import torch and are
-imported by name.
+(CoarseTrainer: include/splat2d_coarse.h, with the signatures of its two symbols), backdrop (BackdropTrainer:
+include/splat2d_backdrop.h, likewise); torch_op, torch_backdrop and distributed import torch and are imported by name.
 
 The package name starts with a digit, so import it with
     importlib.import_module("2dgaussiansplatting_amd")
@@ -27,9 +27,10 @@ from ._abi import (S2D_ABI_VERSION, S2D_BWD_DENSITY_STATS, S2D_BWD_SKIP_OPACITY_
                    S2D_VIEW_RGBA32F)
 from ._handle import S2DError
 from ._runtime import hip_runtimes_mapped, load_library, use_library
+from .backdrop import BackdropTrainer
 from .coarse import CoarseTrainer
 from .multi import MultiTrainer
 from .trainer import Trainer
 
-__all__ = ["Trainer", "MultiTrainer", "CoarseTrainer", "S2DError", "load_library", "use_library", "hip_runtimes_mapped",
+__all__ = ["Trainer", "MultiTrainer", "CoarseTrainer", "BackdropTrainer", "S2DError", "load_library", "use_library", "hip_runtimes_mapped",
            "SPLAT_DTYPE", "ADAM_DTYPE", "STATUS_NAMES"]

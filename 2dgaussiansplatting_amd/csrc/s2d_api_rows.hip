@@ -10,6 +10,7 @@ int s2d_halo_masks(s2d_ctx* c, int32_t world, const int32_t* row_bounds, float m
     for (int q = 0; q < world; q++)
         if (row_bounds[q] > row_bounds[q + 1]) return S2D_E_INVALID;
     if (int rc = coverage_refused(c, "s2d_halo_masks")) return rc;
+    if (int rc = backdrop_refused(c, "s2d_halo_masks")) return rc;
     if (c->state.kind() == SplatState::Subset::Alive) // (its flags are no hold set: the two kinds of subset exclude each other)
         return fail(c, S2D_E_INVALID, "s2d_halo_masks: this context has an alive set (s2d_set_alive(NULL) first)");
     if (int rc = use_device(c)) return rc;
@@ -23,6 +24,7 @@ int s2d_halo_commit(s2d_ctx* c, const uint32_t* masks_device, int32_t rank, int3
 {
     if (!c || rank < 0 || rank > 31) return S2D_E_INVALID;
     if (int rc = coverage_refused(c, "s2d_halo_commit")) return rc;
+    if (int rc = backdrop_refused(c, "s2d_halo_commit")) return rc;
     if (masks_device && c->surface.reference_order())
         return fail(c, S2D_E_INVALID, "reference order (S2D_CFG_REFERENCE_ORDER) has no slab ownership: the chains run over all splats");
     if (masks_device && (c->has_optim || c->has_frozen))

@@ -23,13 +23,16 @@ int view_alloc(s2d_ctx* c, hipError_t e, const char* what)
 namespace {
 
 // Everything the view calls (`who`) refuse for the configuration or the context, before any device work (S2D_E_INVALID).
-int view_refused(s2d_ctx* c, const s2d_view_config* cfg, const char* who)
+// draws: the call rasterises the view (a plane backdrop has no view kernel).
+int view_refused(s2d_ctx* c, const s2d_view_config* cfg, const char* who, bool draws = false)
 {
     if (!cfg) return fail(c, S2D_E_INVALID, "%s: NULL s2d_view_config", who);
     if (const char* why = view_config_invalid(cfg->struct_size, (uint32_t)sizeof(s2d_view_config), cfg->out_width, cfg->out_height,
                                               cfg->origin_x, cfg->origin_y, cfg->zoom, cfg->filter_var, cfg->samples, cfg->format,
                                               S2D_VIEW_RGBA8))
         return fail(c, S2D_E_INVALID, "%s: s2d_view_config: %s", who, why);
+    if (draws && c->backdrop.kind() == BackdropState::Plane)
+        return fail(c, S2D_E_INVALID, "%s: a view over a plane backdrop is not available (the plane would have to be resampled)", who);
     return whole_scene_refused(c, who, true); // (an alive set and reference order are no obstacle)
 }
 
@@ -55,6 +58,14 @@ void view_walk(s2d_ctx* c, const s2d_view_config* cfg, RasterArgs* a)
 // The raster kernel over the view's lists as they stand (queued).
 int view_raster(s2d_ctx* c, const s2d_view_config* cfg, void* out)
 {
+    if (c->backdrop.set()) { // (a constant: view_refused) the composite per sample, backdrop_view_kernel
+        BackdropViewArgs b;
+        view_walk(c, cfg, &b.walk);
+        b.out = out; b.out_width = cfg->out_width; b.samples = view_samples(cfg->samples); b.rgba8 = cfg->format == S2D_VIEW_RGBA8;
+        for (int k = 0; k < 3; k++) b.rgb[k] = c->backdrop.rgb()[k];
+        S2D_HIP(c, launch_backdrop_view(b, c->stream));
+        return S2D_OK;
+    }
     ViewRasterArgs a;
     view_walk(c, cfg, &a.walk);
     a.walk.coverage = coverage(c);
@@ -145,6 +156,7 @@ int view_gradient_refused(s2d_ctx* c, const s2d_view_config* cfg, const float* s
     if (!src) return fail(c, S2D_E_INVALID, "%s: NULL image gradient (or target)", who);
     if ((uintptr_t)src & 15u) return fail(c, S2D_E_INVALID, "%s: the image gradient (or target) must be 16-byte aligned", who);
     if (flags & ~(S2D_VIEW_BWD_FROM_TARGET | S2D_BWD_SKIP_OPACITY_GRAD)) return fail(c, S2D_E_INVALID, "%s: unknown flags %#x", who, flags);
+    if (int rc = backdrop_refused(c, who)) return rc; // (view_gradient_kernel forms the final colour itself, without the backdrop)
     return view_pass_context_refused(c, who);
 }
 
@@ -185,7 +197,7 @@ int s2d_render_view_device(s2d_ctx* c, const s2d_view_config* cfg, void* out_dev
 {
     if (!c) return S2D_E_INVALID;
     if (!out_device) return fail(c, S2D_E_INVALID, "s2d_render_view_device: NULL output");
-    if (int rc = view_refused(c, cfg, "s2d_render_view_device")) return rc;
+    if (int rc = view_refused(c, cfg, "s2d_render_view_device", true)) return rc;
     if ((uintptr_t)out_device & (cfg->format == S2D_VIEW_RGBA8 ? 3u : 15u))
         return fail(c, S2D_E_INVALID, "s2d_render_view_device: the buffer must be 16-byte (RGBA32F) or 4-byte (RGBA8) aligned");
     if (int rc = use_device(c)) return rc;
@@ -196,7 +208,7 @@ int s2d_render_view(s2d_ctx* c, const s2d_view_config* cfg, void* out_host)
 {
     if (!c) return S2D_E_INVALID;
     if (!out_host) return fail(c, S2D_E_INVALID, "s2d_render_view: NULL output");
-    if (int rc = view_refused(c, cfg, "s2d_render_view")) return rc;
+    if (int rc = view_refused(c, cfg, "s2d_render_view", true)) return rc;
     if (int rc = use_device(c)) return rc;
     void* image = nullptr;
     if (int rc = view_alloc(c, c->view.image(view_bytes(cfg), &image), "the image")) return rc;
@@ -229,7 +241,7 @@ int s2d_view_grads(s2d_ctx* c, const s2d_view_config* cfg, const float* dview_or
 int s2d_debug_view_raster(s2d_ctx* c, const s2d_view_config* cfg, void* out_device)
 {
     if (!c || !out_device) return S2D_E_INVALID;
-    if (int rc = view_refused(c, cfg, "s2d_debug_view_raster")) return rc;
+    if (int rc = view_refused(c, cfg, "s2d_debug_view_raster", true)) return rc;
     if ((uintptr_t)out_device & (cfg->format == S2D_VIEW_RGBA8 ? 3u : 15u)) return fail(c, S2D_E_INVALID, "s2d_debug_view_raster: misaligned buffer");
     if (!c->view.has_lists(view_geometry(cfg->out_width, cfg->out_height, view_samples(cfg->samples))))
         return fail(c, S2D_E_STATE, "s2d_debug_view_raster: no lists of this raster grid (render the view first)");

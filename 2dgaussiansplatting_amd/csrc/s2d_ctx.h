@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdio>
 
+#include "s2d_backdrop.h"
 #include "s2d_device.h"
 #include "s2d_context.h"
 #include "s2d_lists.h"
@@ -59,6 +60,7 @@ struct s2d_ctx {
     DevBuf<uint8_t> d_frozen;      // n bytes, non-zero = frozen; allocated by the first mask
     SeedScratch seed;              // the importance map of s2d_importance / s2d_seed_splats / s2d_reseed (s2d_seed.h), on first use
     ViewScratch view;              // the records, lists and image of s2d_view_splats / s2d_render_view (s2d_view.h), on first use
+    BackdropState backdrop;        // what image0 is composited over (include/splat2d_backdrop.h, s2d_backdrop.h), on first use
     DevBuf<DeviceStatus> d_status;
     DevBuf<PairCounters> d_counters;
     // pinned host mirrors
@@ -118,6 +120,13 @@ S2D_LOCAL inline bool coverage(const s2d_ctx* c) { return (c->cfg.flags & S2D_CF
 S2D_LOCAL inline int coverage_refused(s2d_ctx* c, const char* who)
 {
     if (coverage(c)) return fail(c, S2D_E_INVALID, "%s: not available with S2D_CFG_COVERAGE", who);
+    return S2D_OK;
+}
+
+// What has no kernels over a backdrop (`who`: a call's name).  S2D_E_INVALID, before any device work.
+S2D_LOCAL inline int backdrop_refused(s2d_ctx* c, const char* who)
+{
+    if (c->backdrop.set()) return fail(c, S2D_E_INVALID, "%s: not available while a backdrop is set (s2d_set_backdrop(ctx, NULL) removes it)", who);
     return S2D_OK;
 }
 

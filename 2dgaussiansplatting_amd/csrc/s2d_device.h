@@ -235,6 +235,7 @@ enum class RasterPass {
     ForwardRange,  // index-range rendering (scenes beyond one set of lists; s2d_raster_ranges.hip, s2d_sequence.hip
     BackwardRange, // chunked_forward / chunked_backward): the lists are those of ONE index range of the splats
 };
+struct BackdropArgs; // s2d_backdrop.h
 // What a raster pass works on; a member left at its default is not used.
 struct RasterArgs {
     const uint32_t* tile_off = nullptr;
@@ -279,6 +280,7 @@ struct RasterArgs {
     bool exact_exp = false;
     bool need_opacity_grad = false;
     bool coverage = false; // Forward, Backward: image0.w / image_ref.w / upstream.w are the coverage channel (s2d_raster_coverage.hip)
+    const BackdropArgs* backdrop = nullptr; // Forward: image0 = C + T_final * backdrop, T_final kept (s2d_backdrop.h); every other pass is the plain one
 };
 hipError_t launch_raster(RasterPass pass, const RasterArgs& a, hipStream_t stream);
 // Reference-order backward pass (S2D_CFG_REFERENCE_ORDER; s2d_raster_reference.hip).  The walk stores the

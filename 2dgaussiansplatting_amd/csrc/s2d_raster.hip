@@ -25,7 +25,8 @@
 // plain iteration -- forward, backward from the target image, fused, the squared-error sum -- and launch_raster; every other
 // kernel family has a unit of its own: s2d_raster_ranges.hip (index ranges), s2d_raster_gradient.hip
 // (backward from a caller's gradient, density statistics), s2d_raster_det.hip (deterministic mode's gather),
-// s2d_raster_reference.hip (reference-order validation), s2d_raster_coverage.hip (the coverage channel).
+// s2d_raster_reference.hip (reference-order validation), s2d_raster_coverage.hip (the coverage channel), s2d_backdrop.hip (the
+// forward walk over a backdrop).
 //
 // The alpha / throughput / colour arithmetic is the reference's, operation for operation
 // (-ffp-contract=off), in both walks, so the framebuffer is bit-identical to the oracle's and the backward
@@ -35,6 +36,7 @@
 // with S2D_CFG_DETERMINISTIC, keeps one slot per wave, adds them in a fixed order and stores the partial into the
 // tile's own slot of that splat, and a gather kernel sums each splat's slots in a fixed order (bitwise
 // reproducible gradients).
+#include "s2d_backdrop.h"
 #include "s2d_walk_backward.h"
 
 namespace s2d {
@@ -129,11 +131,14 @@ __global__ __launch_bounds__(256) void sqerr_finalize_kernel(const double* __res
 // Which unit's kernels run a pass: the pass, then whether the backward walk starts from the target image or from a caller's
 // gradient (a.upstream), then whether it also sums the density statistics (a.density).  Only the backward kernels have the last
 // two; a combination without a kernel is hipErrorInvalidValue.  A coverage context (a.coverage) has its own forward and backward
-// kernels and no others.
+// kernels and no others.  A backdrop (a.backdrop, s2d_backdrop.hip) has a forward kernel of its own; its backward walks are the
+// plain ones, and it has no fused launch and no index ranges.
 hipError_t launch_raster(RasterPass pass, const RasterArgs& a, hipStream_t stream)
 {
     if (a.g.num_tiles <= 0) return hipSuccess;
     if (a.coverage) return launch_raster_coverage(pass, a, stream);
+    if (a.backdrop != nullptr && pass != RasterPass::Backward)
+        return pass == RasterPass::Forward ? launch_raster_backdrop(a, stream) : hipErrorInvalidValue;
     const dim3 grid(raster_grid(a.g.num_tiles)), block(256);
     const bool from_target = a.upstream == nullptr, stats = a.density != nullptr;
     const bool det_mode = a.det.now != 0u;

@@ -76,6 +76,7 @@ S2D_LOCAL int check_status(s2d_ctx* c);      // ... read, waited for and judged
 // ---- events -----------------------------------------------------------------------------------------------------------
 // ("Adam step queued" and "non-finite step judged" are queue_adam's and judge_status's own.)
 S2D_LOCAL void target_replaced(s2d_ctx* c);                 // s2d_set_target, _synthetic
+S2D_LOCAL void backdrop_replaced(s2d_ctx* c);               // s2d_set_backdrop, _device: set, replaced or removed
 S2D_LOCAL int splats_replaced(s2d_ctx* c);                  // s2d_init_splats, s2d_set_splats
 S2D_LOCAL int splats_replaced_from_device(s2d_ctx* c);      // s2d_set_splats_device
 S2D_LOCAL int rows_replaced(s2d_ctx* c, int32_t what);      // S2D_ROWS_*: s2d_rows_scatter; s2d_relocate and the seeding write S2D_ROWS_SPLATS (with their moments)

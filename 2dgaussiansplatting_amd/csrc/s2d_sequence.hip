@@ -64,6 +64,7 @@ RasterArgs raster_args(const s2d_ctx* c, int range = -1)
     c->ranges.fill(&a, range);
     a.half_images = c->half_images; a.count = (c->cfg.flags & S2D_CFG_COUNT_PAIRS) != 0; a.exact_exp = (c->cfg.flags & S2D_CFG_EXACT_EXP) != 0;
     a.coverage = coverage(c);
+    a.backdrop = c->backdrop.args();
     return a;
 }
 
@@ -223,6 +224,9 @@ int queue_raster(s2d_ctx* c, const RasterJob& job)
         if (need_ranges && coverage(c))
             return fail(c, S2D_E_NOMEM, "the coverage channel (S2D_CFG_COVERAGE) is not available for scenes beyond %llu (tile, splat) pairs",
                         (unsigned long long)c->ranges.budget());
+        if (need_ranges && c->backdrop.set())
+            return fail(c, S2D_E_NOMEM, "a backdrop is not available for scenes beyond %llu (tile, splat) pairs (index-range rendering)",
+                        (unsigned long long)c->ranges.budget());
         if (need_ranges && c->surface.reference_order())
             return fail(c, S2D_E_NOMEM, "reference order (S2D_CFG_REFERENCE_ORDER) is not available for scenes beyond %llu (tile, splat) pairs",
                         (unsigned long long)c->ranges.budget());
@@ -311,10 +315,11 @@ int queue_backward(s2d_ctx* c, bool need_opacity_grad, const float4* upstream, b
 
 // Forward + backward (+ squared error) of the current parameters through the fused kernel.  Pair counting is a
 // property of the separate kernels only, so a counting context takes those; so does a coverage context, whose kernels are the
-// separate ones (image0 stored every time, whatever write_image says).
+// separate ones (image0 stored every time, whatever write_image says), and a context with a backdrop, whose backward walk reads
+// the composite from image0.
 int queue_forward_backward(s2d_ctx* c, bool need_opacity_grad, bool write_image)
 {
-    if ((c->cfg.flags & S2D_CFG_COUNT_PAIRS) || c->surface.reference_order() || coverage(c)) { // (reference order: its backward pass is a launch of its own)
+    if ((c->cfg.flags & S2D_CFG_COUNT_PAIRS) || c->surface.reference_order() || coverage(c) || c->backdrop.set()) { // (reference order: its backward pass is a launch of its own)
         if (int rc = queue_forward(c)) return rc;
         return queue_backward(c, need_opacity_grad);
     }
@@ -455,6 +460,9 @@ void target_replaced(s2d_ctx* c)
     c->fresh.invalidate(Stale::Frames);
     c->view.target_stale(); // (the views' own resampled target, s2d_step_view: derived from the one replaced)
 }
+
+// What image0 is composited over changed: the frames are stale; the projection and the lists depend on the splats alone.
+void backdrop_replaced(s2d_ctx* c) { c->fresh.invalidate(Stale::Frames); }
 
 // Every splat is new (init / set_splats): the lists are none of theirs, and a non-finite event of the old ones no longer
 // stops the queue.  (init also zeroes the gradients and restarts the counters, and asks for the arrays with

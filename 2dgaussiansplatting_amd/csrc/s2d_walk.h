@@ -296,7 +296,8 @@ __device__ __forceinline__ BlendedCoverage blend_entry_coverage(const float4 q0,
 // *T_io on entry -- and leaves the state for the range after it.  The reference's loop is front to back in index order
 // (main.cpp:419), so cutting it at any index and carrying (colour, T) across the cut changes no operation.
 // COVERAGE (s2d_raster_coverage.hip): the walk blends through blend_entry_coverage and leaves the pixel's coverage in *ca_out.
-template <bool COUNT, bool EXACT, bool CHUNK = false, bool COVERAGE = false>
+// THROUGHPUT (s2d_backdrop.hip): the plain walk, retirement hint included, that also leaves the pixel's final T in *T_io.
+template <bool COUNT, bool EXACT, bool CHUNK = false, bool COVERAGE = false, bool THROUGHPUT = false>
 __device__ __forceinline__ uint32_t forward_tile(FwdShared& s, const TileCtx& c, const uint32_t* __restrict__ tile_off,
                                              const uint32_t* __restrict__ list, const ProjRec* __restrict__ proj,
                                              unsigned long long* __restrict__ wave_masks, uint32_t* __restrict__ exec_list,
@@ -305,6 +306,7 @@ __device__ __forceinline__ uint32_t forward_tile(FwdShared& s, const TileCtx& c,
                                              float* ca_out = nullptr)
 {
     static_assert(!(COVERAGE && (COUNT || EXACT || CHUNK)), "the coverage channel: plain lists, exp_approx, no pair counting");
+    static_assert(!(THROUGHPUT && (COUNT || EXACT || CHUNK || COVERAGE)), "the final throughput: plain lists, exp_approx, no pair counting");
     constexpr bool HINT = !COUNT && !CHUNK;
     const int tid = c.tid, lane = c.lane, w = c.w;
     const f2 pxy = c.pxy;
@@ -416,6 +418,7 @@ __device__ __forceinline__ uint32_t forward_tile(FwdShared& s, const TileCtx& c,
         }
     }
     if (CHUNK) *T_io = T;
+    if constexpr (THROUGHPUT) *T_io = T;
     if constexpr (COVERAGE) *ca_out = ca;
     if constexpr (HINT)
         if (tid == 0) retire_hint[c.tile] = retired ? last_exec : kNoHint;

@@ -29,6 +29,7 @@
 #include "image_io.h"
 #include "overlay.h"
 #include "splat2d.h"
+#include "splat2d_backdrop.h"
 #include "splat2d_coarse.h"
 
 namespace {
@@ -119,6 +120,10 @@ struct Options {
     std::vector<std::pair<float, int>> coarse;
     bool coarse_malformed = false;
     int coarse_samples = 1;
+    // --background R,G,B: a constant backdrop (splat2d_backdrop.h): the splats are drawn and trained over that colour, and
+    // --out-image, --out-size and --out-view include it.  One context; a checkpoint does not carry it.
+    bool have_background = false, background_malformed = false;
+    float background[3] = {0, 0, 0};
     bool replicated = false;    // --exchange dense: replicated state + RCCL all-reduce of all gradients (default: slab ownership)
                                 // (RCCL takes one rank per GPU): a rehearsal of the N-rank host logic on a box with fewer GPUs
 };
@@ -148,6 +153,7 @@ int usage()
                  "                     [--lr-groups P,S,R,C,O [--lr-final-ratio P,S,R,C,O --lr-decay-iters T]] [--rebin-margin PX] [--freeze-unmoved]\n"
                  "                     [--alive-from K0] [--grow-every M --grow-count C [--grow-scale X]]\n"
                  "                     [--prune-every K [--prune-min-weight W] [--prune-window S]] [--coverage]\n"
+                 "                     [--background R,G,B]\n"
                  "  --loss-weights M,L,D: train with the sum over pixels and channels of M * d^2 / 2 + L * |d| + D * (1 - SSIM), e.g.\n"
                  "    0,0.8,0.2, instead of the reference's squared error (one GPU only); every line ends with the loss's mean.\n"
                  "  --relocate-every K: before iteration K, 2K, ... move the starved splats (summed T * alpha per pass below W) onto\n"
@@ -187,7 +193,24 @@ int usage()
                  "    that size, then the next stage, then full size; the trace prints the view's MSE.  The stages count towards --iters.\n"
                  "    One GPU only; not with --coverage, --reference-order, --loss-weights or the options that gather density\n"
                  "    statistics (--relocate-every, --reseed-every, --prune-every, --grow-every).  The schedule is provisional.\n");
+    std::fprintf(stderr,
+                 "  --background R,G,B: draw and train the splats over that colour instead of black, e.g. 1,1,1 for a page or a chart on\n"
+                 "    white; --out-image, --out-size and --out-view include it.  One GPU only; not with --coverage, --reference-order or\n"
+                 "    --coarse.  A checkpoint does not carry the background: give the option again with --load-checkpoint.\n");
     return 2;
+}
+
+// "R,G,B" -> three finite values; false: malformed (a missing part, trailing characters, a value that is not finite).
+bool parse_background(const char* text, float* rgb)
+{
+    const char* p = text;
+    for (int k = 0; k < 3; k++) {
+        char* end = nullptr;
+        rgb[k] = std::strtof(p, &end);
+        if (end == p || !std::isfinite(rgb[k]) || *end != (k < 2 ? ',' : '\0')) return false;
+        p = end + 1;
+    }
+    return true;
 }
 
 // "Z:K[,Z:K...]" -> stages; false: malformed (an empty list, a missing part, trailing characters).
@@ -373,6 +396,7 @@ int main(int argc, char** argv)
         else if (a == "--coverage") o.coverage = true;
         else if (a == "--coarse") o.coarse_malformed = !parse_coarse(next("--coarse"), &o.coarse);
         else if (a == "--coarse-samples") o.coarse_samples = std::atoi(next("--coarse-samples"));
+        else if (a == "--background") { o.background_malformed = !parse_background(next("--background"), o.background); o.have_background = true; }
         else return usage();
     }
     if (!o.convert_in.empty()) { // file conversion between .s2di / .ppm / .png; touches no GPU
@@ -405,6 +429,20 @@ int main(int argc, char** argv)
         }
         if (!o.out_image.empty() && !s2dio::ends_with(o.out_image, ".png")) {
             std::fprintf(stderr, "--coverage writes --out-image with its alpha: the file must be a .png\n");
+            return 2;
+        }
+    }
+    if (o.have_background) { // (all of it before a file or the device is touched)
+        if (o.background_malformed) {
+            std::fprintf(stderr, "--background takes three finite values R,G,B, e.g. 1,1,1\n");
+            return 2;
+        }
+        if (o.gpus > 1 || std::getenv("S2D_TRAIN_FORCE_MULTI")) {
+            std::fprintf(stderr, "--background works on one context: the multi-device handle has no backdrop\n");
+            return 2;
+        }
+        if (o.coverage || o.reference_order || !o.coarse.empty() || o.coarse_malformed) {
+            std::fprintf(stderr, "--background is not available with --coverage, --reference-order or --coarse\n");
             return 2;
         }
     }
@@ -541,6 +579,7 @@ int main(int argc, char** argv)
     bool views_held = false; // a stage ran and s2d_view_release has not followed yet
     Session S;
     CK(S.create(o, W, H));
+    if (o.have_background) CK(s2d_set_backdrop(S.ctx, o.background));
     if (have_optim) { // (groups without a rate of their own: the one --lr)
         s2d_optim_config oc;
         std::memset(&oc, 0, sizeof(oc));
