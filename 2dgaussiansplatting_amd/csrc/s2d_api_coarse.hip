@@ -50,14 +50,14 @@ int own_target(s2d_ctx* c, const s2d_view_config* cfg, const float4** out)
 // transform into the gradient buffer.
 int queue_view_fit(s2d_ctx* c, const s2d_view_config* cfg, const float4* target, bool need_opacity_grad, int ring_slot, double** ring)
 {
-    ViewFitArgs a;
+    ViewGradientArgs a;
     float* record_grads = nullptr;
     if (int rc = view_backward_prepare(c, cfg, need_opacity_grad, &a.walk, &record_grads)) return rc;
     SqerrJob job{};
     if (int rc = view_alloc(c, c->view.fit_errors(a.walk.g.num_tiles, c->stream, &job, &a.walk.tile_sqerr), "the tile errors")) return rc;
     *ring = job.out;
     job.out += ring_slot;
-    a.target = target;
+    a.src = target; a.from_target = true;
     a.out_width = cfg->out_width; a.samples = view_samples(cfg->samples);
     S2D_HIP(c, launch_view_fit(a, c->stream));
     S2D_HIP(c, launch_sqerr_finalize(job, c->d_status, c->iterations, c->stream));

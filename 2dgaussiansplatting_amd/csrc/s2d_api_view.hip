@@ -58,18 +58,15 @@ void view_walk(s2d_ctx* c, const s2d_view_config* cfg, RasterArgs* a)
 // The raster kernel over the view's lists as they stand (queued).
 int view_raster(s2d_ctx* c, const s2d_view_config* cfg, void* out)
 {
-    if (c->backdrop.set()) { // (a constant: view_refused) the composite per sample, backdrop_view_kernel
-        BackdropViewArgs b;
-        view_walk(c, cfg, &b.walk);
-        b.out = out; b.out_width = cfg->out_width; b.samples = view_samples(cfg->samples); b.rgba8 = cfg->format == S2D_VIEW_RGBA8;
-        for (int k = 0; k < 3; k++) b.rgb[k] = c->backdrop.rgb()[k];
-        S2D_HIP(c, launch_backdrop_view(b, c->stream));
-        return S2D_OK;
-    }
     ViewRasterArgs a;
     view_walk(c, cfg, &a.walk);
-    a.walk.coverage = coverage(c);
     a.out = out; a.out_width = cfg->out_width; a.samples = view_samples(cfg->samples); a.rgba8 = cfg->format == S2D_VIEW_RGBA8;
+    if (c->backdrop.set()) { // (a constant: view_refused) the composite per sample, backdrop_view_kernel
+        for (int k = 0; k < 3; k++) a.rgb[k] = c->backdrop.rgb()[k];
+        S2D_HIP(c, launch_backdrop_view(a, c->stream));
+        return S2D_OK;
+    }
+    a.walk.coverage = coverage(c);
     S2D_HIP(c, launch_view_raster(a, c->stream));
     return S2D_OK;
 }

@@ -20,16 +20,7 @@ struct BackdropArgs {
 // uses of `a`: as raster_forward_kernel's (lists, hand-over, image0, g, status, abort_stamp, iteration, half_images) and a.backdrop
 hipError_t launch_raster_backdrop(const RasterArgs& a, hipStream_t stream);
 
-struct BackdropViewArgs {
-    RasterArgs walk;        // of it: tile_off, list, proj, g (the raster grid: out * samples)
-    void* out = nullptr;    // out_height * out_width pixels: RGBA32F (16-byte aligned) or, with rgba8, 4 bytes each
-    int out_width = 0;
-    int samples = 1;        // 1, 2 or 4 per axis
-    bool rgba8 = false;
-    float rgb[3] = {0.0f, 0.0f, 0.0f};
-};
-// view_raster_kernel's walk with c += T * B per sample before the resolve (a constant backdrop, exp_approx).
-hipError_t launch_backdrop_view(const BackdropViewArgs& a, hipStream_t stream);
+// (the view over a constant backdrop, launch_backdrop_view, takes a ViewRasterArgs and is declared with it: s2d_view.h)
 
 constexpr int kBackdropGradBlocks = 256; // partial sums of s2d_backdrop_grads: at most this many workgroups, each a fixed set of pixels
 

@@ -1,6 +1,6 @@
 // s2d_backdrop.hip -- the kernels of a backdrop (include/splat2d_backdrop.h, s2d_backdrop.h) and their
-// launches: the forward walk that composites over the backdrop and leaves T_final, the view walk over a constant backdrop, and
-// the gradient of the backdrop.
+// launches: the forward walk that composites over the backdrop and leaves T_final, the view over a constant backdrop (the sample
+// walk and the resolve of s2d_view_walk.h with the composite between them), and the gradient of the backdrop.
 //
 // image0.c = C.c + (T_final * B.c), one fp32 multiply and one add (-ffp-contract=off).  The reference's loop throws T_final away
 // (main.cpp:543-546); forward_tile (s2d_walk.h) has it in a register when the walk ends and, with its THROUGHPUT flag, hands it
@@ -17,7 +17,7 @@
 // There is no variant with pair counting, the exact exponential, the coverage channel or index ranges: the API refuses those
 // combinations (s2d_api_backdrop.hip), and a pass without a kernel is hipErrorInvalidValue.
 #include "s2d_backdrop.h"
-#include "s2d_view.h"
+#include "s2d_view_walk.h"
 #include "s2d_walk_backward.h"
 
 namespace s2d {
@@ -59,89 +59,21 @@ __global__ __launch_bounds__(256) void backdrop_forward_kernel(const uint32_t* _
     }
 }
 
-namespace {
-
-// LDS of the view walk (s2d_view.hip ViewShared): the entry records as the forward walk lays them out and one copy of the masks.
-struct BackdropViewShared {
-    float4 rec[B][3];
-    unsigned long long mask[4 * B]; // [wave][entry]
-    int4 alive;                     // per wave: does it still have a live pixel
-};
-
-} // namespace
-
-// view_raster_kernel<false, S, RGBA8> (s2d_view.hip) with the composite per sample: the same loop made of the same parts of the
-// walk (stage_masks, blend_entry, block_any_alive), then c += T * B, then the resolve.
+// view_raster_kernel<false, S, RGBA8> (s2d_view.hip) with the composite per sample: the same sample walk (s2d_view_walk.h), then
+// c += T * B, one fp32 multiply and one add per channel, then the same resolve and store.
 template <int S, bool RGBA8>
 __global__ __launch_bounds__(256) void backdrop_view_kernel(const uint32_t* __restrict__ tile_off, const uint32_t* __restrict__ list,
                                                             const ProjRec* __restrict__ proj, void* __restrict__ out, Geometry g,
                                                             int out_width, BackdropRgb constant)
 {
-    __shared__ BackdropViewShared s;
+    __shared__ ViewShared s;
     const int tile = (int)blockIdx.x;
     if (tile >= g.num_tiles) return;
-    const int tx = tile % g.tiles_x, ty = tile / g.tiles_x;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int lx = (w % kWavesX) * kWaveW + (lane % kWaveW), ly = (w / kWavesX) * kWaveH + (lane / kWaveW); // pixel_of_thread
-    const int x = tx * kTile + lx, y = ty * kTile + ly;
-    const bool inside = x < g.W && y < g.row_end;
-    const f2 pxy = mk2((float)x + 0.5f, (float)y + 0.5f); // pixel centre, main.cpp:523
-
-    f2 crg = mk2(0.0f, 0.0f); // main.cpp:414: (0,0,0,1)
-    float cb = 0.0f, T = 1.0f;
-    unsigned long long alive_mask = __ballot(inside); // pixels still above the throughput cut-off (main.cpp:520), wave-uniform
-    const uint32_t beg = tile_off[tile], end = tile_off[tile + 1];
-    const int se = tid >> 2, sub = tid & 3;
-    for (uint32_t base = beg; base < end; base += B) {
-        const int cnt = (int)min((uint32_t)B, end - base);
-        if (se < cnt) {
-            const ProjRec* r = proj + list[base + se];
-            const float4 q0 = r->q0, q1 = r->q1, q2 = r->q2;
-            stage_masks(reinterpret_cast<uint32_t*>(s.mask), se, sub, q0, q1, __float_as_int(q2.y), __float_as_int(q2.z), ty * kTile,
-                        tx * kTile, g.W, g.row_end);
-            if (sub == 0) {
-                s.rec[se][0] = q0;
-                s.rec[se][1] = make_float4(q0.w, q1.x, q1.y, q1.z);
-                s.rec[se][2] = make_float4(q1.w, q2.x, 0.0f, 0.0f);
-            }
-        }
-        __syncthreads();
-        if (alive_mask != 0ull) {
-            const unsigned long long my_mask = (lane < cnt) ? s.mask[w * B + lane] : 0ull;
-            unsigned long long cand = __ballot((my_mask & alive_mask) != 0ull);
-            while (cand != 0ull) {
-                const int e = __builtin_ctzll(cand);
-                cand &= cand - 1ull;
-                const unsigned long long act = readlane_u64(my_mask, e) & alive_mask; // visited (main.cpp:511-514), not cut off (:520)
-                if (act == 0ull) continue;
-                const Blended bl = blend_entry<false>(s.rec[e][0], s.rec[e][1], s.rec[e][2], pxy, act, crg, cb, T, alive_mask);
-                cb = bl.cb;
-                T = bl.T;
-                alive_mask = bl.alive_mask;
-            }
-        }
-        // (also the barrier behind which the next batch may overwrite the records and masks)
-        if (!block_any_alive(&s.alive, w, lane, alive_mask)) break; // every pixel of the tile saturated: retire it
-    }
-
-    float cr = crg.x + (T * constant.r), cg = crg.y + (T * constant.g); // the composite of the sample
-    cb = cb + (T * constant.b);
-    if (S >= 2) {
-        cr = resolve_level<1, 8>(cr);
-        cg = resolve_level<1, 8>(cg);
-        cb = resolve_level<1, 8>(cb);
-    }
-    if (S == 4) {
-        cr = resolve_level<2, 16>(cr);
-        cg = resolve_level<2, 16>(cg);
-        cb = resolve_level<2, 16>(cb);
-    }
-    // the top-left sample of an output pixel stores it (S divides 8: lx % S == x % S); a block is inside the grid as a whole
-    if (inside && (lx % S) == 0 && (ly % S) == 0) {
-        const size_t o = (size_t)(y / S) * (size_t)out_width + (size_t)(x / S);
-        if (RGBA8) reinterpret_cast<uint32_t*>(out)[o] = view_pack_rgba8(cr, cg, cb);
-        else reinterpret_cast<float4*>(out)[o] = make_float4(cr, cg, cb, 1.0f);
-    }
+    ViewSample p = view_walk_tile<false, false>(s, tile, tile_off, list, proj, g);
+    p.cr = p.cr + (p.T * constant.r); // the composite of the sample
+    p.cg = p.cg + (p.T * constant.g);
+    p.cb = p.cb + (p.T * constant.b);
+    view_resolve_store<S, RGBA8, false>(p, out, out_width);
 }
 
 // t_c = T_final * g_c per pixel and channel (one fp32 multiply), g = upstream or image0 - image_ref (loss_grad).  Workgroup b of
@@ -204,32 +136,21 @@ hipError_t launch_raster_backdrop(const RasterArgs& a, hipStream_t stream)
     return e != hipSuccess ? e : hipGetLastError();
 }
 
-namespace {
-
-template <int S>
-void launch_backdrop_view_format(const BackdropViewArgs& a, hipStream_t stream)
+hipError_t launch_backdrop_view(const ViewRasterArgs& a, hipStream_t stream)
 {
     const RasterArgs& w = a.walk;
+    if (w.g.num_tiles <= 0 || w.exact_exp || w.coverage) return hipErrorInvalidValue; // a missing kernel is an error
     const dim3 grid((unsigned)w.g.num_tiles), block(256);
     const BackdropRgb constant{a.rgb[0], a.rgb[1], a.rgb[2]};
-    if (a.rgba8)
-        hipLaunchKernelGGL((backdrop_view_kernel<S, true>), grid, block, 0, stream, w.tile_off, w.list, w.proj, a.out, w.g, a.out_width, constant);
-    else
-        hipLaunchKernelGGL((backdrop_view_kernel<S, false>), grid, block, 0, stream, w.tile_off, w.list, w.proj, a.out, w.g, a.out_width, constant);
-}
-
-} // namespace
-
-hipError_t launch_backdrop_view(const BackdropViewArgs& a, hipStream_t stream)
-{
-    if (a.walk.g.num_tiles <= 0 || a.walk.exact_exp || a.walk.coverage) return hipErrorInvalidValue; // a missing kernel is an error
-    switch (a.samples) {
-    case 1: launch_backdrop_view_format<1>(a, stream); break;
-    case 2: launch_backdrop_view_format<2>(a, stream); break;
-    case 4: launch_backdrop_view_format<4>(a, stream); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const hipError_t e = with_samples(a.samples, [&](auto samples) {
+        constexpr int S = decltype(samples)::value;
+        if (a.rgba8)
+            hipLaunchKernelGGL((backdrop_view_kernel<S, true>), grid, block, 0, stream, w.tile_off, w.list, w.proj, a.out, w.g, a.out_width, constant);
+        else
+            hipLaunchKernelGGL((backdrop_view_kernel<S, false>), grid, block, 0, stream, w.tile_off, w.list, w.proj, a.out, w.g, a.out_width, constant);
+        return hipSuccess;
+    });
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 hipError_t launch_backdrop_grads(const BackdropGradArgs& a, hipStream_t stream)

@@ -17,6 +17,8 @@
 #include "s2d_owned.h"
 #include "s2d_view_math.h"
 
+#include <type_traits>
+
 namespace s2d {
 
 // The raster grid of a view: (out_width * samples) x (out_height * samples), whole, not a slab.
@@ -34,9 +36,25 @@ struct ViewRasterArgs {
     int out_width = 0;
     int samples = 1;        // 1, 2 or 4 per axis
     bool rgba8 = false;
+    float rgb[3] = {0.0f, 0.0f, 0.0f}; // launch_backdrop_view: the constant backdrop
 };
-// The forward walk of every tile of the grid, resolved to output pixels inside the workgroup: writes nothing but `out`.
+// The sample walk of every tile of the grid, resolved to output pixels inside the workgroup: writes nothing but `out`.
 hipError_t launch_view_raster(const ViewRasterArgs& a, hipStream_t stream);
+// The same with c += T * rgb per sample before the resolve (s2d_backdrop.hip; exp_approx, no coverage).
+hipError_t launch_backdrop_view(const ViewRasterArgs& a, hipStream_t stream);
+
+// samples per axis -> a compile-time constant: f(std::integral_constant<int, S>{}) for S = 1, 2, 4 and what it returns; every
+// launch of a view kernel goes through here, so which S exist is decided here and nowhere else.
+template <typename F>
+inline hipError_t with_samples(int samples, F&& f)
+{
+    switch (samples) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    default: return hipErrorInvalidValue; // a missing kernel is an error
+    }
+}
 
 #if defined(__HIPCC__)
 // One level of the resolve: the 2 x 2 block whose top-left lane is this one, DX / DY = the lane distance of its right / lower
@@ -65,16 +83,10 @@ hipError_t launch_view_gradient(const ViewGradientArgs& a, hipStream_t stream);
 hipError_t launch_view_adjoint(const float* splats, const uint8_t* held, int n, ViewXform x, const float* view_grads, float* grads,
                                hipStream_t stream);
 
-// Coarse-to-fine fitting (include/splat2d_coarse.h; s2d_view_fit.hip).
-struct ViewFitArgs {
-    // as ViewGradientArgs::walk, and tile_sqerr (one double per tile of g: every tile's is stored)
-    RasterArgs walk;
-    const float4* target = nullptr; // out_height * out_width RGBA32F, .w ignored
-    int out_width = 0;
-    int samples = 1;                // 1, 2 or 4 per axis
-};
-// view_gradient_kernel's pass from a target, with the view's squared error per tile (and deterministic mode's gather).
-hipError_t launch_view_fit(const ViewFitArgs& a, hipStream_t stream);
+// Coarse-to-fine fitting (include/splat2d_coarse.h; s2d_view_fit.hip): view_gradient_kernel's pass from a
+// target (a.from_target, a.src the target) with the view's squared error per tile into a.walk.tile_sqerr (one double per tile of
+// g: every tile's is stored), and deterministic mode's gather.
+hipError_t launch_view_fit(const ViewGradientArgs& a, hipStream_t stream);
 // out[j][i] = view_target_pixel (s2d_view_target_math.h) of the W x H image at ref (half_images: 4 x fp16 per pixel, else RGBA32F).
 hipError_t launch_view_target(const void* ref, bool half_images, int W, int H, float origin_x, float origin_y, float zoom, int out_width,
                               int out_height, float4* out, hipStream_t stream);

@@ -3,9 +3,10 @@
 // (s2d_view_gradient.hip) with the squared error of the view riding along -- and view_target_kernel, which resamples the context's
 // target to a view's window (s2d_view_target_math.h).
 //
-// view_fit_kernel is composed from the shared walks exactly as its sibling is: forward_tile, the resolve in lanes
-// (resolve_level), the top-left lane of an output pixel forms resolved - target, the broadcast times 0.25 per level, backward_tile
-// (UPSTREAM).  One step stands between the resolve and the broadcast: the top-left lane's term (dx * 255)^2 + (dy * 255)^2 +
+// view_fit_kernel is composed exactly as its sibling is, of the same pieces (s2d_view_walk.h): forward_tile, view_top_lane,
+// view_minus_target (the resolve in lanes, then resolved - target in the top-left lane of an output pixel), view_broadcast (times
+// 0.25 per level), view_zero_outside, backward_tile (UPSTREAM).  One step of its own stands between view_minus_target and the
+// broadcast: the top-left lane's term (dx * 255)^2 + (dy * 255)^2 +
 // (dz * 255)^2, a float, as pixel_terms (s2d_loss.hip) and main.cpp:801-802 form it -- every other lane contributes 0 -- is summed
 // over the workgroup in double (block_sum_256) and stored, one plain store, to tile_sqerr[tile].  A tile whose list is empty, or
 // none of whose entries executes, stores the energy of its piece of the target like any other.  The four doubles of the sum lie
@@ -13,7 +14,7 @@
 // walk, and block_sum_256 ends with the barrier the backward walk needs.  The per-tile values are added up in a fixed order by
 // sqerr_reduce (launch_sqerr_finalize), as the training image's are.
 // The gradients are the bytes view_gradient_kernel gives: nothing that reaches backward_tile differs.
-#include "s2d_view.h"
+#include "s2d_view_walk.h"
 #include "s2d_view_target_math.h"
 #include "s2d_walk_backward.h"
 
@@ -41,27 +42,11 @@ __global__ __launch_bounds__(256, (EXACT && DET) ? 4 : 8) void view_fit_kernel(c
     if (c.tid == 0) tile_exec[tile] = n_exec;
     float4 fin = make_float4(crg.x, crg.y, cb, 1.0f);
 
-    // the top-left sample of an output pixel (S divides 8, so the block is inside the grid as a whole or not at all)
-    int lx, ly;
-    pixel_of_thread(c.tid, &lx, &ly);
-    const bool top = c.inside && (lx % S) == 0 && (ly % S) == 0;
-    const size_t o = (size_t)(c.y / S) * (size_t)out_width + (size_t)(c.x / S);
-    float4 u = make_float4(0.f, 0.f, 0.f, 0.f);
-    float rr = fin.x, rg = fin.y, rb = fin.z; // the view's pixel, as view_raster_kernel resolves it
-    if (S >= 2) {
-        rr = resolve_level<1, 8>(rr);
-        rg = resolve_level<1, 8>(rg);
-        rb = resolve_level<1, 8>(rb);
-    }
-    if (S == 4) {
-        rr = resolve_level<2, 16>(rr);
-        rg = resolve_level<2, 16>(rg);
-        rb = resolve_level<2, 16>(rb);
-    }
+    size_t o;
+    const bool top = view_top_lane<S>(c, out_width, &o);
+    float4 u = view_minus_target<S>(fin, top, target, o);
     double e2 = 0.0;
     if (top) {
-        const float4 t = target[o];
-        u = make_float4(rr - t.x, rg - t.y, rb - t.z, 0.0f);
         const float ex = u.x * 255.0f, ey = u.y * 255.0f, ez = u.z * 255.0f; // main.cpp:801-802: float per pixel, double across pixels
         e2 = (double)(ex * ex + ey * ey + ez * ez);
     }
@@ -70,24 +55,8 @@ __global__ __launch_bounds__(256, (EXACT && DET) ? 4 : 8) void view_fit_kernel(c
     __syncthreads();
     const double tile_e2 = block_sum_256(e2, reinterpret_cast<double*>(smem));
     if (c.tid == 0) tile_sqerr[tile] = tile_e2;
-    if (S >= 2) {
-        constexpr int kBlockBits = S == 4 ? (1 | 2 | 8 | 16) : (1 | 8);
-        constexpr int kLevels = S == 4 ? 2 : 1;
-        const int from = c.lane & ~kBlockBits;
-        u.x = __shfl(u.x, from, 64);
-        u.y = __shfl(u.y, from, 64);
-        u.z = __shfl(u.z, from, 64);
-#pragma unroll
-        for (int l = 0; l < kLevels; l++) {
-            u.x *= 0.25f;
-            u.y *= 0.25f;
-            u.z *= 0.25f;
-        }
-    }
-    if (!c.inside) {
-        fin = make_float4(0.f, 0.f, 0.f, 0.f);
-        u = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    view_broadcast<S>(u, c.lane);
+    view_zero_outside(c, fin, u);
     backward_tile<false, NEED_OP, DET, EXACT, false, true>(*reinterpret_cast<BwdShared<DET>*>(smem), c, fin, u, tile_off, list, proj,
                                                            wave_masks, exec_list, n_exec, grads, nullptr, g, det, nullptr,
                                                            SqerrJob{nullptr, 0, nullptr, nullptr});
@@ -117,39 +86,21 @@ __global__ __launch_bounds__(256) void view_target_kernel(const void* __restrict
     out[p] = make_float4(v[0], v[1], v[2], v[3]);
 }
 
-namespace {
-
-template <bool EXACT, int S>
-hipError_t launch_view_fit_flags(const ViewFitArgs& a, hipStream_t stream)
+hipError_t launch_view_fit(const ViewGradientArgs& a, hipStream_t stream)
 {
     const RasterArgs& w = a.walk;
+    if (w.g.num_tiles <= 0 || w.tile_sqerr == nullptr || a.src == nullptr || !a.from_target) return hipErrorInvalidValue;
     const dim3 grid((unsigned)w.g.num_tiles), block(256);
     const std::false_type no; // flags the view has no variants of: pair counting, fp16 images
-    return with_variant([&](auto, auto, auto, auto op, auto d) {
-        hipLaunchKernelGGL((view_fit_kernel<EXACT, S, op, d>), grid, block, 0, stream, w.tile_off, w.list, w.proj, a.target,
-                           w.wave_masks, w.exec_list, w.tile_exec, w.retire_hint, w.grads, w.tile_sqerr, w.g, a.out_width, det_slots(w.det));
-    }, std::bool_constant<EXACT>{}, no, no, w.need_opacity_grad, w.det.now != 0u);
-}
-
-template <bool EXACT>
-hipError_t launch_view_fit_samples(const ViewFitArgs& a, hipStream_t stream)
-{
-    switch (a.samples) {
-    case 1: return launch_view_fit_flags<EXACT, 1>(a, stream);
-    case 2: return launch_view_fit_flags<EXACT, 2>(a, stream);
-    case 4: return launch_view_fit_flags<EXACT, 4>(a, stream);
-    default: return hipErrorInvalidValue; // a missing kernel is an error
-    }
-}
-
-} // namespace
-
-hipError_t launch_view_fit(const ViewFitArgs& a, hipStream_t stream)
-{
-    if (a.walk.g.num_tiles <= 0 || a.walk.tile_sqerr == nullptr || a.target == nullptr) return hipErrorInvalidValue;
-    const hipError_t e = a.walk.exact_exp ? launch_view_fit_samples<true>(a, stream) : launch_view_fit_samples<false>(a, stream);
+    const hipError_t e = with_samples(a.samples, [&](auto samples) {
+        constexpr int S = decltype(samples)::value;
+        return with_variant([&](auto exact, auto, auto, auto op, auto d) {
+            hipLaunchKernelGGL((view_fit_kernel<exact, S, op, d>), grid, block, 0, stream, w.tile_off, w.list, w.proj, a.src, w.wave_masks,
+                               w.exec_list, w.tile_exec, w.retire_hint, w.grads, w.tile_sqerr, w.g, a.out_width, det_slots(w.det));
+        }, w.exact_exp, no, no, w.need_opacity_grad, w.det.now != 0u);
+    });
     if (e != hipSuccess) return e;
-    return launch_det_gather(a.walk, stream); // deterministic mode: the slots of the view's rectangles, summed in slot order into walk.grads
+    return launch_det_gather(w, stream); // deterministic mode: the slots of the view's rectangles, summed in slot order into walk.grads
 }
 
 hipError_t launch_view_target(const void* ref, bool half_images, int W, int H, float origin_x, float origin_y, float zoom, int out_width,

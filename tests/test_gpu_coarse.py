@@ -153,6 +153,39 @@ def test_float_atomics_stay_under_the_bars_of_the_training_sweep(k, samples):
     assert (np.abs(got_mse - want_mse) <= 1e-12 * want_mse).all()
 
 
+FIT_VARIANTS = [(exact, samples, need_op, det) for exact in (False, True) for samples in (1, 2, 4) for need_op in (False, True)
+                for det in (False, True)]
+
+
+@pytest.mark.parametrize("exact,samples,need_op,det", FIT_VARIANTS,
+                         ids=["%s_s%d_%s_%s" % ("exact" if e else "approx", s, "op" if o else "noop", "det" if d else "atomic")
+                              for e, s, o, d in FIT_VARIANTS])
+def test_every_view_fit_kernel_variant_against_the_existing_calls(exact, samples, need_op, det):
+    """A row for each view_fit_kernel<EXACT, S, NEED_OP, DET>: scene M through view 1 (53 x 37, so raster grids of 53 x 37,
+    106 x 74 and 212 x 148: several tiles and partial ones at every S), three iterations.  NEED_OP = false is a step without
+    optimize_opacity, on both sides.  Deterministic rows leave the bytes of the twin's view_backward_device(from_target) +
+    adam_step.  Rows that add with float atomics are held to the bars of
+    test_float_atomics_stay_under_the_bars_of_the_training_sweep; its MSE bar is applied to the first iteration's value, the one
+    both contexts form from the same splats -- the later ones are errors of states the order of the atomic additions has already
+    let differ, and that bar (the rounding of one double sum) says nothing about them."""
+    kw = {"exact_exp": True} if exact else {}
+    got, got_mse, want, want_mse = pair("M", V.VIEWS[0], samples, 3, need_op, False, False, det, **kw)
+    assert got[2] == want[2] and got[2][2] == 3                       # beta powers, iteration count
+    assert got[0] != scene("M").tobytes()                              # something was trained
+    assert len(got_mse) == 3 and np.isfinite(got_mse).all() and (got_mse > 0).all()
+    if det:
+        assert got[0] == want[0]                                       # splats
+        assert got[1] == want[1]                                       # moments
+        assert (np.abs(got_mse - want_mse) <= 1e-12 * want_mse).all()  # (the bar of test_mse_out_is_the_error_of_the_view_before_each_step)
+        return
+    a = np.frombuffer(got[0], dtype=F).reshape(-1, 9).astype(np.float64)
+    b = np.frombuffer(want[0], dtype=F).reshape(-1, 9).astype(np.float64)
+    print("\n[view_fit float atomics] worst parameter difference %.3e (bar %.3e), first mse relative difference %.2e"
+          % (np.abs(a - b).max(), 1e-3 * 0.05 + 1e-5 * np.abs(b).max(), abs(got_mse[0] / want_mse[0] - 1)))
+    assert np.abs(a - b).max() <= 1e-3 * 0.05 + 1e-5 * np.abs(b).max(), np.abs(a - b).max()
+    assert abs(got_mse[0] - want_mse[0]) <= 1e-12 * want_mse[0]
+
+
 # (d) ------------------------------------------------------------------------------------------------------------------------
 def test_identity_view_with_the_contexts_target_is_step():
     tgt = O.synthetic_target(W, H)
