@@ -9,7 +9,7 @@ but every compute call needs the built library and a gfx950 device and raises ot
 One module per concern, re-exported here: _abi (constants, structures, the signature table of the C ABI), _runtime (loading the
 library, one HIP runtime per process), _handle (what the two handles share), trainer (Trainer), multi (MultiTrainer), coarse
 (CoarseTrainer: include/splat2d_coarse.h, with the signatures of its two symbols), backdrop (BackdropTrainer:
-include/splat2d_backdrop.h, likewise); torch_op, torch_backdrop and distributed import torch and are imported by name.
+include/splat2d_backdrop.h, likewise), weights (WeightedTrainer: include/splat2d_weights.h, likewise); torch_op, torch_backdrop and distributed import torch and are imported by name.
 
 The package name starts with a digit, so import it with
     importlib.import_module("2dgaussiansplatting_amd")
@@ -31,6 +31,7 @@ from .backdrop import BackdropTrainer
 from .coarse import CoarseTrainer
 from .multi import MultiTrainer
 from .trainer import Trainer
+from .weights import WeightedTrainer
 
-__all__ = ["Trainer", "MultiTrainer", "CoarseTrainer", "BackdropTrainer", "S2DError", "load_library", "use_library", "hip_runtimes_mapped",
+__all__ = ["Trainer", "MultiTrainer", "CoarseTrainer", "BackdropTrainer", "WeightedTrainer", "S2DError", "load_library", "use_library", "hip_runtimes_mapped",
            "SPLAT_DTYPE", "ADAM_DTYPE", "STATUS_NAMES"]

@@ -16,11 +16,11 @@ LIB_PATH = os.path.join(LIB_DIR, "libsplat2d_hip.so")
 HOST_DIR = os.path.join(PKG_DIR, "host")
 TRAIN_BIN = os.path.join(LIB_DIR, "splat2d_train")
 
-HIP_SOURCES = ["s2d_api.hip", "s2d_api_loss.hip", "s2d_api_placement.hip", "s2d_api_optim.hip", "s2d_api_alive.hip", "s2d_api_rows.hip", "s2d_api_view.hip", "s2d_api_coarse.hip", "s2d_api_backdrop.hip", "s2d_api_test.hip", "s2d_sequence.hip", "s2d_lists.hip", "s2d_state.hip", "s2d_context.hip", "s2d_scan_sort.hip", "s2d_binning.hip", "s2d_tilelists.hip", "s2d_raster.hip",
+HIP_SOURCES = ["s2d_api.hip", "s2d_api_loss.hip", "s2d_api_placement.hip", "s2d_api_optim.hip", "s2d_api_alive.hip", "s2d_api_rows.hip", "s2d_api_view.hip", "s2d_api_coarse.hip", "s2d_api_backdrop.hip", "s2d_api_weights.hip", "s2d_api_test.hip", "s2d_sequence.hip", "s2d_lists.hip", "s2d_state.hip", "s2d_context.hip", "s2d_scan_sort.hip", "s2d_binning.hip", "s2d_tilelists.hip", "s2d_raster.hip",
                "s2d_raster_ranges.hip", "s2d_raster_gradient.hip", "s2d_raster_det.hip", "s2d_raster_reference.hip", "s2d_raster_coverage.hip", "s2d_backdrop.hip",
-               "s2d_loss.hip", "s2d_seed.hip", "s2d_view.hip", "s2d_view_gradient.hip", "s2d_view_fit.hip", "s2d_optim.hip", "s2d_optim_controls.hip", "s2d_alive.hip", "s2d_halo.hip",
+               "s2d_loss.hip", "s2d_loss_weighted.hip", "s2d_seed.hip", "s2d_view.hip", "s2d_view_gradient.hip", "s2d_view_fit.hip", "s2d_optim.hip", "s2d_optim_controls.hip", "s2d_alive.hip", "s2d_halo.hip",
                "s2d_multi.hip", "s2d_multi_run.hip", "s2d_multi_ownership.hip", "s2d_multi_replicated.hip", "s2d_multi_stop.hip"]
-HIP_HEADERS = ["s2d_device.h", "s2d_math.h", "s2d_walk.h", "s2d_walk_backward.h", "s2d_owned.h", "s2d_lists.h", "s2d_state.h", "s2d_context.h", "s2d_ctx.h", "s2d_sequence.h", "s2d_ranges.h", "s2d_density.h", "s2d_loss.h", "s2d_seed.h", "s2d_seed_math.h", "s2d_optim_rates.h", "s2d_adam.h", "s2d_alive.h", "s2d_view.h", "s2d_view_walk.h", "s2d_view_math.h", "s2d_view_target_math.h", "s2d_backdrop.h",
+HIP_HEADERS = ["s2d_device.h", "s2d_math.h", "s2d_walk.h", "s2d_walk_backward.h", "s2d_owned.h", "s2d_lists.h", "s2d_state.h", "s2d_context.h", "s2d_ctx.h", "s2d_sequence.h", "s2d_ranges.h", "s2d_density.h", "s2d_loss.h", "s2d_loss_weighted.h", "s2d_seed.h", "s2d_seed_math.h", "s2d_optim_rates.h", "s2d_adam.h", "s2d_alive.h", "s2d_view.h", "s2d_view_walk.h", "s2d_view_math.h", "s2d_view_target_math.h", "s2d_backdrop.h",
                "s2d_multi.h", "s2d_multi_plan.h"]
 
 # -ffp-contract=off: the kernels keep the reference's evaluation order (no FMA contraction) wherever a
@@ -71,7 +71,8 @@ def build_hip_library(force=False, verbose=False):
     deps = srcs + [os.path.join(CSRC, h) for h in HIP_HEADERS] + [os.path.join(ROOT, "include", "splat2d.h"),
                                                                    os.path.join(ROOT, "include", "splat2d_test.h"),
                                                                    os.path.join(ROOT, "include", "splat2d_coarse.h"),
-                                                                   os.path.join(ROOT, "include", "splat2d_backdrop.h")]
+                                                                   os.path.join(ROOT, "include", "splat2d_backdrop.h"),
+                                                                   os.path.join(ROOT, "include", "splat2d_weights.h")]
     if force or _stale(LIB_PATH, deps):
         os.makedirs(LIB_DIR, exist_ok=True)
         cmd = [hipcc()] + HIPCC_FLAGS + ["-o", LIB_PATH] + srcs
@@ -88,7 +89,7 @@ def build_host_program(force=False, verbose=False):
         return None
     deps = [src, os.path.join(HOST_DIR, "image_io.h"), os.path.join(HOST_DIR, "overlay.h"), os.path.join(HOST_DIR, "jpeg_decode.h"),
             os.path.join(ROOT, "include", "splat2d.h"), os.path.join(ROOT, "include", "splat2d_coarse.h"),
-            os.path.join(ROOT, "include", "splat2d_backdrop.h"), LIB_PATH]
+            os.path.join(ROOT, "include", "splat2d_backdrop.h"), os.path.join(ROOT, "include", "splat2d_weights.h"), LIB_PATH]
     if force or _stale(TRAIN_BIN, deps):
         rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
         # -ffp-contract=off: overlay.h restates main.cpp:441-477 operation by operation (tests compare its vertices bitwise)

@@ -99,6 +99,8 @@ int s2d_backdrop_grads(s2d_ctx* c, const float* upstream_rows_device, float* dpl
     if (!c) return S2D_E_INVALID;
     if (((uintptr_t)upstream_rows_device | (uintptr_t)dplane_device) & 15u)
         return fail(c, S2D_E_INVALID, "s2d_backdrop_grads: the image gradient and the plane's gradient must be 16-byte aligned");
+    if (!upstream_rows_device)
+        if (int rc = weights_refused(c, "s2d_backdrop_grads", "a NULL upstream is image0 - target without the plane")) return rc;
     if (int rc = throughput_refused(c, "s2d_backdrop_grads")) return rc;
     if (!upstream_rows_device && !c->fresh.target()) return fail(c, S2D_E_STATE, "s2d_backdrop_grads: no target image set (s2d_set_target)");
     if (!dplane_device && !rgb_out) return S2D_OK; // nothing is asked for

@@ -94,6 +94,7 @@ int s2d_step_view(s2d_ctx* c, const s2d_view_config* cfg, const float* target_de
     if (!c) return S2D_E_INVALID;
     if (int rc = view_pass_config_refused(c, cfg, "s2d_step_view")) return rc;
     if (int rc = view_pass_context_refused(c, "s2d_step_view")) return rc;
+    if (int rc = weights_refused(c, "s2d_step_view", "the plane is not resampled to a view")) return rc;
     if (int rc = backdrop_refused(c, "s2d_step_view")) return rc; // (view_fit_kernel forms the final colour itself, without the backdrop)
     if (flags & ~S2D_STEP_OPTIMIZE_OPACITY) return fail(c, S2D_E_INVALID, "s2d_step_view: unknown flags %#x", flags);
     if (iters < 0) return fail(c, S2D_E_INVALID, "s2d_step_view: iters < 0");

@@ -31,12 +31,58 @@ int queue_loss(s2d_ctx* c, const s2d_loss_config* cfg, float4* dimage, int slot,
     a.w_mse = cfg->w_mse; a.w_l1 = cfg->w_l1; a.w_dssim = cfg->w_dssim;
     a.maps = c->d_loss_maps; a.dimage = dimage; a.partial = c->loss.partial(); a.out3 = c->loss.slot(slot); a.sqerr_out = sqerr_out;
     a.status = c->d_status; a.iteration = c->iterations;
-    S2D_HIP(c, launch_loss(a, c->stream));
+    if (c->weights.set()) { // L_omega: the weighted kernels, their four totals beside the three (include/splat2d_weights.h)
+        WeightedLossArgs wa;
+        wa.base = a;
+        wa.omega = c->weights.plane(); wa.partial4 = c->weights.partial(); wa.out4 = c->weights.slot(slot);
+        S2D_HIP(c, launch_loss_weighted(wa, c->stream));
+    } else {
+        S2D_HIP(c, launch_loss(a, c->stream));
+    }
     c->loss.record(slot, cfg->w_mse, cfg->w_l1, cfg->w_dssim);
     return S2D_OK;
 }
 
 } // namespace
+
+// s2d_backward / s2d_forward_backward / s2d_step under a weight plane: the weighted loss pass of the squared error alone.
+int queue_weighted_backward(s2d_ctx* c, bool need_opacity_grad, bool density)
+{
+    static const s2d_loss_config mse_only = {(uint32_t)sizeof(s2d_loss_config), 1.0f, 0.0f, 0.0f};
+    if (int rc = weights_refused_by_context(c, "the backward pass")) return rc;
+    return queue_loss_backward(c, &mse_only, need_opacity_grad, density);
+}
+
+// What the weighted loss passes cannot work on (`who`): what the loss passes refuse for the context.  The setters ask this
+// before they take a plane; a pass asks again, because a held set (s2d_halo_commit) may have come since.
+int weights_refused_by_context(s2d_ctx* c, const char* who)
+{
+    if (c->cfg.flags & S2D_CFG_COVERAGE) return fail(c, S2D_E_INVALID, "%s: pixel weights are not available with S2D_CFG_COVERAGE", who);
+    if (c->cfg.flags & S2D_CFG_COUNT_PAIRS) return fail(c, S2D_E_INVALID, "%s: pixel weights are not available with S2D_CFG_COUNT_PAIRS", who);
+    if (c->g.row_begin != 0 || c->g.row_end != c->g.H)
+        return fail(c, S2D_E_INVALID, "%s: pixel weights need the whole image, this context owns a row slab", who);
+    if (c->state.kind() == SplatState::Subset::Slab)
+        return fail(c, S2D_E_INVALID, "%s: pixel weights need every splat, this context holds a subset (s2d_halo_commit); "
+                    "s2d_set_pixel_weights(ctx, NULL) removes them", who);
+    return S2D_OK;
+}
+
+// The four sums of a weighted pass -> the terms s2d_loss_get reports (mse unweighted, the rest of L_omega).
+s2d_loss_terms weighted_loss_terms_of(const s2d_ctx* c, const double* sums4, const float* w, double* weighted_mse)
+{
+    const double n3 = mse_norm(c);
+    s2d_loss_terms t;
+    t.mse = sums4[0] / (255.0 * 255.0) / n3;
+    const double wmse = sums4[1] / (255.0 * 255.0) / n3;
+    t.l1 = w[1] > 0.0f ? sums4[2] / n3 : std::nan("");
+    t.dssim = w[2] > 0.0f ? sums4[3] / n3 : std::nan("");
+    t.total = 0.0;
+    if (w[0] > 0.0f) t.total += (double)w[0] * 0.5 * wmse;
+    if (w[1] > 0.0f) t.total += (double)w[1] * t.l1;
+    if (w[2] > 0.0f) t.total += (double)w[2] * t.dssim;
+    if (weighted_mse) *weighted_mse = wmse;
+    return t;
+}
 
 // s2d_backward for the loss: the loss kernels into the context's gradient image, the backward walk from it, and the
 // squared error of the iteration in the ring as the loss finalize left it (SqerrBy::LossPass).
@@ -90,6 +136,12 @@ int s2d_loss_get(s2d_ctx* c, s2d_loss_terms* out)
     if (!c || !out) return S2D_E_INVALID;
     if (c->loss.last_slot() < 0) return fail(c, S2D_E_STATE, "no loss pass has run yet");
     if (int rc = use_device(c)) return rc;
+    if (c->weights.set()) { // (a pass older than the plane is forgotten when the plane is set: the last one was a weighted one)
+        double sums4[kWeightedTerms];
+        if (int rc = read_back(c, sums4, c->weights.slot(c->loss.last_slot()), sizeof(sums4))) return rc;
+        *out = weighted_loss_terms_of(c, sums4, c->loss.last_weights(), nullptr);
+        return S2D_OK;
+    }
     double sums[3];
     if (int rc = read_back(c, sums, c->loss.slot(c->loss.last_slot()), sizeof(sums))) return rc;
     *out = loss_terms_of(c, sums, c->loss.last_weights());

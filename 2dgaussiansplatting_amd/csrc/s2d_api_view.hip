@@ -153,6 +153,8 @@ int view_gradient_refused(s2d_ctx* c, const s2d_view_config* cfg, const float* s
     if (!src) return fail(c, S2D_E_INVALID, "%s: NULL image gradient (or target)", who);
     if ((uintptr_t)src & 15u) return fail(c, S2D_E_INVALID, "%s: the image gradient (or target) must be 16-byte aligned", who);
     if (flags & ~(S2D_VIEW_BWD_FROM_TARGET | S2D_BWD_SKIP_OPACITY_GRAD)) return fail(c, S2D_E_INVALID, "%s: unknown flags %#x", who, flags);
+    if (flags & S2D_VIEW_BWD_FROM_TARGET)
+        if (int rc = weights_refused(c, who, "S2D_VIEW_BWD_FROM_TARGET forms view - target without the plane, which is not resampled to a view")) return rc;
     if (int rc = backdrop_refused(c, who)) return rc; // (view_gradient_kernel forms the final colour itself, without the backdrop)
     return view_pass_context_refused(c, who);
 }

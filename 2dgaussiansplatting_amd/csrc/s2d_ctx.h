@@ -12,6 +12,7 @@
 #include "s2d_context.h"
 #include "s2d_lists.h"
 #include "s2d_loss.h"
+#include "s2d_loss_weighted.h"
 #include "s2d_optim_rates.h"
 #include "s2d_owned.h"
 #include "s2d_seed.h"
@@ -60,6 +61,7 @@ struct s2d_ctx {
     DevBuf<uint8_t> d_frozen;      // n bytes, non-zero = frozen; allocated by the first mask
     SeedScratch seed;              // the importance map of s2d_importance / s2d_seed_splats / s2d_reseed (s2d_seed.h), on first use
     ViewScratch view;              // the records, lists and image of s2d_view_splats / s2d_render_view (s2d_view.h), on first use
+    PixelWeights weights;          // the weight plane of the losses (include/splat2d_weights.h, s2d_loss_weighted.h), on first use
     BackdropState backdrop;        // what image0 is composited over (include/splat2d_backdrop.h, s2d_backdrop.h), on first use
     DevBuf<DeviceStatus> d_status;
     DevBuf<PairCounters> d_counters;
@@ -127,6 +129,14 @@ S2D_LOCAL inline int coverage_refused(s2d_ctx* c, const char* who)
 S2D_LOCAL inline int backdrop_refused(s2d_ctx* c, const char* who)
 {
     if (c->backdrop.set()) return fail(c, S2D_E_INVALID, "%s: not available while a backdrop is set (s2d_set_backdrop(ctx, NULL) removes it)", who);
+    return S2D_OK;
+}
+
+// What cannot follow a pixel-weight plane (`who`: a call's name, `why`: what it would need).  S2D_E_INVALID, before any device work.
+S2D_LOCAL inline int weights_refused(s2d_ctx* c, const char* who, const char* why)
+{
+    if (c->weights.set())
+        return fail(c, S2D_E_INVALID, "%s: not available while pixel weights are set (%s; s2d_set_pixel_weights(ctx, NULL) removes them)", who, why);
     return S2D_OK;
 }
 

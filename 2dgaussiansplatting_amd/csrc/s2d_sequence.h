@@ -69,6 +69,11 @@ S2D_LOCAL int parse_walk_flags(s2d_ctx* c, uint32_t flags, bool step, WalkFlags*
 S2D_LOCAL int run_steps(s2d_ctx* c, int iters, uint32_t flags, const s2d_loss_config* loss, double* loss_out, double* mse_out);
 S2D_LOCAL int queue_loss_backward(s2d_ctx* c, const s2d_loss_config* cfg, bool need_opacity_grad, bool density);
 S2D_LOCAL s2d_loss_terms loss_terms_of(const s2d_ctx* c, const double* sums, const float* w);
+// Under a pixel-weight plane (include/splat2d_weights.h; s2d_api_loss.hip): what the context refuses a plane for, the backward
+// pass of s2d_backward / s2d_step (the weighted loss pass with weights (1, 0, 0), then the walk), and the terms of four sums.
+S2D_LOCAL int weights_refused_by_context(s2d_ctx* c, const char* who);
+S2D_LOCAL int queue_weighted_backward(s2d_ctx* c, bool need_opacity_grad, bool density);
+S2D_LOCAL s2d_loss_terms weighted_loss_terms_of(const s2d_ctx* c, const double* sums4, const float* w, double* weighted_mse);
 
 S2D_LOCAL int queue_status_read(s2d_ctx* c); // -> h_status, valid once the stream has been synchronised
 S2D_LOCAL int check_status(s2d_ctx* c);      // ... read, waited for and judged
@@ -77,6 +82,7 @@ S2D_LOCAL int check_status(s2d_ctx* c);      // ... read, waited for and judged
 // ("Adam step queued" and "non-finite step judged" are queue_adam's and judge_status's own.)
 S2D_LOCAL void target_replaced(s2d_ctx* c);                 // s2d_set_target, _synthetic
 S2D_LOCAL void backdrop_replaced(s2d_ctx* c);               // s2d_set_backdrop, _device: set, replaced or removed
+S2D_LOCAL void weights_replaced(s2d_ctx* c);                // s2d_set_pixel_weights, _device: set, replaced or removed
 S2D_LOCAL int splats_replaced(s2d_ctx* c);                  // s2d_init_splats, s2d_set_splats
 S2D_LOCAL int splats_replaced_from_device(s2d_ctx* c);      // s2d_set_splats_device
 S2D_LOCAL int rows_replaced(s2d_ctx* c, int32_t what);      // S2D_ROWS_*: s2d_rows_scatter; s2d_relocate and the seeding write S2D_ROWS_SPLATS (with their moments)

@@ -297,6 +297,7 @@ int parse_walk_flags(s2d_ctx* c, uint32_t flags, bool step, WalkFlags* out)
 int queue_backward(s2d_ctx* c, bool need_opacity_grad, const float4* upstream, bool density)
 {
     if (!c->fresh.forward()) return fail(c, S2D_E_STATE, "the backward pass needs s2d_forward on the current parameters");
+    if (!upstream && c->weights.set()) return queue_weighted_backward(c, need_opacity_grad, density); // (comes back with its gradient image)
     if (c->surface.reference_order()) return queue_backward_reference(c, need_opacity_grad, upstream);
     if (density && c->ranges.active())
         return fail(c, S2D_E_NOMEM, "density statistics are not available for scenes beyond %llu (tile, splat) pairs (index-range rendering)",
@@ -316,10 +317,10 @@ int queue_backward(s2d_ctx* c, bool need_opacity_grad, const float4* upstream, b
 // Forward + backward (+ squared error) of the current parameters through the fused kernel.  Pair counting is a
 // property of the separate kernels only, so a counting context takes those; so does a coverage context, whose kernels are the
 // separate ones (image0 stored every time, whatever write_image says), and a context with a backdrop, whose backward walk reads
-// the composite from image0.
+// the composite from image0, and a context with pixel weights, whose loss pass stands between the two walks.
 int queue_forward_backward(s2d_ctx* c, bool need_opacity_grad, bool write_image)
 {
-    if ((c->cfg.flags & S2D_CFG_COUNT_PAIRS) || c->surface.reference_order() || coverage(c) || c->backdrop.set()) { // (reference order: its backward pass is a launch of its own)
+    if ((c->cfg.flags & S2D_CFG_COUNT_PAIRS) || c->surface.reference_order() || coverage(c) || c->backdrop.set() || c->weights.set()) { // (reference order: its backward pass is a launch of its own)
         if (int rc = queue_forward(c)) return rc;
         return queue_backward(c, need_opacity_grad);
     }
@@ -394,6 +395,12 @@ int run_steps(s2d_ctx* c, int iters, uint32_t flags, const s2d_loss_config* loss
     WalkFlags wf;
     if (int rc = parse_walk_flags(c, flags, true, &wf)) return rc;
     if (int rc = use_device(c)) return rc;
+    // Under a weight plane s2d_step is s2d_step_loss with the squared error alone: the plane acts in the loss pass.
+    static const s2d_loss_config mse_only = {(uint32_t)sizeof(s2d_loss_config), 1.0f, 0.0f, 0.0f};
+    const bool weighted = c->weights.set();
+    if (weighted)
+        if (int rc = weights_refused_by_context(c, loss ? "s2d_step_loss" : "s2d_step")) return rc;
+    if (weighted && !loss) loss = &mse_only;
     const double norm = mse_norm(c);
     const float w[3] = {loss ? loss->w_mse : 0.0f, loss ? loss->w_l1 : 0.0f, loss ? loss->w_dssim : 0.0f};
     const int call_first_iter = c->iterations;
@@ -419,14 +426,16 @@ int run_steps(s2d_ctx* c, int iters, uint32_t flags, const s2d_loss_config* loss
         const bool with_status = done + piece == iters && piece <= SqerrTrace::kPinned;
         double* const mse_dst = !mse_out ? nullptr : with_status ? c->trace.pinned() : mse_out + done;
         if (loss_out) {
-            sums.resize((size_t)3 * piece);
-            S2D_HIP(c, c->loss.read(first_iter, piece, sums.data()));
+            sums.resize((size_t)(weighted ? kWeightedTerms : 3) * piece);
+            S2D_HIP(c, weighted ? c->weights.read(first_iter, piece, sums.data()) : c->loss.read(first_iter, piece, sums.data()));
         }
         if (mse_dst) S2D_HIP(c, c->trace.read(first_iter, piece, mse_dst));
         if (with_status)
             if (int rc = queue_status_read(c)) return rc;
         if (with_status || loss_out || mse_out) S2D_HIP(c, hipStreamSynchronize(c->stream));
-        for (int k = 0; loss_out && k < piece; k++) loss_out[done + k] = loss_terms_of(c, &sums[(size_t)3 * k], w).total;
+        for (int k = 0; loss_out && k < piece; k++)
+            loss_out[done + k] = weighted ? weighted_loss_terms_of(c, &sums[(size_t)kWeightedTerms * k], w, nullptr).total
+                                          : loss_terms_of(c, &sums[(size_t)3 * k], w).total;
         for (int k = 0; mse_out && k < piece; k++) mse_out[done + k] = mse_dst[k] / norm; // main.cpp:805
         status_read = with_status;
         done += piece;
@@ -463,6 +472,10 @@ void target_replaced(s2d_ctx* c)
 
 // What image0 is composited over changed: the frames are stale; the projection and the lists depend on the splats alone.
 void backdrop_replaced(s2d_ctx* c) { c->fresh.invalidate(Stale::Frames); }
+
+// The weight plane of the losses was set, replaced or removed: the frames, the projection and the lists stand (no pass that
+// produced them read it); the terms of the last loss pass are those of another loss and are forgotten.
+void weights_replaced(s2d_ctx* c) { c->loss.record(-1, 0.0f, 0.0f, 0.0f); }
 
 // Every splat is new (init / set_splats): the lists are none of theirs, and a non-finite event of the old ones no longer
 // stops the queue.  (init also zeroes the gradients and restarts the counters, and asks for the arrays with

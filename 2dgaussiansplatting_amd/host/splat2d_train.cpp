@@ -30,6 +30,7 @@
 #include "overlay.h"
 #include "splat2d.h"
 #include "splat2d_backdrop.h"
+#include "splat2d_weights.h"
 #include "splat2d_coarse.h"
 
 namespace {
@@ -124,6 +125,12 @@ struct Options {
     // --out-image, --out-size and --out-view include it.  One context; a checkpoint does not carry it.
     bool have_background = false, background_malformed = false;
     float background[3] = {0, 0, 0};
+    // --weight-image PATH [--weight-gain G]: a pixel-weight plane (splat2d_weights.h) from the first channel of an image of the
+    // target's size: omega = channel / 255 (a mask), or with the gain omega = 1 + G * channel / 255 (an emphasis).  One context;
+    // a checkpoint does not carry it.  The gain's form is provisional.
+    std::string weight_image;
+    bool have_weight_gain = false, weight_gain_malformed = false;
+    float weight_gain = 0.0f;
     bool replicated = false;    // --exchange dense: replicated state + RCCL all-reduce of all gradients (default: slab ownership)
                                 // (RCCL takes one rank per GPU): a rehearsal of the N-rank host logic on a box with fewer GPUs
 };
@@ -153,7 +160,7 @@ int usage()
                  "                     [--lr-groups P,S,R,C,O [--lr-final-ratio P,S,R,C,O --lr-decay-iters T]] [--rebin-margin PX] [--freeze-unmoved]\n"
                  "                     [--alive-from K0] [--grow-every M --grow-count C [--grow-scale X]]\n"
                  "                     [--prune-every K [--prune-min-weight W] [--prune-window S]] [--coverage]\n"
-                 "                     [--background R,G,B]\n"
+                 "                     [--background R,G,B] [--weight-image file [--weight-gain G]]\n"
                  "  --loss-weights M,L,D: train with the sum over pixels and channels of M * d^2 / 2 + L * |d| + D * (1 - SSIM), e.g.\n"
                  "    0,0.8,0.2, instead of the reference's squared error (one GPU only); every line ends with the loss's mean.\n"
                  "  --relocate-every K: before iteration K, 2K, ... move the starved splats (summed T * alpha per pass below W) onto\n"
@@ -197,6 +204,12 @@ int usage()
                  "  --background R,G,B: draw and train the splats over that colour instead of black, e.g. 1,1,1 for a page or a chart on\n"
                  "    white; --out-image, --out-size and --out-view include it.  One GPU only; not with --coverage, --reference-order or\n"
                  "    --coarse.  A checkpoint does not carry the background: give the option again with --load-checkpoint.\n");
+    std::fprintf(stderr,
+                 "  --weight-image file [--weight-gain G]: weigh every pixel's loss by a plane taken from the first channel of an image\n"
+                 "    of the target's size: channel / 255 (black = ignore the pixel, a mask), or with the gain 1 + G * channel / 255\n"
+                 "    (white = G + 1 times as important; provisional).  Every line ends with the weighted loss's mean, wloss; mse stays\n"
+                 "    the plain one.  One GPU only; not with --coverage or --coarse.  A checkpoint does not carry the weight plane: give\n"
+                 "    the option again with --load-checkpoint.\n");
     return 2;
 }
 
@@ -396,6 +409,14 @@ int main(int argc, char** argv)
         else if (a == "--coverage") o.coverage = true;
         else if (a == "--coarse") o.coarse_malformed = !parse_coarse(next("--coarse"), &o.coarse);
         else if (a == "--coarse-samples") o.coarse_samples = std::atoi(next("--coarse-samples"));
+        else if (a == "--weight-image") o.weight_image = next("--weight-image");
+        else if (a == "--weight-gain") {
+            char* end = nullptr;
+            const char* text = next("--weight-gain");
+            o.weight_gain = std::strtof(text, &end);
+            o.weight_gain_malformed = end == text || *end != '\0' || !(o.weight_gain >= 0.0f) || !std::isfinite(o.weight_gain);
+            o.have_weight_gain = true;
+        }
         else if (a == "--background") { o.background_malformed = !parse_background(next("--background"), o.background); o.have_background = true; }
         else return usage();
     }
@@ -443,6 +464,24 @@ int main(int argc, char** argv)
         }
         if (o.coverage || o.reference_order || !o.coarse.empty() || o.coarse_malformed) {
             std::fprintf(stderr, "--background is not available with --coverage, --reference-order or --coarse\n");
+            return 2;
+        }
+    }
+    if (o.have_weight_gain && o.weight_image.empty()) {
+        std::fprintf(stderr, "--weight-gain scales a weight image: give --weight-image as well\n");
+        return 2;
+    }
+    if (!o.weight_image.empty()) { // (all of it before a file or the device is touched)
+        if (o.weight_gain_malformed) {
+            std::fprintf(stderr, "--weight-gain takes one finite value >= 0, e.g. 3\n");
+            return 2;
+        }
+        if (o.gpus > 1 || std::getenv("S2D_TRAIN_FORCE_MULTI")) {
+            std::fprintf(stderr, "--weight-image works on one context: the multi-device handle has no pixel weights\n");
+            return 2;
+        }
+        if (o.coverage || !o.coarse.empty() || o.coarse_malformed) {
+            std::fprintf(stderr, "--weight-image is not available with --coverage or --coarse\n");
             return 2;
         }
     }
@@ -576,10 +615,31 @@ int main(int argc, char** argv)
         }
         return nullptr;
     };
+    std::vector<float> weight_plane; // --weight-image: read and sized before the device is asked for anything
+    if (!o.weight_image.empty()) {
+        s2dio::Image8 wim;
+        if (!s2dio::load_image(o.weight_image, &wim)) {
+            std::fprintf(stderr, "cannot read the weight image %s\n", o.weight_image.c_str());
+            return 1;
+        }
+        if (wim.w != W || wim.h != H) {
+            std::fprintf(stderr, "the weight image %s is %dx%d, the target %dx%d: --weight-image needs the target's size\n",
+                         o.weight_image.c_str(), wim.w, wim.h, W, H);
+            return 2;
+        }
+        weight_plane.resize((size_t)W * H);
+        for (size_t p = 0; p < weight_plane.size(); p++) {
+            const float v = (float)wim.rgb[p * 3] / 255.0f;
+            weight_plane[p] = o.have_weight_gain ? 1.0f + o.weight_gain * v : v;
+        }
+    }
+    const bool weighted = !o.weight_image.empty();
+    static const s2d_loss_config mse_only = {(uint32_t)sizeof(s2d_loss_config), 1.0f, 0.0f, 0.0f};
     bool views_held = false; // a stage ran and s2d_view_release has not followed yet
     Session S;
     CK(S.create(o, W, H));
     if (o.have_background) CK(s2d_set_backdrop(S.ctx, o.background));
+    if (!o.weight_image.empty()) CK(s2d_set_pixel_weights(S.ctx, weight_plane.data()));
     if (have_optim) { // (groups without a rate of their own: the one --lr)
         s2d_optim_config oc;
         std::memset(&oc, 0, sizeof(oc));
@@ -781,12 +841,14 @@ int main(int argc, char** argv)
             vc.format = S2D_VIEW_RGBA32F;
             CK(s2d_step_view(S.ctx, &vc, nullptr, k, step_flags, mse.data()));
             views_held = true;
-        } else if (o.have_loss) CK(s2d_step_loss(S.ctx, k, step_flags, &o.loss, loss.data(), mse.data()));
+        } else if (o.have_loss || weighted) // (under a plane s2d_step is s2d_step_loss of the squared error: this way the loss comes back)
+            CK(s2d_step_loss(S.ctx, k, step_flags, o.have_loss ? &o.loss : &mse_only, loss.data(), mse.data()));
         else CK(S.step(k, step_flags, mse.data()));
         if (!o.quiet)
             for (int j = 0; j < k; j++) {
                 std::printf("%d itr, mse %.4f", iterations + j, mse[(size_t)j]); // main.cpp:807
                 if (o.have_loss) std::printf(", loss %.6f", loss[(size_t)j]);
+                if (weighted) std::printf(", wloss %.6f", loss[(size_t)j]);
                 std::printf("\n");
             }
         iterations += k; // main.cpp:809
