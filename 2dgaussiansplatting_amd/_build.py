@@ -20,7 +20,7 @@ HIP_SOURCES = ["s2d_api.hip", "s2d_api_loss.hip", "s2d_api_placement.hip", "s2d_
                "s2d_raster_ranges.hip", "s2d_raster_gradient.hip", "s2d_raster_det.hip", "s2d_raster_reference.hip", "s2d_raster_coverage.hip", "s2d_backdrop.hip",
                "s2d_loss.hip", "s2d_loss_weighted.hip", "s2d_seed.hip", "s2d_view.hip", "s2d_view_gradient.hip", "s2d_view_fit.hip", "s2d_optim.hip", "s2d_optim_controls.hip", "s2d_alive.hip", "s2d_halo.hip",
                "s2d_multi.hip", "s2d_multi_run.hip", "s2d_multi_ownership.hip", "s2d_multi_replicated.hip", "s2d_multi_stop.hip"]
-HIP_HEADERS = ["s2d_device.h", "s2d_math.h", "s2d_walk.h", "s2d_walk_backward.h", "s2d_owned.h", "s2d_lists.h", "s2d_state.h", "s2d_context.h", "s2d_ctx.h", "s2d_sequence.h", "s2d_ranges.h", "s2d_density.h", "s2d_loss.h", "s2d_loss_weighted.h", "s2d_seed.h", "s2d_seed_math.h", "s2d_optim_rates.h", "s2d_adam.h", "s2d_alive.h", "s2d_view.h", "s2d_view_walk.h", "s2d_view_math.h", "s2d_view_target_math.h", "s2d_backdrop.h",
+HIP_HEADERS = ["s2d_device.h", "s2d_math.h", "s2d_walk.h", "s2d_walk_backward.h", "s2d_owned.h", "s2d_lists.h", "s2d_state.h", "s2d_context.h", "s2d_ctx.h", "s2d_sequence.h", "s2d_ranges.h", "s2d_density.h", "s2d_loss.h", "s2d_loss_kernels.h", "s2d_loss_weighted.h", "s2d_seed.h", "s2d_seed_math.h", "s2d_optim_rates.h", "s2d_adam.h", "s2d_alive.h", "s2d_view.h", "s2d_view_walk.h", "s2d_view_math.h", "s2d_view_target_math.h", "s2d_backdrop.h",
                "s2d_multi.h", "s2d_multi_plan.h"]
 
 # -ffp-contract=off: the kernels keep the reference's evaluation order (no FMA contraction) wherever a

@@ -24,17 +24,17 @@ int loss_refused(s2d_ctx* c, const s2d_loss_config* cfg)
 int queue_loss(s2d_ctx* c, const s2d_loss_config* cfg, float4* dimage, int slot, double* sqerr_out)
 {
     if (!c->fresh.forward()) return fail(c, S2D_E_STATE, "the loss needs s2d_forward on the current parameters");
-    S2D_HIP(c, c->loss.ensure(c->g.W, c->g.H, c->stream));
+    S2D_HIP(c, c->loss.ring.ensure(c->g.W, c->g.H, c->stream));
     if (cfg->w_dssim > 0.0f && !c->d_loss_maps) S2D_HIP(c, c->d_loss_maps.alloc((size_t)kLossMapPlanes * slab_pixels(c)));
     LossArgs a;
     a.image0 = c->d_image0; a.image_ref = c->d_ref; a.half_images = c->half_images; a.W = c->g.W; a.H = c->g.H;
     a.w_mse = cfg->w_mse; a.w_l1 = cfg->w_l1; a.w_dssim = cfg->w_dssim;
-    a.maps = c->d_loss_maps; a.dimage = dimage; a.partial = c->loss.partial(); a.out3 = c->loss.slot(slot); a.sqerr_out = sqerr_out;
+    a.maps = c->d_loss_maps; a.dimage = dimage; a.partial = c->loss.ring.partial(); a.out3 = c->loss.ring.slot(slot); a.sqerr_out = sqerr_out;
     a.status = c->d_status; a.iteration = c->iterations;
     if (c->weights.set()) { // L_omega: the weighted kernels, their four totals beside the three (include/splat2d_weights.h)
         WeightedLossArgs wa;
         wa.base = a;
-        wa.omega = c->weights.plane(); wa.partial4 = c->weights.partial(); wa.out4 = c->weights.slot(slot);
+        wa.omega = c->weights.plane(); wa.partial4 = c->weights.ring.partial(); wa.out4 = c->weights.ring.slot(slot);
         S2D_HIP(c, launch_loss_weighted(wa, c->stream));
     } else {
         S2D_HIP(c, launch_loss(a, c->stream));
@@ -67,15 +67,29 @@ int weights_refused_by_context(s2d_ctx* c, const char* who)
     return S2D_OK;
 }
 
-// The four sums of a weighted pass -> the terms s2d_loss_get reports (mse unweighted, the rest of L_omega).
-s2d_loss_terms weighted_loss_terms_of(const s2d_ctx* c, const double* sums4, const float* w, double* weighted_mse)
+// s2d_backward for the loss: the loss kernels into the context's gradient image, the backward walk from it, and the
+// squared error of the iteration in the ring as the loss finalize left it (SqerrBy::LossPass).
+int queue_loss_backward(s2d_ctx* c, const s2d_loss_config* cfg, bool need_opacity_grad, bool density)
 {
+    if (!c->fresh.forward()) return fail(c, S2D_E_STATE, "the backward pass needs s2d_forward on the current parameters");
+    if (!c->d_loss_grad) S2D_HIP(c, c->d_loss_grad.alloc(slab_pixels(c)));
+    if (int rc = queue_loss(c, cfg, c->d_loss_grad, TermRing::slot_of(c->iterations), c->trace.job(c->iterations).out)) return rc;
+    if (int rc = queue_backward(c, need_opacity_grad, c->d_loss_grad, density)) return rc;
+    return backward_queued(c, SqerrBy::LossPass);
+}
+
+// The `terms` sums of a loss pass (kLossTerms, or kWeightedTerms under a plane) -> the means and the total; a term with
+// weight 0 was not formed.  sums[0] is the squared error on the 255 scale, which t.mse reports; the last three of either are
+// the squared error the total counts (without a plane sums[0] once more, under one omega * it), the sum of |d| and that of 1 - s.
+s2d_loss_terms loss_terms_of(const s2d_ctx* c, int terms, const double* sums, const float* w, double* weighted_mse)
+{
+    const double* last = sums + terms - 3;
     const double n3 = mse_norm(c);
     s2d_loss_terms t;
-    t.mse = sums4[0] / (255.0 * 255.0) / n3;
-    const double wmse = sums4[1] / (255.0 * 255.0) / n3;
-    t.l1 = w[1] > 0.0f ? sums4[2] / n3 : std::nan("");
-    t.dssim = w[2] > 0.0f ? sums4[3] / n3 : std::nan("");
+    t.mse = sums[0] / (255.0 * 255.0) / n3;
+    const double wmse = last[0] / (255.0 * 255.0) / n3;
+    t.l1 = w[1] > 0.0f ? last[1] / n3 : std::nan("");
+    t.dssim = w[2] > 0.0f ? last[2] / n3 : std::nan("");
     t.total = 0.0;
     if (w[0] > 0.0f) t.total += (double)w[0] * 0.5 * wmse;
     if (w[1] > 0.0f) t.total += (double)w[1] * t.l1;
@@ -84,31 +98,8 @@ s2d_loss_terms weighted_loss_terms_of(const s2d_ctx* c, const double* sums4, con
     return t;
 }
 
-// s2d_backward for the loss: the loss kernels into the context's gradient image, the backward walk from it, and the
-// squared error of the iteration in the ring as the loss finalize left it (SqerrBy::LossPass).
-int queue_loss_backward(s2d_ctx* c, const s2d_loss_config* cfg, bool need_opacity_grad, bool density)
-{
-    if (!c->fresh.forward()) return fail(c, S2D_E_STATE, "the backward pass needs s2d_forward on the current parameters");
-    if (!c->d_loss_grad) S2D_HIP(c, c->d_loss_grad.alloc(slab_pixels(c)));
-    if (int rc = queue_loss(c, cfg, c->d_loss_grad, LossTrace::slot_of(c->iterations), c->trace.job(c->iterations).out)) return rc;
-    if (int rc = queue_backward(c, need_opacity_grad, c->d_loss_grad, density)) return rc;
-    return backward_queued(c, SqerrBy::LossPass);
-}
-
-// Sums of a loss pass (squared error on the 255 scale, |d|, 1 - s) -> the means and the total; a term with weight 0 was not formed.
-s2d_loss_terms loss_terms_of(const s2d_ctx* c, const double* sums, const float* w)
-{
-    const double n3 = mse_norm(c);
-    s2d_loss_terms t;
-    t.mse = sums[0] / (255.0 * 255.0) / n3;
-    t.l1 = w[1] > 0.0f ? sums[1] / n3 : std::nan("");
-    t.dssim = w[2] > 0.0f ? sums[2] / n3 : std::nan("");
-    t.total = 0.0;
-    if (w[0] > 0.0f) t.total += (double)w[0] * 0.5 * t.mse;
-    if (w[1] > 0.0f) t.total += (double)w[1] * t.l1;
-    if (w[2] > 0.0f) t.total += (double)w[2] * t.dssim;
-    return t;
-}
+// The ring the loss passes of the context write now: the four totals under a plane, the three without.
+const TermRing& current_ring(const s2d_ctx* c) { return c->weights.set() ? c->weights.ring : c->loss.ring; }
 
 extern "C" {
 
@@ -118,7 +109,7 @@ int s2d_loss_image_grads_device(s2d_ctx* c, const s2d_loss_config* cfg, float* d
     if (int rc = loss_refused(c, cfg)) return rc;
     if ((uintptr_t)dimage_rows_device & 15u) return fail(c, S2D_E_INVALID, "the image gradient must be 16-byte aligned");
     if (int rc = use_device(c)) return rc;
-    return queue_loss(c, cfg, reinterpret_cast<float4*>(dimage_rows_device), LossTrace::kEvalSlot, nullptr);
+    return queue_loss(c, cfg, reinterpret_cast<float4*>(dimage_rows_device), TermRing::kEvalSlot, nullptr);
 }
 
 int s2d_loss_backward(s2d_ctx* c, const s2d_loss_config* cfg, uint32_t flags)
@@ -136,15 +127,10 @@ int s2d_loss_get(s2d_ctx* c, s2d_loss_terms* out)
     if (!c || !out) return S2D_E_INVALID;
     if (c->loss.last_slot() < 0) return fail(c, S2D_E_STATE, "no loss pass has run yet");
     if (int rc = use_device(c)) return rc;
-    if (c->weights.set()) { // (a pass older than the plane is forgotten when the plane is set: the last one was a weighted one)
-        double sums4[kWeightedTerms];
-        if (int rc = read_back(c, sums4, c->weights.slot(c->loss.last_slot()), sizeof(sums4))) return rc;
-        *out = weighted_loss_terms_of(c, sums4, c->loss.last_weights(), nullptr);
-        return S2D_OK;
-    }
-    double sums[3];
-    if (int rc = read_back(c, sums, c->loss.slot(c->loss.last_slot()), sizeof(sums))) return rc;
-    *out = loss_terms_of(c, sums, c->loss.last_weights());
+    const TermRing& ring = current_ring(c); // (a pass older than the plane is forgotten when the plane is set: the last one was a weighted one)
+    double sums[kWeightedTerms];
+    if (int rc = read_back(c, sums, ring.slot(c->loss.last_slot()), (size_t)ring.terms() * sizeof(double))) return rc;
+    *out = loss_terms_of(c, ring.terms(), sums, c->loss.last_weights());
     return S2D_OK;
 }
 

@@ -98,9 +98,9 @@ int s2d_weighted_loss_get(s2d_ctx* c, s2d_weighted_terms* out)
     if (c->loss.last_slot() < 0) return fail(c, S2D_E_STATE, "no loss pass has run under the current pixel weights");
     if (int rc = use_device(c)) return rc;
     double sums4[kWeightedTerms];
-    if (int rc = read_back(c, sums4, c->weights.slot(c->loss.last_slot()), sizeof(sums4))) return rc;
+    if (int rc = read_back(c, sums4, c->weights.ring.slot(c->loss.last_slot()), sizeof(sums4))) return rc;
     double wmse = 0.0;
-    const s2d_loss_terms t = weighted_loss_terms_of(c, sums4, c->loss.last_weights(), &wmse);
+    const s2d_loss_terms t = loss_terms_of(c, kWeightedTerms, sums4, c->loss.last_weights(), &wmse);
     out->reserved = 0;
     out->weight_sum = c->weights.sum();
     out->mse = wmse; out->l1 = t.l1; out->dssim = t.dssim; out->total = t.total;

@@ -40,46 +40,62 @@ struct LossArgs {
 };
 inline int loss_slots(int W, int H) { return ((W + kLossTile - 1) / kLossTile) * ((H + kLossTile - 1) / kLossTile); }
 hipError_t launch_loss(const LossArgs& a, hipStream_t stream);
+const LossWindow& loss_window(); // the one window of every loss pass, built on first use (s2d_loss.hip)
 
-// What the loss passes of a context leave: per-tile partial sums, and the totals of every iteration in a ring beside the
-// squared-error ring (slot iteration % kCapacity), plus one slot for a pass that belongs to no iteration
-// (s2d_loss_image_grads_device).  Allocated by the first loss pass.
-class S2D_LOCAL LossTrace {
+// The totals of a pass: kLossTerms of them (squared error on the 255 scale, |d|, 1 - s), or under a weight plane
+// (s2d_loss_weighted.h) kWeightedTerms: the squared error unweighted, then omega * that, omega * |d|, omega * (1 - s).
+constexpr int kLossTerms = 3, kWeightedTerms = 4;
+
+// Per-tile partial sums of `terms` terms, and their totals of every iteration in a ring beside the squared-error ring (slot
+// iteration % kCapacity), plus one slot for a pass that belongs to no iteration (s2d_loss_image_grads_device).  Allocated by
+// the first ensure().
+class S2D_LOCAL TermRing {
 public:
     static constexpr int kCapacity = 1 << 16;
     static constexpr int kEvalSlot = kCapacity; // of the pass that formed a gradient image alone
+    static int slot_of(int iteration) { return iteration % kCapacity; }
 
+    explicit TermRing(int terms) : terms_((size_t)terms) {}
+    int terms() const { return (int)terms_; }
     hipError_t ensure(int W, int H, hipStream_t stream)
     {
         stream_ = stream;
         if (ring_) return hipSuccess;
-        hipError_t e = partial_.alloc((size_t)3 * (size_t)loss_slots(W, H));
-        if (e == hipSuccess) e = ring_.alloc((size_t)3 * (kCapacity + 1));
-        if (e == hipSuccess) e = hipMemsetAsync(ring_, 0, (size_t)3 * (kCapacity + 1) * sizeof(double), stream);
+        hipError_t e = partial_.alloc(terms_ * (size_t)loss_slots(W, H));
+        if (e == hipSuccess) e = ring_.alloc(terms_ * (kCapacity + 1));
+        if (e == hipSuccess) e = hipMemsetAsync(ring_, 0, terms_ * (kCapacity + 1) * sizeof(double), stream);
         return e;
     }
     double* partial() const { return partial_; }
-    double* slot(int s) const { return ring_ + (size_t)3 * (size_t)s; }
-    static int slot_of(int iteration) { return iteration % kCapacity; }
-    // The three totals of the iterations [first, first + count) -> out (3 doubles each), queued.
+    double* slot(int s) const { return ring_ + terms_ * (size_t)s; }
+    // The totals of the iterations [first, first + count) -> out (terms() doubles each), queued.
     hipError_t read(int first, int count, double* out) const
     {
         for (int got = 0; got < count;) {
             const int s = slot_of(first + got), run = std::min(count - got, kCapacity - s);
-            const hipError_t e = hipMemcpyAsync(out + (size_t)3 * got, slot(s), (size_t)3 * run * sizeof(double), hipMemcpyDeviceToHost, stream_);
+            const hipError_t e = hipMemcpyAsync(out + terms_ * got, slot(s), terms_ * run * sizeof(double), hipMemcpyDeviceToHost, stream_);
             if (e != hipSuccess) return e;
             got += run;
         }
         return hipSuccess;
     }
+
+private:
+    const size_t terms_;
+    hipStream_t stream_ = nullptr;
+    DevBuf<double> partial_, ring_;
+};
+
+// What the loss passes of a context leave: the ring of the three totals, and which pass was the last.
+class S2D_LOCAL LossTrace {
+public:
+    TermRing ring{kLossTerms};
     // A pass has been queued into slot `s` with these weights: what s2d_loss_get reports.
     void record(int s, float w_mse, float w_l1, float w_dssim) { last_ = s, w_[0] = w_mse, w_[1] = w_l1, w_[2] = w_dssim; }
     int last_slot() const { return last_; } // -1: no loss pass yet
     const float* last_weights() const { return w_; }
 
 private:
-    hipStream_t stream_ = nullptr;
-    DevBuf<double> partial_, ring_;
     int last_ = -1;
     float w_[3] = {0.0f, 0.0f, 0.0f};
 };

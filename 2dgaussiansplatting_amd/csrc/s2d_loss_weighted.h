@@ -2,15 +2,13 @@
 // launch declarations of s2d_loss_weighted.hip and the owner of what a plane brings to a context.
 //
 //   L_omega = sum over pixels p of omega(p) * sum over channels of  w_mse * 1/2 * d^2 + w_l1 * |d| + w_dssim * (1 - s)
-// The kernels are those of s2d_loss.hip with one multiply by omega per stored map value and per pointwise term, and a
-// fourth sum: a plane of ones gives the unweighted kernels' bytes, gradient image and totals.
+// The kernels are the bodies of s2d_loss.hip's (s2d_loss_kernels.h) with one multiply by omega per stored map value and per
+// pointwise term, and a fourth sum: a plane of ones gives the unweighted kernels' bytes, gradient image and totals.
 #pragma once
 
 #include "s2d_loss.h"
 
 namespace s2d {
-
-constexpr int kWeightedTerms = 4; // squared error (255 scale) unweighted, then omega * that, omega * |d|, omega * (1 - s)
 
 // One weighted loss pass.  base: as for launch_loss, but base.partial and base.out3 are not the unweighted pass's:
 // partial4 holds kWeightedTerms x slots doubles, out4 the four totals; base.out3 (the slot of the unweighted ring, so that
@@ -28,15 +26,14 @@ hipError_t launch_loss_weighted(const WeightedLossArgs& a, hipStream_t stream);
 inline size_t weight_check_slots(size_t pixels) { return (pixels + 1023) / 1024; }
 hipError_t launch_weight_check(const float* plane, size_t pixels, double* partial, double* out2, hipStream_t stream);
 
-// What a plane brings to a context: the plane itself, the per-tile partial sums of a weighted pass and the ring of the four
-// totals of every iteration beside LossTrace's (same slots, same capacity).  Everything is allocated by the first plane.
+// What a plane brings to a context: the plane itself, and the ring of the four totals of every iteration beside LossTrace's
+// (same slots, same capacity).  Everything is allocated by the first plane.
 class S2D_LOCAL PixelWeights {
 public:
+    TermRing ring{kWeightedTerms};
     bool set() const { return set_; }
     double sum() const { return set_ ? sum_ : 0.0; }
     const float* plane() const { return plane_; }
-    double* partial() const { return partial_; }
-    double* slot(int s) const { return ring_ + (size_t)kWeightedTerms * (size_t)s; }
 
     // A buffer for a candidate plane and the scratch of its check.  The candidate becomes the plane with adopt(), and only then.
     hipError_t candidate(size_t pixels, float** plane, double** partial, double** out2)
@@ -48,12 +45,7 @@ public:
     }
     hipError_t adopt(int W, int H, double sum, hipStream_t stream)
     {
-        stream_ = stream;
-        if (!ring_) {
-            S2D_TRY(partial_.alloc((size_t)kWeightedTerms * (size_t)loss_slots(W, H)));
-            S2D_TRY(ring_.alloc((size_t)kWeightedTerms * (LossTrace::kCapacity + 1)));
-            S2D_TRY(hipMemsetAsync(ring_, 0, (size_t)kWeightedTerms * (LossTrace::kCapacity + 1) * sizeof(double), stream));
-        }
+        S2D_TRY(ring.ensure(W, H, stream));
         plane_ = std::move(candidate_); // (the old plane goes with the candidate's owner: no stream uses it, the check was waited for)
         candidate_.release();
         sum_ = sum, set_ = true;
@@ -65,22 +57,10 @@ public:
         plane_.release();
         set_ = false;
     }
-    // The four totals of the iterations [first, first + count) -> out (4 doubles each), queued.
-    hipError_t read(int first, int count, double* out) const
-    {
-        for (int got = 0; got < count;) {
-            const int s = LossTrace::slot_of(first + got), run = std::min(count - got, LossTrace::kCapacity - s);
-            S2D_TRY(hipMemcpyAsync(out + (size_t)kWeightedTerms * got, slot(s), (size_t)kWeightedTerms * run * sizeof(double),
-                                   hipMemcpyDeviceToHost, stream_));
-            got += run;
-        }
-        return hipSuccess;
-    }
 
 private:
-    hipStream_t stream_ = nullptr;
     DevBuf<float> plane_, candidate_;
-    DevBuf<double> partial_, ring_, check_;
+    DevBuf<double> check_;
     double sum_ = 0.0;
     bool set_ = false;
 };

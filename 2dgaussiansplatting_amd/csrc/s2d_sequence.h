@@ -14,6 +14,7 @@
 
 #include "../../include/splat2d.h"
 #include "s2d_device.h"
+#include "s2d_loss.h"
 #include "s2d_owned.h"
 #include "s2d_state.h"
 
@@ -68,12 +69,15 @@ S2D_LOCAL int parse_walk_flags(s2d_ctx* c, uint32_t flags, bool step, WalkFlags*
 // s2d_step (loss == nullptr) and s2d_step_loss.  The loss passes of the latter are s2d_api_loss.hip's:
 S2D_LOCAL int run_steps(s2d_ctx* c, int iters, uint32_t flags, const s2d_loss_config* loss, double* loss_out, double* mse_out);
 S2D_LOCAL int queue_loss_backward(s2d_ctx* c, const s2d_loss_config* cfg, bool need_opacity_grad, bool density);
-S2D_LOCAL s2d_loss_terms loss_terms_of(const s2d_ctx* c, const double* sums, const float* w);
-// Under a pixel-weight plane (include/splat2d_weights.h; s2d_api_loss.hip): what the context refuses a plane for, the backward
-// pass of s2d_backward / s2d_step (the weighted loss pass with weights (1, 0, 0), then the walk), and the terms of four sums.
+// The ring the context's loss passes write now (the four totals under a pixel-weight plane, the three without), and the terms
+// of one entry of it (weighted_mse: the mean the total counts, which under a plane is not t.mse).
+S2D_LOCAL const s2d::TermRing& current_ring(const s2d_ctx* c);
+S2D_LOCAL s2d_loss_terms loss_terms_of(const s2d_ctx* c, int terms, const double* sums, const float* w,
+                                       double* weighted_mse = nullptr);
+// Under a pixel-weight plane (include/splat2d_weights.h; s2d_api_loss.hip): what the context refuses a plane for, and the backward
+// pass of s2d_backward / s2d_step (the weighted loss pass with weights (1, 0, 0), then the walk).
 S2D_LOCAL int weights_refused_by_context(s2d_ctx* c, const char* who);
 S2D_LOCAL int queue_weighted_backward(s2d_ctx* c, bool need_opacity_grad, bool density);
-S2D_LOCAL s2d_loss_terms weighted_loss_terms_of(const s2d_ctx* c, const double* sums4, const float* w, double* weighted_mse);
 
 S2D_LOCAL int queue_status_read(s2d_ctx* c); // -> h_status, valid once the stream has been synchronised
 S2D_LOCAL int check_status(s2d_ctx* c);      // ... read, waited for and judged

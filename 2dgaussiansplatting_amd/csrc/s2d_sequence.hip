@@ -391,7 +391,7 @@ int check_status(s2d_ctx* c)
 // errors (and loss totals) read back per piece, the status word judged once at the end.
 int run_steps(s2d_ctx* c, int iters, uint32_t flags, const s2d_loss_config* loss, double* loss_out, double* mse_out)
 {
-    static_assert(LossTrace::kCapacity == SqerrTrace::kCapacity, "one piece size for both rings");
+    static_assert(TermRing::kCapacity == SqerrTrace::kCapacity, "one piece size for both rings");
     WalkFlags wf;
     if (int rc = parse_walk_flags(c, flags, true, &wf)) return rc;
     if (int rc = use_device(c)) return rc;
@@ -401,6 +401,7 @@ int run_steps(s2d_ctx* c, int iters, uint32_t flags, const s2d_loss_config* loss
     if (weighted)
         if (int rc = weights_refused_by_context(c, loss ? "s2d_step_loss" : "s2d_step")) return rc;
     if (weighted && !loss) loss = &mse_only;
+    const TermRing& ring = current_ring(c); // (the plane cannot change within the call)
     const double norm = mse_norm(c);
     const float w[3] = {loss ? loss->w_mse : 0.0f, loss ? loss->w_l1 : 0.0f, loss ? loss->w_dssim : 0.0f};
     const int call_first_iter = c->iterations;
@@ -426,16 +427,15 @@ int run_steps(s2d_ctx* c, int iters, uint32_t flags, const s2d_loss_config* loss
         const bool with_status = done + piece == iters && piece <= SqerrTrace::kPinned;
         double* const mse_dst = !mse_out ? nullptr : with_status ? c->trace.pinned() : mse_out + done;
         if (loss_out) {
-            sums.resize((size_t)(weighted ? kWeightedTerms : 3) * piece);
-            S2D_HIP(c, weighted ? c->weights.read(first_iter, piece, sums.data()) : c->loss.read(first_iter, piece, sums.data()));
+            sums.resize((size_t)ring.terms() * piece);
+            S2D_HIP(c, ring.read(first_iter, piece, sums.data()));
         }
         if (mse_dst) S2D_HIP(c, c->trace.read(first_iter, piece, mse_dst));
         if (with_status)
             if (int rc = queue_status_read(c)) return rc;
         if (with_status || loss_out || mse_out) S2D_HIP(c, hipStreamSynchronize(c->stream));
         for (int k = 0; loss_out && k < piece; k++)
-            loss_out[done + k] = weighted ? weighted_loss_terms_of(c, &sums[(size_t)kWeightedTerms * k], w, nullptr).total
-                                          : loss_terms_of(c, &sums[(size_t)3 * k], w).total;
+            loss_out[done + k] = loss_terms_of(c, ring.terms(), &sums[(size_t)ring.terms() * k], w).total;
         for (int k = 0; mse_out && k < piece; k++) mse_out[done + k] = mse_dst[k] / norm; // main.cpp:805
         status_read = with_status;
         done += piece;

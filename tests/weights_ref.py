@@ -16,6 +16,7 @@ import math
 import numpy as np
 
 import loss_ref as LR
+import oracle_lib as O
 
 SIZES = {"7x5": (7, 5), "40x1": (40, 1), "33x17": (33, 17), "96x80": (96, 80)}
 WEIGHTINGS = [(1.0, 0.0, 0.0), (0.0, 0.8, 0.2), (0.5, 0.3, 0.2)]
@@ -144,6 +145,25 @@ def plane(kind, W, H, seed=0):
     if kind == "ones":
         return np.ones((H, W), dtype=np.float32)
     raise KeyError(kind)
+
+
+RANDOM_SCENES = {"7x5": (7, 5, 20, 14), "40x1": (40, 1, 30, 13), "33x17": (33, 17, 200, 11), "96x80": (96, 80, 300, 12)}  # W, H, splats, seed
+
+
+def noise_scene(size):
+    """-> (target (H, W, 4) float32, splats as SPLAT_DTYPE records) of a size of SIZES: the random-splat scene on the noise
+    target that tests/test_gpu_pixel_weights.py draws under the same name, number for number."""
+    W, H, n, seed = RANDOM_SCENES[size]
+    rng = np.random.default_rng(seed)
+    s = np.zeros(n, dtype=O.SPLAT_DTYPE)
+    s["pos"][:, 0] = rng.uniform(0, W - 1, n)
+    s["pos"][:, 1] = rng.uniform(0, H - 1, n)
+    s["sx"] = rng.uniform(1.0, 6.0, n)
+    s["sy"] = rng.uniform(1.0, 6.0, n)
+    s["rot"] = rng.uniform(-np.pi, np.pi, n)
+    s["color"] = rng.uniform(0, 1, (n, 3))
+    s["opacity"] = rng.uniform(0.1, 1.0, n)
+    return np.ascontiguousarray(LR.noise_image(W, H, 100 + seed), dtype=np.float32), s
 
 
 def image_pair(W, H, content, seed):

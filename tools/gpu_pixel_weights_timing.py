@@ -2,13 +2,13 @@
 10^6 splats from init() after a few iterations:
 
   (a) the loss pass alone (s2d_loss_image_grads_device) for the weightings (1, 0, 0) and (0, 0.8, 0.2): under a plane, without
-      one, and -- with --parent-lib -- without one on a build of the parent commit, each in a process of its own, one after
-      the other in the same session;
+      one, and -- with --parent-lib -- both again on a build of the parent commit (which must have the plane's symbols: a
+      process that fails ends the series), tree and parent alternating, each in a process of its own, one after the other in the same session;
   (b) one iteration: s2d_step under a plane against s2d_step_loss (1, 0, 0) without one (the same separate launches), and the
       plain fused s2d_step beside them.
 
     python tools/gpu_pixel_weights_timing.py [--size 4096] [--splats 1000000] [--reps 9] [--parent-lib build/libsplat2d_hip_parent.so]
-                                             [--out profiles/r28/pixel_weights_timing.json]
+                                             [--out profiles/r29/pixel_weights_timing_1.json]
 
 Wall clock around `calls` queued calls and one wait for the stream, per repetition; medians (min - max) in ms per call.
 """
@@ -90,8 +90,9 @@ def main():
         print("RESULT " + json.dumps(measure(a.role, a.size, a.splats, a.reps, a.calls)))
         return 0
     runs = [("tree, plane", "plane", None), ("tree, no plane", "plain", None)]
-    if a.parent_lib:
-        runs.append(("parent, no plane", "plain", os.path.abspath(a.parent_lib)))
+    if a.parent_lib:   # tree and parent alternating, role by role
+        parent = os.path.abspath(a.parent_lib)
+        runs = [runs[0], ("parent, plane", "plane", parent), runs[1], ("parent, no plane", "plain", parent)]
     result = {"command": " ".join(sys.argv), "size": a.size, "splats": a.splats, "reps": a.reps, "calls": a.calls, "ms_per_call": {}}
     for label, role, lib in runs:   # one process after the other: never two on the card at once
         env = dict(os.environ)
